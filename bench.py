@@ -11,8 +11,12 @@ as `other_post_form`; --post split: three dispatches.)
 
 The HEADLINE (`metric`, `value`, `ms_per_step`, `roofline`) is --config cfg3, BASELINE config 3, the configuration the metric is quoted on:
 a 3840x2160 tile per GPU, 64 point lights + the full-size cfg4 IBL; N > 1 is WEAK scaling (frame 3840 x 2160*N). K timed steps, exactly.
+A plain invocation does only that: set-up, untimed spin-up and W warm-up steps, the K timed steps, the line. --dump-outputs DIR also writes what the
+last timed step delivered (dump_outputs) before the line is printed.
 
-Every invocation (N = 1 included) ALSO times, outside the headline's timed region and reported as extra objects of the same JSON line:
+--full ALSO measures everything below and the self-audit figures of the headline (cold start, the isolated post kernels, per-stage events,
+frame latency, the other Fresnel-pow mode and the DXC reading, the CPU baselines). It ALSO times, outside the headline's timed region and reported as
+extra objects of the same JSON line:
   cfg5_strong    BASELINE config 5, the configuration the ">= 6x at 8 GPUs" target is defined on: ONE 7680x4320 frame, 256 point lights
                  (100 cbuffer + 156 extension), 4320/N rows per GPU — STRONG scaling; with shade / halo / composite / latency figures
   (N = 1 only)
@@ -23,7 +27,7 @@ Every invocation (N = 1 included) ALSO times, outside the headline's timed regio
                  SSR environment fallback — ms, algorithmic bytes per pixel, fraction of the HBM spec
   coherent_scene the cfg3 frame on surface-coherent content (synth.gbuffer_rows_coherent) instead of white noise — never the headline
   tile_curve     per-tile step time of the cfg5 frame at 4320/N rows, N = 1, 2, 4, 8, on this one GPU + a labelled MODELLED speed-up
---config cfg5 makes cfg5 the headline instead (then `scaling` is "strong"); --no-extras skips everything but the headline.
+--config cfg5 makes cfg5 the headline instead (then `scaling` is "strong"); with --full, --no-extras skips the extra objects again.
 
 Every byte that crosses GPUs goes through the C ABI (include/vqhip.h, vqengine_amd/csrc/mgpu.hip); torch.distributed is the control
 plane only (communicator-id broadcast, barriers, the max-over-ranks reduction of the wall time).
@@ -35,6 +39,7 @@ import argparse
 import ctypes as C
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -116,10 +121,11 @@ def upload_tile(cfg, frame_h, row0, row1, coherent=False):
 
 
 def launch_ranks(n):
-    """`python bench.py --gpus N` without a launcher: bench.py starts its own N ranks (one per GPU) by replacing itself with
-    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>`;
-    rank 0 prints the one JSON line, the exit status is the launcher's. Refuses — non-zero, with a message — when the node has fewer than N GPUs
-    (VQ_BENCH_SHARE_GPU=1, the single-GPU debug aid, lifts that: the ranks then share the visible GPUs)."""
+    """`python bench.py --gpus N` without a launcher: bench.py starts its own N ranks (one per GPU) as a child process
+    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>`
+    (not by replacing itself: this process has already opened the GPU); rank 0 prints the one JSON line, the exit status is the launcher's. Refuses —
+    non-zero, with a message — when the node has fewer than N GPUs (VQ_BENCH_SHARE_GPU=1, the single-GPU debug aid, lifts that: the ranks then share the
+    visible GPUs)."""
     import socket
     have = torch.cuda.device_count()
     if have < n and os.environ.get("VQ_BENCH_SHARE_GPU") != "1":
@@ -133,7 +139,7 @@ def launch_ranks(n):
            os.path.abspath(__file__)] + sys.argv[1:]
     print(f"bench.py: no launcher in the environment (WORLD_SIZE unset): starting {n} ranks: {' '.join(cmd[1:9])} ...", file=sys.stderr, flush=True)
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
 class Dist:
@@ -508,19 +514,45 @@ def measure_strong(pipe, steps, warmup):
     return out
 
 
+DUMP_PIXELS = 1 << 20           # --dump-outputs: at most this many pixels per image (16 MB as float32 RGBA), a fixed seeded sample of larger images
+DUMP_SEED = 0xD0
+
+
+def dump_outputs(dirname, pipe, i):
+    """--dump-outputs DIR: what step i of the timed path delivered, as DIR/<name>.npy (float32, one row of channels per pixel): at N = 1 the frame
+    (RGBA8, tonemapped) and the scene colour it was made from (RGBA16F), the buffer pair of step i; at N > 1 the composited RGBA8 frame on rank 0.
+    An image of more than DUMP_PIXELS pixels is sampled at the same DUMP_PIXELS pixel indices (sorted, seeded) in every run with the same arguments."""
+    b = i & 1
+    if pipe.d.world == 1:
+        imgs = {"frame_rgba8": pipe.sdr[b], "scene_color_rgba16f": pipe.scene[b]}
+    else:
+        imgs = {"frame_rgba8": pipe.frame[b]} if pipe.d.rank == 0 else {}
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in imgs.items():
+        px = t.reshape(-1, t.shape[-1])
+        if px.shape[0] > DUMP_PIXELS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(px.shape[0], DUMP_PIXELS, replace=False))
+            px = px[torch.from_numpy(idx).to(px.device)]
+        np.save(os.path.join(dirname, name + ".npy"), px.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)      # a step is ~1 ms: 0.2 s of timed GPU work; the run stays dominated by set-up and the CPU baselines
+    ap.add_argument("--steps", type=int, default=200)      # a step is ~1 ms: 0.2 s of timed GPU work
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--config", choices=["cfg3", "cfg5"], default="cfg3", help="the HEADLINE workload (the other BASELINE configs are reported as extra objects)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: skip cfg5_strong / cfg2 / ibl_load / coherent_scene / tile_curve")
+    ap.add_argument("--config", choices=["cfg3", "cfg5"], default="cfg3", help="the HEADLINE workload (with --full the other BASELINE configs are reported as extra objects)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: its self-audit figures (cold start, isolated post kernels, per-stage events, frame latency), the other "
+                         "Fresnel-pow mode and the DXC reading, the CPU baselines and the extra objects (cfg5_strong, cfg2, ibl_load, ...)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step delivered as DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip cfg5_strong / cfg2 / ibl_load / coherent_scene / tile_curve")
     ap.add_argument("--post", choices=["chain", "fused", "split"], default="chain",
                     help="post chain: blur X + blur Y + tonemapper in ONE kernel (chain: vqhip_post_process_tile, the library's default for frames of >= 2^20 pixels), "
                          "blur X then Y blur + tonemapper in one kernel (fused), or three dispatches (split); identical bits")
     ap.add_argument("--post-stream", choices=["main", "own", "frames"], default="own",
-                    help="N = 1 with --post chain: the post chain of frame i on a stream of its own, next to the shade kernel of frame i + 1 (double-buffered scene colour; + 1.5 %: "
+                    help="N = 1 with --post chain: the post chain of frame i on a stream of its own, next to the shade kernel of frame i + 1 (double-buffered scene colour; + 1.5 %%: "
                          "profiles/r5y_post_stream_ab.txt), or on the main stream (main). N > 1 keeps the main stream (the composite is what overlaps the next frame there)")
     ap.add_argument("--composite", choices=["root", "all"], default="root",
                     help="final composite of the RGBA8 tiles: on rank 0 only (the presenting GPU; it receives over its N-1 direct xGMI links) or on every rank")
@@ -531,7 +563,7 @@ def main():
     ap.add_argument("--fresnel-pow", choices=["product", "exp2_log2"], default="product",
                     help="pow(1 - cos, 5) of the Fresnel terms: the product x*((x*x)*(x*x)) (default, contract v4) or exp2(5*log2 x), the engine's own "
                          "DXC lowering (vqhip_set_fresnel_pow; DESIGN.md 3.2). The other mode is timed too and reported as `engine_lowering`.")
-    ap.add_argument("--no-second-mode", action="store_true", help="skip the timing of the other Fresnel-pow mode")
+    ap.add_argument("--no-second-mode", action="store_true", help="with --full: skip the timing of the other Fresnel-pow mode and of the DXC reading")
     ap.add_argument("--content", choices=["noise", "coherent"], default="noise",
                     help="noise: the BASELINE workload (white-noise G-buffer, SURVEY.md 8d). coherent: the same frame size on surface-coherent content; the line is "
                          "then NOT the headline (metric and data say so) — used to collect counters for `coherent_scene` (scripts/pmc_refresh.sh)")
@@ -541,6 +573,8 @@ def main():
         raise SystemExit("bench.py needs a GPU: the product path has no CPU fallback")
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args.gpus)                              # does not return
     d = Dist(args)
@@ -552,7 +586,7 @@ def main():
         wiring_check(d, comms, ctx)
 
     ibl_t = {}
-    pre, lut = build_ibl(ctx, ibl_t if (world == 1 and not args.no_extras) else None)     # cfg4: the headline's IBL inputs (cfg3) — and, timed, `ibl_load`
+    pre, lut = build_ibl(ctx, ibl_t if (world == 1 and args.full and not args.no_extras) else None)     # cfg4: the headline's IBL inputs (cfg3) — and, timed, `ibl_load`
     env = capi.make_envmap(pre["diffuse_blurred"], pre["specular"], 128, pre["spec_mips"], lut)
     root = 0 if args.composite == "root" else capi.ALL_RANKS
     pipe = Pipeline(ctx, d, comms, cfg, args, env=env if cfg["env"] else None, max_env_lod=pre["spec_mips"] if cfg["env"] else 0, composite_root=root,
@@ -569,20 +603,20 @@ def main():
             wiring_check(d, comms, ctx)
     overlap = comms.overlap
 
-    # 1. cold start: the very first steps after the idle set-up phase, timed on their own (the chip has not ramped its clocks yet)
-    dt_cold = pipe.timed(COLD_STEPS)
+    # 1. (--full) cold start: the very first steps after the idle set-up phase, timed on their own (the chip has not ramped its clocks yet)
+    dt_cold = pipe.timed(COLD_STEPS) if args.full else None
     # 2. untimed spin-up: the chip needs ~0.2-0.3 s of sustained load to reach its steady-state clocks, so a fixed number of extra
-    #    untimed steps precedes the W warm-up steps whatever W is. The timed region is still exactly K steps.
-    for i in range(max(0, SPINUP_STEPS - COLD_STEPS)):
+    #    untimed steps precedes the W warm-up steps whatever W is (the cold-start steps count as part of it). The timed region is still exactly K steps.
+    for i in range(max(0, SPINUP_STEPS - (COLD_STEPS if args.full else 0))):
         pipe.step(i)
     pipe.drain()
-    # 2b. the post kernels on their own, after the spin-up and before the warm-up: 20 back-to-back launches of each between two events, on the
+    # 2b. (--full) the post kernels on their own, after the spin-up and before the warm-up: 20 back-to-back launches of each between two events, on the
     #     frame's own buffers (no event, no other kernel in between). In the frame loop each of them follows a kernel that has just filled the
     #     caches with other data, and the per-stage events sit inside the intervals they measure; both figures are reported. (Taken here rather
     #     than after the timed region: after ~0.4 s of sustained shading a burst of X passes runs 2.5-3x slower — the chip's power limiter,
     #     profiles/r2k_frame_loop.md — which says nothing about the kernel.)
     iso = None
-    if args.post in ("chain", "fused"):
+    if args.post in ("chain", "fused") and args.full:
         iso = {}
         if args.post == "chain":
             st = _stage_stats(lambda: ctx.post_process_tile(pipe.scene[0], F16, R8, out=pipe.sdr[0], halo_top=pipe.halo_top, halo_bottom=pipe.halo_bottom), spin_s=0.01)
@@ -606,27 +640,32 @@ def main():
     #    HBM-bound post kernels are taken in a separate, untimed pass afterwards so their instrumentation does not sit in `value`
     evs = [{"t0": _ev(), "shade": _ev()} for _ in range(args.steps)]
     dt = pipe.timed(args.steps, evs)
+    if args.dump_outputs:                                    # before any later step reuses the buffers (or runs another mode)
+        dump_outputs(args.dump_outputs, pipe, args.steps - 1)
 
-    n_detail = min(args.steps, 10)
-    keys = ["t0", "shade", "x", "halo", "post"] + (["y"] if args.post == "split" else []) + (["comp0", "comp1"] if world > 1 else [])
-    evd = [{k: _ev() for k in keys} for _ in range(n_detail)]
-    for i in range(n_detail):
-        pipe.step(args.steps + i + (args.steps & 1), evd[i])
-    pipe.drain()
-    d.barrier()
-    # the chain as a whole, without an event between its kernels: `shade` after the shade kernel ... `post` after the last post kernel
-    evc = [{"shade": _ev(), "post": _ev()} for _ in range(n_detail)]
-    for i in range(n_detail):
-        pipe.step(args.steps + i + (args.steps & 1), evc[i])
-    pipe.drain()
-    d.barrier()
-    # 4. frame latency: one step at a time, nothing in flight before or after it
-    frame_latency = pipe.latency()
+    # 3b. (--full) per-stage events: `evd` with an event between the stages, `evc` the chain as a whole, without an event between its kernels
+    #     (`shade` after the shade kernel ... `post` after the last post kernel)
+    evd = evc = frame_latency = None
+    if args.full:
+        n_detail = min(args.steps, 10)
+        keys = ["t0", "shade", "x", "halo", "post"] + (["y"] if args.post == "split" else []) + (["comp0", "comp1"] if world > 1 else [])
+        evd = [{k: _ev() for k in keys} for _ in range(n_detail)]
+        for i in range(n_detail):
+            pipe.step(args.steps + i + (args.steps & 1), evd[i])
+        pipe.drain()
+        d.barrier()
+        evc = [{"shade": _ev(), "post": _ev()} for _ in range(n_detail)]
+        for i in range(n_detail):
+            pipe.step(args.steps + i + (args.steps & 1), evc[i])
+        pipe.drain()
+        d.barrier()
+        # 4. frame latency: one step at a time, nothing in flight before or after it
+        frame_latency = pipe.latency()
 
     # 4b. sustained run: the same step for ~SUSTAINED_S seconds without interruption — a long-window cross-check of `value` (thousands of steps instead
     #     of K) and a stretch of GPU activity an outside observer (rocm-smi, the driver's clock) can see; never the headline
     sustained = None
-    if not args.no_extras and SUSTAINED_S > 0:
+    if args.full and not args.no_extras and SUSTAINED_S > 0:
         n_sus = int(min(20000, max(200, SUSTAINED_S / (dt / args.steps))))         # the same on every rank: dt is the max over ranks
         n_sus += n_sus & 1                                                         # the double-buffered composite alternates buffers
         dt_sus = pipe.timed(n_sus)
@@ -636,7 +675,7 @@ def main():
 
     # 4c. the OTHER form of the post chain (two kernels when the headline runs the one-kernel chain, and vice versa), same frame loop, same clocks: a companion figure
     chain_alt = None
-    if args.post in ("chain", "fused") and not args.no_extras:
+    if args.post in ("chain", "fused") and args.full and not args.no_extras:
         mine, other = args.post, ("fused" if args.post == "chain" else "chain")
         args.post = other
         for i in range(10):
@@ -660,7 +699,7 @@ def main():
     #     the next frame's — the reference's own habit (three back buffers, SwapChain.h). A companion figure, not the headline: with two shade kernels on the chip at once a launch
     #     lasts twice as long, and the per-kernel roofline / rocprofv3 figures of the line would stop describing the kernel
     frames2 = None
-    if world == 1 and args.post == "chain" and args.post_stream != "frames" and not args.no_extras:
+    if world == 1 and args.post == "chain" and args.post_stream != "frames" and args.full and not args.no_extras:
         mine = args.post_stream
         args.post_stream = "frames"
         for i in range(10):
@@ -715,7 +754,7 @@ def main():
 
     # 5. the other Fresnel-pow lowering, same invocation, same clocks: `engine_lowering` is the engine-faithful exp2(5*log2 x) form
     second = None
-    if not args.no_second_mode:
+    if args.full and not args.no_second_mode:
         other = "exp2_log2" if args.fresnel_pow == "product" else "product"
         ctx.set_fresnel_pow(other == "exp2_log2")
         for i in range(20):
@@ -729,7 +768,7 @@ def main():
     # 5b. the other READING of dot / normalize (vqhip_set_arithmetic): DXC's lowering — FMA-chain dot, v * correctly rounded rsqrt — with the exp2/log2
     # Fresnel power, i.e. the second build of the reference's sources (tests/golden/ref_outputs_dxc.npz); same invocation, same clocks
     dxc = None
-    if not args.no_second_mode:
+    if args.full and not args.no_second_mode:
         ctx.set_arithmetic(True); ctx.set_fresnel_pow(True)
         for i in range(20):
             pipe.step(i)
@@ -746,7 +785,7 @@ def main():
     # 6. the other BASELINE configs, outside the headline's timed region (every rank takes part in the distributed ones)
     extras = {}
     pf_head, extra_head, pv_head = pipe.pf, pipe.extra, pipe.pv
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         x_steps = max(4, min(args.steps, 20))
         if args.config != "cfg5":
             pipe.free()
@@ -779,13 +818,14 @@ def main():
     if rank == 0:
         px_tile, px_frame = W * rows, W * frame_h
         t_shade = mean_ms(evs, "t0", "shade") * 1e-3
-        if args.post == "split":
-            t_blur, t_tm = mean_ms(evd, "shade", "y") * 1e-3, mean_ms(evd, "y", "post") * 1e-3
-        else:
-            t_blur, t_tm = mean_ms(evd, "shade", "halo") * 1e-3, mean_ms(evd, "halo", "post") * 1e-3
-        t_chain = mean_ms(evc, "shade", "post") * 1e-3
         own_stream = args.post == "chain" and world == 1 and args.post_stream == "own"
-        t_chain_alone = iso["post_chain"] if (own_stream and iso and "post_chain" in iso) else t_chain
+        if args.full:
+            if args.post == "split":
+                t_blur, t_tm = mean_ms(evd, "shade", "y") * 1e-3, mean_ms(evd, "y", "post") * 1e-3
+            else:
+                t_blur, t_tm = mean_ms(evd, "shade", "halo") * 1e-3, mean_ms(evd, "halo", "post") * 1e-3
+            t_chain = mean_ms(evc, "shade", "post") * 1e-3
+            t_chain_alone = iso["post_chain"] if (own_stream and iso and "post_chain" in iso) else t_chain
         ach = SHADE_BYTES_PER_PX * px_tile / t_shade / 1e9
         flops_px = 170 * L + 160
         pmc, pmc_meta = load_pmc_constants(args.config + ("_coherent" if args.content == "coherent" else ""), args.fresnel_pow)
@@ -799,7 +839,7 @@ def main():
             "config": {"workload": cfg["workload"] + ("" if world == 1 else f"; frame {W}x{frame_h} row-tiled {rows} rows per GPU, RCCL p2p halo exchange + composite on "
                                                        f"{'rank 0' if root == 0 else 'every rank'} through the C ABI"),
                        "name": args.config, "width": W, "frame_height": frame_h, "tile_rows": rows, "lights": L, "parallelism": f"rows{world}",
-                       "composite_overlap": overlap, "untimed_spinup_steps": SPINUP_STEPS + (SPINUP_STEPS // 2 if args.post in ("chain", "fused") else 0), "fresnel_pow": args.fresnel_pow,
+                       "composite_overlap": overlap, "untimed_spinup_steps": SPINUP_STEPS + (SPINUP_STEPS // 2 if iso is not None else 0), "fresnel_pow": args.fresnel_pow,
                        "post_stream": ("own: the post chain of frame i runs on a second stream next to the shade kernel of frame i + 1 (double-buffered); frame_latency_ms is one frame alone"
                                        if (args.post == "chain" and world == 1 and args.post_stream == "own") else "main"),
                        "post": {"chain": "blur X, blur Y and the tonemapper in ONE kernel (identical bits to three dispatches)",
@@ -817,7 +857,7 @@ def main():
             "pmc_constants": pmc_meta,
             "rccl": comms.info(),
             "stages": {"shade_Mpix_s": round(px_tile / t_shade / 1e6, 1), "shade_ms": round(t_shade * 1e3, 4),
-                       **({"blur_xy_ms": round(t_blur * 1e3, 4), "blur_xy_GBps": round(px_tile * 32 / t_blur / 1e9, 1),
+                       **({} if not args.full else {"blur_xy_ms": round(t_blur * 1e3, 4), "blur_xy_GBps": round(px_tile * 32 / t_blur / 1e9, 1),
                            "tonemap_ms": round(t_tm * 1e3, 4), "tonemap_GBps": round(px_tile * 12 / t_tm / 1e9, 1)} if args.post == "split" else
                           {"post_chain_ms": round(t_chain * 1e3, 4), "post_chain_in_loop_ms": round(t_chain * 1e3, 4), "post_chain_alone_ms": round(t_chain_alone * 1e3, 4),
                            "post_chain_bytes_per_px": 12,
@@ -850,13 +890,13 @@ def main():
                                         "blur_x_ms_spread": iso["blur_x_spread"], "blur_y_tonemap_ms_spread": iso["blur_y_tonemap_spread"],
                                         "note": "median of 7 batches of back-to-back launches of the one kernel (spread = fastest / slowest batch), after the spin-up and before the warm-up steps; "
                                                 "the figures above are taken inside the frame loop with an event record between the stages"}}),
-                       **({"blur_x_includes": "halo exchange", "composite_ms": round(mean_ms(evd, "comp0", "comp1"), 4)} if world > 1 else {})},
-            "frame_latency_ms": round(frame_latency * 1e3, 4),
+                       **({"blur_x_includes": "halo exchange", "composite_ms": round(mean_ms(evd, "comp0", "comp1"), 4)} if world > 1 and args.full else {})},
+            **({"frame_latency_ms": round(frame_latency * 1e3, 4)} if args.full else {}),
             **({"sustained": sustained} if sustained else {}),
             **({"other_post_form": chain_alt} if chain_alt else {}),
             **({"two_frames_in_flight": frames2} if frames2 else {}),
-            "cold_start": {"steps": COLD_STEPS, "ms_per_step": round(dt_cold / COLD_STEPS * 1e3, 4), "value": round(px_frame * COLD_STEPS / dt_cold / 1e6, 2),
-                           "note": "the first steps after the idle set-up phase, before the clocks ramp; `value` is the steady-state figure"},
+            **({"cold_start": {"steps": COLD_STEPS, "ms_per_step": round(dt_cold / COLD_STEPS * 1e3, 4), "value": round(px_frame * COLD_STEPS / dt_cold / 1e6, 2),
+                               "note": "the first steps after the idle set-up phase, before the clocks ramp; `value` is the steady-state figure"}} if args.full else {}),
         }
         if pmc:
             vw, tw = pmc["valu_instr_per_wave"], pmc.get("quarter_rate_instr_per_wave", 0)
@@ -918,7 +958,7 @@ def main():
             if cc:
                 out["coherent_scene"].update(traffic=cc.get("hbm_bytes_per_launch"), valu_instr_per_wave=cc["valu_instr_per_wave"],
                                              traffic_ratio_to_algorithmic=round(cc["hbm_bytes_per_launch"] / (SHADE_BYTES_PER_PX * px_tile), 3) if cc.get("hbm_bytes_per_launch") else None)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             env_np = (pre["diffuse_blurred"].cpu().numpy(), pre["specular"].cpu().numpy(), 128, pre["spec_mips"], lut.cpu().numpy()) if cfg["env"] else None
             if args.fresnel_pow == "exp2_log2":
                 from tests import oracle_lib as _O

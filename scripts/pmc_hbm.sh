@@ -2,16 +2,17 @@
 # HBM traffic of the bench kernels of the CURRENT build from the PMC counters (run on the GPU box): one rocprofv3 pass per
 # counter (FETCH_SIZE and WRITE_SIZE in one pass crashed the tool on this pool), each under its own timeout. Unit: KiB.
 cd /tmp && export TMPDIR=/tmp && cd ${GRAFT_REPO_ROOT:-/root/repo}
+O=${VQ_PROF_OUT:-prof_out}     # where the profiler writes (git-ignored)
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf gpurun_out/pmc_$c
-  timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d gpurun_out/pmc_$c -- python bench.py --no-cpu-baseline --steps 10 --warmup 3 > /dev/null 2>&1
+  rm -rf $O/pmc_$c
+  timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -- python bench.py --full --no-cpu-baseline --steps 10 --warmup 3 > /dev/null 2>&1
   echo "pass $c rc=$?"
 done
 python - <<PY
 import csv, glob, statistics as st, collections
 res = collections.defaultdict(dict)
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
-    fs = glob.glob(f"gpurun_out/pmc_{c}/*/*counter_collection.csv")
+    fs = glob.glob(f"$O/pmc_{c}/*/*counter_collection.csv")
     if not fs:
         print("no output for", c); continue
     by = collections.defaultdict(list)

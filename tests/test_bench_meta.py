@@ -31,7 +31,7 @@ def test_configs_are_the_baseline_ones():
 
 
 def test_every_invocation_reports_the_other_baseline_configs():
-    """the default invocation times cfg5 strong scaling (every N) and cfg2 / cfg4 / the coherent frame / the tile curve (N = 1)
+    """the --full invocation times cfg5 strong scaling (every N) and cfg2 / cfg4 / the coherent frame / the tile curve (N = 1)
     next to the cfg3 headline; source-level check of the wiring (the values need a GPU: tests/test_gpu_bench_flow.py)."""
     src = open(os.path.join(ROOT, "bench.py")).read()
     wid = open(os.path.join(ROOT, "benchlib", "widened.py")).read()         # extras["widened"] = widened_report(...)

@@ -28,7 +28,7 @@ def _run(ranks, extra_args, **more_env):
     script = os.path.join(ROOT, "tests", "bench_fault_harness.py") if "VQ_TEST_FAULT" in more_env else os.path.join(ROOT, "bench.py")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), script, "--gpus", str(ranks), "--steps", "4", "--warmup", "1",
-           "--no-cpu-baseline", "--no-second-mode"] + extra_args
+           "--full", "--no-cpu-baseline", "--no-second-mode"] + extra_args
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -65,7 +65,7 @@ def test_every_post_form_flow_matches_the_untiled_frame(ranks, post):
 
 
 def test_every_run_also_times_cfg5_strong_scaling():
-    """The standard invocation at N = 3: the cfg3 headline (weak) AND the cfg5 strong-scaling object the >= 6x target is defined on
+    """The --full invocation at N = 3: the cfg3 headline (weak) AND the cfg5 strong-scaling object the >= 6x target is defined on
     (one 7680x4320 frame, 256 lights, 1440 rows per rank), with its stage figures and the communicator's own report."""
     d = _run(3, [])
     assert d["config"]["name"] == "cfg3" and d["scaling"] == "weak" and d["verify"]["mismatching_bytes"] == 0
@@ -134,10 +134,10 @@ def test_gpus_n_without_a_launcher_starts_its_own_ranks():
 
 
 def test_single_gpu_line_carries_the_contract_fields():
-    """`python bench.py` (N = 1, defaults shortened): one JSON line with the driver's contract fields, the roofline and cpu_baseline objects,
+    """`python bench.py --full` (N = 1, defaults shortened): one JSON line with the driver's contract fields, the roofline and cpu_baseline objects,
     counter constants that belong to the current kernel sources, and the self-audit extras (engine lowering, cold start, isolated post kernels)."""
     env = dict(os.environ, VQ_BENCH_SPINUP="30", VQ_BENCH_SUSTAINED_S="0.5", VQ_BENCH_VERIFY="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, "bench.py must print exactly one line on stdout"
@@ -207,3 +207,34 @@ def test_single_gpu_line_carries_the_contract_fields():
     assert [t["tile_rows"] for t in tc] == [4320, 2160, 1080, 540] and all(t["step_ms"] > 0 for t in tc)
     assert tc[3]["modelled_speedup_serial_half_link"] <= tc[3]["modelled_speedup_overlapped_peak_link"] <= tc[3]["compute_speedup"]
     assert d["rccl"]["nranks_seen"] == 1
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` (no --full): the headline fields and nothing that takes runs of its own, and the last timed step's
+    frame and scene colour as float32 .npy files (a seeded 2^20-pixel sample of the 4K tile) that two runs with the same arguments reproduce bit for bit."""
+    import numpy as np
+    env = dict(os.environ, VQ_BENCH_SPINUP="30")
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--dump-outputs", str(out)], cwd=ROOT, env=env,
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, "bench.py must print exactly one line on stdout"
+        d = json.loads(lines[0])
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["unit"] == "Mpix/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and "4K,64 lights" in d["metric"]
+        assert d["ms_per_step"] > 0 and abs(d["value"] - 3840 * 2160 / (d["ms_per_step"] * 1e-3) / 1e6) < 0.01 * d["value"]
+        for k2 in ("cfg5_strong", "cfg2", "ibl_load", "widened", "cpu_baseline", "engine_lowering", "dxc_lowering", "cold_start", "sustained", "frame_latency_ms"):
+            assert k2 not in d, k2
+        files = sorted(os.listdir(out))
+        assert files == ["frame_rgba8.npy", "scene_color_rgba16f.npy"], files
+        arrs = {f: np.load(out / f) for f in files}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        for a in arrs.values():
+            assert a.dtype == np.float32 and a.shape == (1 << 20, 4)
+        fr = arrs["frame_rgba8.npy"]
+        assert np.isfinite(fr).all() and fr.min() >= 0 and fr.max() <= 255 and (fr == np.round(fr)).all() and fr[:, :3].std() > 1
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f].view(np.uint32), dumps[1][f].view(np.uint32)), f
