@@ -341,7 +341,8 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
 #define VQHIP_ABI_VERSION 3   /* 3 (round 5): + vqhip_post_process_tile; options blur_x_wgs / blur_y_form / blur_y_rows removed, post_form / post_strips added.
                                * 2 (round 4): + vqhip_set_arithmetic, vqhip_set_option, vqhip_ssr_environment_fallback, VQHIP_FMT_R10G10B10A2_UNORM; conv order default SEQUENTIAL;
                                * later in round 4, additions only: vqhip_forward_lighting_mrt, vqhip_forward_lighting_from_materials_mrt, vqhip_scene_normals_from_materials,
-                               * vqhip_composite_reflections; vqhip_visualize reads R10G10B10A2 / RG16F / RG32F inputs */
+                               * vqhip_composite_reflections; vqhip_visualize reads R10G10B10A2 / RG16F / RG32F inputs.
+                               * Later additions to 3: vqhip_gbuffer_msaa, vqhip_forward_lighting_msaa */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -385,6 +386,40 @@ VQHIP_API int vqhip_forward_lighting_mrt(vqhip_ctx* ctx, void* stream,
         const VQ_PointLight* extraPoint, int numExtraPoint,
         const vqhip_envmap* env, const vqhip_shadowmaps* sm,
         void* out, int out_row_pitch_px, vqhip_format outFmt, const vqhip_psmain_targets* targets);
+
+/* ---- 4x MSAA scene colour (docs/DESIGN_DETAILS.md §7.9) -----------------------------------------------------------------
+ * Replaces the bMSAA branch of RenderSceneColor (the lit draw into the 4-sample Tex_SceneColorMSAA, MSAA_SAMPLE_COUNT = 4,
+ * RenderResources.h:26, RenderResources.cpp:114-130, targets picked at SceneRendering.cpp:1644-1650) AND VQRenderer::ResolveMSAA's
+ * ResolveSubresource of that target (SceneRendering.cpp:2060-2112): PSMain declares no sample / centroid inputs, so it runs once per
+ * (pixel, primitive) and its result goes to every sample the primitive covers. The caller supplies up to 4 fragment layers:
+ *   layer[k]    : a full vqhip_gbuffer (same planes and meaning as vqhip_forward_lighting; same width / height in every used layer,
+ *                 own row_pitch_px each)
+ *   coverage[k] : uint8 [height][coverage_pitch]; bit s (0..3) = "the fragment of layer k covers sample s" (D3D's standard 4x pattern),
+ *                 bits 4-7 ignored. Any masks are valid: sample s is owned by the LOWEST layer k < layers whose mask has bit s, else it is
+ *                 background. A layer that owns no sample of a pixel is not shaded there (its record may hold anything, NaN included).
+ * Sample value: owned = shade_pixel(record of the owner) stored in outFmt (RGBA16F RNE | RGBA32F); background = background[p] (a plane in
+ * outFmt, background_pitch_px pixels per row, e.g. the skydome drawn into it; must not be `out`) or (0,0,0,0) when background == NULL
+ * (the clear value, SceneRendering.cpp:1660-1669). Resolve per channel: r = (((s0 + s1) + s2) + s3) * 0.25f in binary32 with the samples
+ * widened from outFmt, stored to outFmt (RNE for RGBA16F); NaN / Inf propagate. A pixel whose four samples share one owner therefore holds
+ * exactly the RGBA16F bits vqhip_forward_lighting writes for that record. Pitches in pixels; coverage_pitch in bytes (0 = width).
+ * vqhip_set_arithmetic / vqhip_set_fresnel_pow apply as for vqhip_forward_lighting. The context keeps an edge-pixel list of 4 + 4*width*height
+ * bytes (grown on demand: a growth waits for the device); calls on different streams are ordered on it by an event, nothing else synchronises. */
+#define VQHIP_MSAA_MAX_LAYERS 4
+typedef struct vqhip_gbuffer_msaa {
+    vqhip_gbuffer  layer[VQHIP_MSAA_MAX_LAYERS];     /* same width / height in every used layer; own row_pitch_px each */
+    const uint8_t* coverage[VQHIP_MSAA_MAX_LAYERS];  /* [height][coverage_pitch] sample masks, bit s = sample s */
+    int32_t        layers;                           /* 1..4; entries >= layers are ignored */
+    int32_t        coverage_pitch;                   /* bytes per row, 0 = width */
+} vqhip_gbuffer_msaa;
+VQHIP_STATIC_ASSERT(sizeof(vqhip_gbuffer) == 48, "vqhip_gbuffer");
+VQHIP_STATIC_ASSERT(sizeof(vqhip_gbuffer_msaa) == 232 && offsetof(vqhip_gbuffer_msaa, coverage) == 192 &&
+                    offsetof(vqhip_gbuffer_msaa, layers) == 224 && offsetof(vqhip_gbuffer_msaa, coverage_pitch) == 228, "vqhip_gbuffer_msaa layout");
+VQHIP_API int vqhip_forward_lighting_msaa(vqhip_ctx* ctx, void* stream, const vqhip_gbuffer_msaa* gb,
+        const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
+        const VQ_PointLight* extraPoint, int numExtraPoint,
+        const vqhip_envmap* env, const vqhip_shadowmaps* sm,
+        const void* background, int background_pitch_px,      /* NULL = clear value 0 */
+        void* out, int out_row_pitch_px, vqhip_format outFmt);  /* RGBA16F | RGBA32F */
 
 /* Replaces the GaussianBlur.hlsl CSMain_X / CSMain_Y dispatches (EnvironmentMapRendering.cpp:279-373,
  * SceneRendering.cpp:2582-2638): 21-tap separable Gaussian, clamp-to-edge, alpha := 1.

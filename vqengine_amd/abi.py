@@ -123,6 +123,13 @@ class PsmainTargets(C.Structure):    # vqhip_psmain_targets: the lit draw's othe
 
 assert C.sizeof(PsmainTargets) == 56
 
+MSAA_MAX_LAYERS = 4   # VQHIP_MSAA_MAX_LAYERS
+MSAA_SAMPLE_POSITIONS = ((-2, -6), (6, -2), (-6, 2), (2, 6))   # D3D's standard 4x pattern, in 1/16 pixel from the pixel centre; sample s = bit s of a coverage byte
+
+
+class GBufferMSAA(C.Structure):   # vqhip_gbuffer_msaa: up to 4 fragment layers + their per-pixel sample masks (vqhip_forward_lighting_msaa)
+    _fields_ = [("layer", GBuffer * MSAA_MAX_LAYERS), ("coverage", C.c_void_p * MSAA_MAX_LAYERS), ("layers", C.c_int32), ("coverage_pitch", C.c_int32)]
+
 class CommInfo(C.Structure):    # vqhip_comm_info
     _fields_ = [("world", C.c_int32), ("rank", C.c_int32), ("nranks_seen", C.c_int32), ("rank_seen", C.c_int32),
                 ("rccl_version", C.c_int32), ("reserved", C.c_int32), ("library_path", C.c_char * 232)]
@@ -189,6 +196,8 @@ _chk(PerViewLightingData, 320, WorldFrustumPlanes=192, CameraPosition=288, MaxEn
 _chk(MaterialData, 80, uvScaleOffset=48, roughness=64, textureConfig=76)
 _chk(Texture2D, 24, width=8, mips=16)
 _chk(MaterialDesc, 256, texDiffuse=80, texLocalAO=224)
+_chk(GBuffer, 48, width=32, row_pitch_px=40)
+_chk(GBufferMSAA, 232, coverage=192, layers=224, coverage_pitch=228)
 _chk(TonemapperParams, 16)
 _chk(BlurParams, 8)
 _chk(SSSRConstants, 512, bufferDimensions=448, roughnessThreshold=472, envMapSpecularIrradianceCubemapMipLevelCount=504)

@@ -44,6 +44,8 @@ def load_library():
                                          vp, i32, C.POINTER(abi.EnvMap), C.POINTER(abi.ShadowMaps), vp, i32, i32]),
         "vqhip_forward_lighting_mrt": (i32, [vp, vp, C.POINTER(abi.GBuffer), C.POINTER(abi.PerFrameData), C.POINTER(abi.PerViewLightingData),
                                              vp, i32, C.POINTER(abi.EnvMap), C.POINTER(abi.ShadowMaps), vp, i32, i32, C.POINTER(abi.PsmainTargets)]),
+        "vqhip_forward_lighting_msaa": (i32, [vp, vp, C.POINTER(abi.GBufferMSAA), C.POINTER(abi.PerFrameData), C.POINTER(abi.PerViewLightingData),
+                                              vp, i32, C.POINTER(abi.EnvMap), C.POINTER(abi.ShadowMaps), vp, i32, vp, i32, i32]),
         "vqhip_gaussian_blur": (i32, [vp, vp, vp, vp, vp, C.POINTER(abi.BlurParams), i32]),
         "vqhip_gaussian_blur_x": (i32, [vp, vp, vp, vp, C.POINTER(abi.BlurParams), i32]),
         "vqhip_gaussian_blur_y": (i32, [vp, vp, vp, vp, vp, vp, i32, C.POINTER(abi.BlurParams), i32]),
@@ -119,7 +121,7 @@ EXPORTED_SYMBOLS = [
     "vqhip_skydome", "vqhip_unlit_composite", "vqhip_set_fresnel_pow", "vqhip_set_arithmetic", "vqhip_set_option", "vqhip_hdr_parse_header", "vqhip_hdr_decode_rgba32f", "vqhip_hdr_downsize_rgba32f",
     "vqhip_fsr_easu_con", "vqhip_fsr_rcas_con", "vqhip_fsr_easu", "vqhip_fsr_rcas", "vqhip_visualize", "vqhip_apply_reflections", "vqhip_composite_reflections", "vqhip_ssr_environment_fallback",
     "vqhip_rowtile", "vqhip_comm_unique_id", "vqhip_comm_create", "vqhip_comm_adopt", "vqhip_comm_destroy", "vqhip_comm_query", "vqhip_comm_abort", "vqhip_comm_loopback", "vqhip_exchange_blur_halos",
-    "vqhip_composite_tiles",
+    "vqhip_composite_tiles", "vqhip_forward_lighting_msaa",
 ]
 
 
@@ -351,6 +353,35 @@ class Context:
                 C.byref(shadow) if shadow is not None else None, _ptr(out), out.shape[1], out_fmt)
         rc = self.lib.vqhip_forward_lighting(*args) if _targets is None else self.lib.vqhip_forward_lighting_mrt(*args, C.byref(_targets))
         self._ck(rc)
+        return out
+
+    def forward_lighting_msaa(self, layers, coverage, per_frame, per_view, background=None, out=None, out_fmt=FMT_RGBA16F, extra_point=None, env=None,
+                              shadow=None, stream=None):
+        """4x MSAA lit draw + resolve (vqhip_forward_lighting_msaa). layers: 1..4 G-buffers, each a tuple of 4 float32 cuda tensors [H,W,4];
+        coverage: one uint8 cuda tensor [H,W] per layer (bit s = the layer's fragment covers sample s); background: None (clear value 0) or an
+        out_fmt image [H,W,4] (e.g. the skydome). Returns the resolved image."""
+        if not 1 <= len(layers) <= abi.MSAA_MAX_LAYERS or len(coverage) != len(layers):
+            raise ValueError(f"forward_lighting_msaa: 1..{abi.MSAA_MAX_LAYERS} layers, one coverage plane each (got {len(layers)} and {len(coverage)})")
+        h, w = layers[0][0].shape[0], layers[0][0].shape[1]
+        g = abi.GBufferMSAA()
+        g.layers, g.coverage_pitch = len(layers), w
+        for k, (gb, cov) in enumerate(zip(layers, coverage)):
+            for i, p in enumerate(gb):
+                _check_img(p, FMT_RGBA32F, f"layer {k} gb{i}", (h, w))
+            if not (cov.is_cuda and cov.is_contiguous() and cov.dtype == torch.uint8 and tuple(cov.shape) == (h, w)):
+                raise ValueError(f"coverage {k}: expected contiguous cuda uint8 tensor of shape {(h, w)}, got {tuple(cov.shape)} {cov.dtype} {cov.device}")
+            g.layer[k] = abi.GBuffer(gb[0].data_ptr(), gb[1].data_ptr(), gb[2].data_ptr(), gb[3].data_ptr(), w, h, w)
+            g.coverage[k] = cov.data_ptr()
+        if background is not None:
+            _check_img(background, out_fmt, "background", (h, w))
+        if out is None:
+            out = empty_image(h, w, out_fmt, self.device)
+        _check_img(out, out_fmt, "out", (h, w))
+        n_extra = len(extra_point) if extra_point is not None else 0
+        extra_ptr = C.cast(extra_point, C.c_void_p) if n_extra else C.c_void_p(None)
+        self._ck(self.lib.vqhip_forward_lighting_msaa(self._h, self._stream(stream), C.byref(g), C.byref(per_frame), C.byref(per_view), extra_ptr, n_extra,
+                                                      C.byref(env) if env is not None else None, C.byref(shadow) if shadow is not None else None,
+                                                      _ptr(background), w, _ptr(out), w, out_fmt))
         return out
 
     # ---- post-process (RenderPostProcess, SceneRendering.cpp:2507) ------------------------------------------

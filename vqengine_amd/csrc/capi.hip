@@ -33,6 +33,9 @@ struct vqhip_ctx {
     // footprint records of the diffuse convolution (conv.hip:k_diffuse_records): rewritten by every vqhip_conv_diffuse; `recFree` is recorded behind the
     // kernel that reads them, and the next call's stream waits for it before it overwrites them (calls may come on different streams)
     void* rec = nullptr; size_t recBytes = 0; hipEvent_t recFree = nullptr; bool recUsed = false;
+    // edge-pixel list of vqhip_forward_lighting_msaa (msaa.hip): a counter + 4 B per pixel. Its own buffer, not `scratch` (the post chain's two-kernel form keeps
+    // BlurIntermediate there, possibly on another stream next to shading); `edgeFree` is recorded behind the kernel that reads it, the next call's stream waits for it
+    void* edge = nullptr; size_t edgeBytes = 0; hipEvent_t edgeFree = nullptr; bool edgeUsed = false;
     int pow5ExpLog = 0;            // vqhip_set_fresnel_pow
     int arithDxc = 0;              // vqhip_set_arithmetic
     vqk::Options opt;              // vqhip_set_option
@@ -278,6 +281,8 @@ void vqhip_destroy(vqhip_ctx* ctx) {
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->rec) (void)hipFree(ctx->rec);
     if (ctx->recFree) (void)hipEventDestroy(ctx->recFree);
+    if (ctx->edge) (void)hipFree(ctx->edge);
+    if (ctx->edgeFree) (void)hipEventDestroy(ctx->edgeFree);
     for (int i = 0; i < vqhip_ctx::kLuts; ++i) {
         if (ctx->lut[i].table) (void)hipFree(ctx->lut[i].table);
         if (ctx->lut[i].built) (void)hipEventDestroy(ctx->lut[i].built);
@@ -456,6 +461,67 @@ int vqhip_forward_lighting_mrt(vqhip_ctx* ctx, void* stream, const vqhip_gbuffer
     a.arithDxc = ctx->arithDxc;
     hipError_t e = launch_forward_lighting(st, a, env != nullptr, casters, outFmt, ctx->opt);
     if (e != hipSuccess) return failHip(ctx, e, "forward_lighting launch");
+    return releaseSlot(ctx, slot, st);
+}
+
+int vqhip_forward_lighting_msaa(vqhip_ctx* ctx, void* stream, const vqhip_gbuffer_msaa* gb,
+        const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
+        const VQ_PointLight* extraPoint, int numExtraPoint,
+        const vqhip_envmap* env, const vqhip_shadowmaps* sm,
+        const void* background, int background_pitch_px,
+        void* out, int out_row_pitch_px, vqhip_format outFmt) {
+    vqk::Range range_("RenderSceneColor");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "forward_lighting_msaa: ctx is NULL");
+    CTX_GUARD(ctx, "forward_lighting_msaa");
+    if (!gb || !out) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_msaa: NULL argument");
+    if (gb->layers < 1 || gb->layers > VQHIP_MSAA_MAX_LAYERS) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_msaa: layers must be 1..4");
+    const int W = gb->layer[0].width, H = gb->layer[0].height;
+    if (W <= 0 || H <= 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_msaa: bad dimensions");
+    if ((uint64_t)W * (uint64_t)H > 0xFFFFFFFFull) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "forward_lighting_msaa: more than 2^32 - 1 pixels");
+    const int covPitch = gb->coverage_pitch ? gb->coverage_pitch : W;
+    if (covPitch < W || out_row_pitch_px < W || (background && background_pitch_px < W))
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_msaa: pitch below the width");
+    if (background && background == out) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_msaa: background must not be out");
+    MsaaArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (int k = 0; k < gb->layers; ++k) {
+        const vqhip_gbuffer& g = gb->layer[k];
+        if (!g.gb0 || !g.gb1 || !g.gb2 || !g.gb3 || !gb->coverage[k])
+            return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_msaa: NULL plane or coverage of layer " + std::to_string(k));
+        if (g.width != W || g.height != H) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_msaa: layers of different sizes");
+        if (g.row_pitch_px < W) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_msaa: pitch below the width");
+        a.L[k].gb0 = (const float4*)g.gb0; a.L[k].gb1 = (const float4*)g.gb1; a.L[k].gb2 = (const float4*)g.gb2; a.L[k].gb3 = (const float4*)g.gb3;
+        a.L[k].cov = gb->coverage[k]; a.L[k].pitch = g.row_pitch_px;
+    }
+    bool casters = false;
+    int rc = validateLighting(ctx, "forward_lighting_msaa", perFrame, perView, extraPoint, numExtraPoint, env, sm, outFmt, &casters);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    // the edge list: the previous call's kernels (maybe on another stream) are done with it before this stream touches it
+    const size_t edgeNeed = 4 + 4 * (size_t)W * (size_t)H;
+    if (ctx->edgeUsed) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->edgeFree, 0));
+    if (ctx->edgeBytes < edgeNeed) {
+        if (ctx->edge) { HIP_TRY(ctx, hipDeviceSynchronize()); HIP_TRY(ctx, hipFree(ctx->edge)); ctx->edge = nullptr; ctx->edgeBytes = 0; }
+        HIP_TRY(ctx, hipMalloc(&ctx->edge, edgeNeed));
+        ctx->edgeBytes = edgeNeed;
+    }
+    if (!ctx->edgeFree) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->edgeFree, hipEventDisableTiming));
+    int slot;
+    rc = acquireSlot(ctx, &slot);
+    if (rc) return rc;
+    const size_t bytes = fillFrameConstants(ctx, slot, perFrame, perView, extraPoint, numExtraPoint, env, sm);
+    rc = commitSlot(ctx, slot, bytes, st);
+    if (rc) return rc;
+    a.bg = background; a.out = out;
+    a.fc = (const FrameConstants*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
+    a.edgeCount = (uint32_t*)ctx->edge; a.edgeList = (uint32_t*)ctx->edge + 1;
+    a.width = W; a.height = H; a.layers = gb->layers; a.covPitch = covPitch; a.bgPitch = background_pitch_px; a.outPitch = out_row_pitch_px;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->edge, 0, 4, st));
+    hipError_t e = launch_forward_lighting_msaa(st, a, env != nullptr, casters, outFmt, ctx->arithDxc, ctx->nCUs);
+    if (e != hipSuccess) return failHip(ctx, e, "forward_lighting_msaa launch");
+    HIP_TRY(ctx, hipEventRecord(ctx->edgeFree, st));
+    ctx->edgeUsed = true;
     return releaseSlot(ctx, slot, st);
 }
 

@@ -144,6 +144,19 @@ struct SsrArgs {
 };
 hipError_t launch_ssr_env_fallback(hipStream_t s, const SsrArgs& a, int sceneFmt, int normalFmt, int outFmt);
 
+// 4x MSAA lit draw + resolve (vqhip_forward_lighting_msaa, msaa.hip). Edge pixels (samples with more than one owner) are listed by the
+// shading kernel in edgeList[0 .. *edgeCount) as y * width + x; *edgeCount is zeroed on the call's stream before the launch.
+struct MsaaLayer { const float4* gb0; const float4* gb1; const float4* gb2; const float4* gb3; const uint8_t* cov; int pitch; };
+struct MsaaArgs {
+    MsaaLayer L[VQHIP_MSAA_MAX_LAYERS];
+    const void* bg;             // background plane in the output format, NULL = (0,0,0,0)
+    void* out;
+    const FrameConstants* fc;   // device
+    uint32_t* edgeCount; uint32_t* edgeList;
+    int width, height, layers, covPitch, bgPitch, outPitch;
+};
+hipError_t launch_forward_lighting_msaa(hipStream_t s, const MsaaArgs& a, bool hasEnv, bool hasCasters, int outFmt, int arithDxc, int nCUs);
+
 // launchers (each returns the hipError_t of the launch)
 hipError_t launch_forward_lighting(hipStream_t s, const ShadeArgs& a, bool hasEnv, bool hasCasters, int outFmt, const Options& opt);
 hipError_t launch_blur_x(hipStream_t s, const void* in, void* out, int W, int H, int fmt, const Options& opt);

@@ -457,3 +457,59 @@ def ssr_surfaces(width, height, seed=0x55E7, sky_fraction=0.1):
     packed = (q[..., 0] | (q[..., 1] << 10) | (q[..., 2] << 20) | (np.uint32(3) << 30)).astype(np.uint32)
     n01 = np.concatenate([q.astype(np.float32) / np.float32(1023.0), np.ones((height, width, 1), np.float32)], axis=-1)
     return scene, depth, packed, n01
+
+
+def gbuffer_msaa(width, height, layers=2, split_fraction=0.05, seed=0x4A4A, mode="edges"):
+    """Fragment layers of a 4x MSAA frame for vqhip_forward_lighting_msaa: (list of `layers` G-buffers as from gbuffer(), list of uint8 [H,W]
+    coverage planes). mode "edges": layer 0 is gbuffer(width, height, seed); the others are other records. Random discs and triangles
+    (straight edges), each given one of the layers, are painted over layer 0 and evaluated at D3D's standard 4x sample positions
+    (abi.MSAA_SAMPLE_POSITIONS): the masks are disjoint and leave no gap, and shapes are added until about `split_fraction` of the
+    pixels have samples of more than one layer (0: every mask of layer 0 is 0xF). mode "random": arbitrary coverage bytes."""
+    if not 1 <= layers <= abi.MSAA_MAX_LAYERS:
+        raise ValueError("layers must be 1..4")
+    gbs = [gbuffer(width, height, seed=seed if k == 0 else (seed + 0x9E37 * k) & 0xFFFFFFFF) for k in range(layers)]
+    rng = np.random.default_rng(seed)
+    if mode == "random":
+        return gbs, [rng.integers(0, 256, (height, width), dtype=np.uint8) for _ in range(layers)]
+    if mode != "edges":
+        raise ValueError(f"unknown mode {mode!r}")
+    ids = np.zeros((height, width, 4), np.int8)                         # layer of each sample
+    split = np.zeros((height, width), bool)
+    n_split = 0
+    target = split_fraction * width * height
+    if layers > 1 and split_fraction > 0:
+        pos = np.array(abi.MSAA_SAMPLE_POSITIONS, np.float64) / 16.0
+        # shape size: about 200 shapes reach the target (a boundary of length l splits about l pixels), small enough for the
+        # fraction (the boundaries of overlapping shapes saturate near 0.8 / radius); a bounded number of tries
+        size = max(1.5, min(16.0, 0.5 / split_fraction, target / (200 * 2 * np.pi)))
+        for _ in range(200000):
+            if n_split >= target:
+                break
+            cx, cy = rng.uniform(0, width), rng.uniform(0, height)
+            r = size * rng.uniform(0.5, 1.5)
+            x0, x1 = max(0, int(cx - r) - 1), min(width, int(cx + r) + 2)
+            y0, y1 = max(0, int(cy - r) - 1), min(height, int(cy + r) + 2)
+            if x0 >= x1 or y0 >= y1:
+                continue
+            sx = (np.arange(x0, x1) + 0.5)[None, :, None] + pos[None, None, :, 0]
+            sy = (np.arange(y0, y1) + 0.5)[:, None, None] + pos[None, None, :, 1]
+            sx, sy = np.broadcast_arrays(sx, sy)
+            if rng.random() < 0.5:                                      # disc
+                inside = (sx - cx) ** 2 + (sy - cy) ** 2 < r * r
+            else:                                                       # triangle: three straight edges
+                a = rng.uniform(0, 2 * np.pi) + np.array([0.0, 2.1, 4.2]) + rng.uniform(-0.4, 0.4, 3)
+                vx, vy = cx + r * np.cos(a), cy + r * np.sin(a)
+                inside = np.ones(sx.shape, bool)
+                for i in range(3):
+                    j = (i + 1) % 3
+                    inside &= (vx[j] - vx[i]) * (sy - vy[i]) - (vy[j] - vy[i]) * (sx - vx[i]) > 0
+            blk = ids[y0:y1, x0:x1]
+            blk[inside] = rng.integers(0, layers)
+            now = (blk != blk[..., :1]).any(-1)
+            n_split += int(now.sum()) - int(split[y0:y1, x0:x1].sum())
+            split[y0:y1, x0:x1] = now
+    cov = [np.zeros((height, width), np.uint8) for _ in range(layers)]
+    for s in range(4):
+        for k in range(layers):
+            cov[k] |= ((ids[..., s] == k).astype(np.uint8) << s)
+    return gbs, cov
