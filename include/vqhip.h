@@ -342,7 +342,7 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * 2 (round 4): + vqhip_set_arithmetic, vqhip_set_option, vqhip_ssr_environment_fallback, VQHIP_FMT_R10G10B10A2_UNORM; conv order default SEQUENTIAL;
                                * later in round 4, additions only: vqhip_forward_lighting_mrt, vqhip_forward_lighting_from_materials_mrt, vqhip_scene_normals_from_materials,
                                * vqhip_composite_reflections; vqhip_visualize reads R10G10B10A2 / RG16F / RG32F inputs.
-                               * Later additions to 3: vqhip_gbuffer_msaa, vqhip_forward_lighting_msaa */
+                               * Later additions to 3: vqhip_gbuffer_msaa, vqhip_forward_lighting_msaa; vqhip_msaa_surfaces, vqhip_msaa_resolve_surfaces, vqhip_depth_hierarchy (+ _bytes, _level_offset_bytes) */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -420,6 +420,83 @@ VQHIP_API int vqhip_forward_lighting_msaa(vqhip_ctx* ctx, void* stream, const vq
         const vqhip_envmap* env, const vqhip_shadowmaps* sm,
         const void* background, int background_pitch_px,      /* NULL = clear value 0 */
         void* out, int out_row_pitch_px, vqhip_format outFmt);  /* RGBA16F | RGBA32F */
+
+/* ---- 4x MSAA depth / normals / roughness resolve and the depth hierarchy (docs/DESIGN_DETAILS.md §7.10) -------------------
+ * vqhip_msaa_resolve_surfaces replaces DepthMSAAResolvePass (Shaders/DepthResolve.hlsl:CSMain :36-100; VQRenderer::ResolveMSAA_DepthPrePass,
+ * SceneRendering.cpp:1455-1471, called at :484-487; the OUTPUT_ROUGHNESS permutation: call site :2115-2147): from the 4-sample depth and the 4-sample
+ * packed normals, Tex_SceneDepthResolve and Tex_SceneNormals — the `depth` and `normals` arguments of vqhip_ssr_environment_fallback — and the roughness
+ * of the nearest sample into the alpha of the resolved scene colour (its `sceneColorRoughness` argument). Inputs, in the representation of
+ * vqhip_forward_lighting_msaa (layers + coverage masks, same ownership rule: the lowest layer whose mask has bit s owns sample s, no owner = background):
+ *   depth_ms     : float [height][depth_pitch_px][4], 16-byte aligned — the Texture2DMS<float> depth, sample s of a pixel at [..][s]; NDC z, far plane /
+ *                  clear value 1. Producing it stays with the caller (the rasteriser's z), like the interpolant planes.
+ *   coverage[k]  : as vqhip_gbuffer_msaa; read only when outNormals or sceneColor is given
+ *   normals[k]   : layer k's pre-pass normals == what vqhip_scene_normals_from_materials writes for that layer's interpolants, normals_fmt
+ *                  R10G10B10A2_UNORM | RGBA32F (one format for all layers), normals_pitch_px[k] pixels per row. A background sample reads the clear value 0.
+ *                  Read only when outNormals is given.
+ *   roughness[k] : layer k's gb1 plane (float4 per pixel, .w = roughness), roughness_pitch_px[k]; background: the scene colour's background plane (its alpha is a
+ *                  background sample's alpha; NULL = 0) — the two things vqhip_forward_lighting_msaa was given. Read only when sceneColor is given.
+ * Outputs, each optional, at least one required (every one NULL: VQHIP_ERR_INVALID_ARG — the permutation the reference refuses to compile):
+ *   outDepth     : R32F. min(min(min(s0, s1), s2), s3) in binary32 (`half` in that shader is float: the PSO is built without 16-bit types). min is fminf: a NaN
+ *                  sample is dropped, which of +0 / -0 wins is not specified; the tested domain is finite depth in [0, 1].
+ *   outNormals   : R10G10B10A2_UNORM | RGBA32F. Each sample's rgb (UNORM10: c / 1023 correctly rounded) * 2 - 1, summed left to right ((N0 + N1) + N2) + N3,
+ *                  * 0.25, normalize in the reading vqhip_set_arithmetic selects, (+ 1) * 0.5, stored like vqhip_scene_normals_from_materials
+ *                  (trunc(saturate(c) * 1023 + 0.5)). A zero sum normalises to NaN: the UNORM store writes code 0 in all three channels (saturate(NaN) = 0), the
+ *                  RGBA32F store the NaN. The shader writes a float3 to a four-channel UAV — alpha undefined in the reference: 1 is written (alpha bits 3).
+ *   sceneColor   : RGBA16F | RGBA32F, IN PLACE: alpha := the alpha the 4-sample colour target holds at sample iSample — an owned sample: gb1.w of the owner's
+ *                  record stored in sceneFmt (what vqhip_forward_lighting writes), a background sample: the background's alpha. rgb is not touched.
+ *                  iSample starts at 0, then `if (minDepth == s1) iSample = 1; .. s2 ..; .. s3 ..`: on a tie the HIGHEST equal index wins (:59-62).
+ *   hierarchy    : the buffer of vqhip_depth_hierarchy (flags as there). The resolved depth is then not written and re-read: the hierarchy kernel takes "min of
+ *                  the pixel's four samples" as its level-0 load — resolve + level 0 + levels 1-6 in one launch, 16 B/px in. outDepth may be NULL (level 0 IS the
+ *                  resolved depth); outNormals / sceneColor of the same call run as the per-pixel kernel on the same stream.
+ * An output must not alias an input. Pitches in pixels, 0 = width; coverage_pitch in bytes, 0 = width. 4 samples only (DepthMSAAResolve.cpp:73). */
+typedef struct vqhip_msaa_surfaces {
+    const float*   depth_ms;
+    const uint8_t* coverage[VQHIP_MSAA_MAX_LAYERS];
+    const void*    normals[VQHIP_MSAA_MAX_LAYERS];
+    const void*    roughness[VQHIP_MSAA_MAX_LAYERS];
+    const void*    background;
+    int32_t        normals_pitch_px[VQHIP_MSAA_MAX_LAYERS];
+    int32_t        roughness_pitch_px[VQHIP_MSAA_MAX_LAYERS];
+    int32_t        width, height;
+    int32_t        layers;                             /* 1..4 */
+    int32_t        coverage_pitch;
+    int32_t        depth_pitch_px, background_pitch_px;
+    int32_t        normals_fmt;                        /* vqhip_format: R10G10B10A2_UNORM | RGBA32F */
+    int32_t        pad_;
+} vqhip_msaa_surfaces;
+VQHIP_STATIC_ASSERT(sizeof(vqhip_msaa_surfaces) == 176 && offsetof(vqhip_msaa_surfaces, coverage) == 8 && offsetof(vqhip_msaa_surfaces, normals) == 40 &&
+                    offsetof(vqhip_msaa_surfaces, roughness) == 72 && offsetof(vqhip_msaa_surfaces, background) == 104 &&
+                    offsetof(vqhip_msaa_surfaces, normals_pitch_px) == 112 && offsetof(vqhip_msaa_surfaces, roughness_pitch_px) == 128 &&
+                    offsetof(vqhip_msaa_surfaces, width) == 144 && offsetof(vqhip_msaa_surfaces, layers) == 152 &&
+                    offsetof(vqhip_msaa_surfaces, depth_pitch_px) == 160 && offsetof(vqhip_msaa_surfaces, normals_fmt) == 168, "vqhip_msaa_surfaces layout");
+VQHIP_API int vqhip_msaa_resolve_surfaces(vqhip_ctx* ctx, void* stream, const vqhip_msaa_surfaces* in,
+        float* outDepth, int outDepthPitchPx,
+        void* outNormals, vqhip_format outNormalsFmt, int outNormalsPitchPx,
+        void* sceneColor, vqhip_format sceneFmt, int scenePitchPx,
+        float* hierarchy, unsigned flags);
+
+/* Replaces VQRenderer::DownsampleDepth (SceneRendering.cpp:2151-2183, called at :496-499; Shaders/DownsampleDepth.hlsl + FidelityFX SPD): the min-depth pyramid
+ * Tex_DownsampledSceneDepth (R32F, full chain, RenderResources.cpp:95-112) of a single-sample depth plane (MSAA off; an MSAA frame passes `hierarchy` to
+ * vqhip_msaa_resolve_surfaces instead). Writes all L = vqhip_mip_level_count(width, height) levels into `mips`: level 0 first, levels densely packed, level l is
+ * max(1, width >> l) x max(1, height >> l) floats (the convention of vqhip_mip_chain_min_rgba32f); vqhip_depth_hierarchy_bytes sizes the buffer.
+ *   level 0      = a copy of `depth` (depth_pitch_px floats per row, 0 = width);
+ *   level l >= 1 : texel (x, y) = min(min(a, b), min(c, d)) over level l-1 at (2x, 2y), (2x+1, 2y), (2x, 2y+1), (2x+1, 2y+1), where a coordinate outside level l-1
+ *                  reads 0.0 (D3D's out-of-bounds typed load): with floor-halved sizes that happens once one dimension has been clamped to 1 and the other has not
+ *                  (1280 x 720: level 9 is 2 x 1, so level 10 = 0);
+ *   the 1 x 1 top level, default: min(top, 0.0) whenever L <= 12 — the reference hands SPD its number of LEVELS as the number of reductions, and the surplus
+ *                  reduction (the top texel and three out-of-extent neighbours) lands on the last subresource (DownsampleDepth.hlsl:82-85,105;
+ *                  RenderResources.cpp:110-111). That is what the reference's SSR reads.
+ *   flags & VQHIP_DEPTH_HIERARCHY_TRUE_TOP : the 1 x 1 top level holds the minimum over all of level 0 instead (for culling); nothing else changes.
+ * This reading of the out-of-bounds and top-level behaviour comes from the sources and is NOT yet confirmed against a D3D12 run (docs/WARP_CALIBRATION.md).
+ * max(width, height) > 4096: VQHIP_ERR_UNSUPPORTED (the reference's SPD instance covers 12 reductions; above that it produces no pyramid — BASELINE cfg5's
+ * 7680 x 4320 frame is out of range). Two kernel launches (levels 0-6 per 64 x 64 tile, then levels 7+ by one workgroup), one for frames of <= 64 x 64. TRUE_TOP
+ * keeps 16 KiB of per-tile minima in the context; calls on different streams are ordered on it by an event. `mips` must not overlap `depth`. */
+#define VQHIP_DEPTH_HIERARCHY_TRUE_TOP 1u
+#define VQHIP_DEPTH_HIERARCHY_MAX_DIM  4096
+VQHIP_API size_t vqhip_depth_hierarchy_bytes(int width, int height);
+VQHIP_API size_t vqhip_depth_hierarchy_level_offset_bytes(int width, int height, int level);
+VQHIP_API int    vqhip_depth_hierarchy(vqhip_ctx* ctx, void* stream, const float* depth, int depth_pitch_px, int width, int height,
+        float* mips, unsigned flags);
 
 /* Replaces the GaussianBlur.hlsl CSMain_X / CSMain_Y dispatches (EnvironmentMapRendering.cpp:279-373,
  * SceneRendering.cpp:2582-2638): 21-tap separable Gaussian, clamp-to-edge, alpha := 1.

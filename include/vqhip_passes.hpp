@@ -11,6 +11,9 @@
 // These adaptors give them the IRenderPass shape so a maintainer can register them next to the other 8 passes
 // (Renderer.cpp:577-585) and call RecordCommands() where the D3D12 code recorded command lists. "Recording" here means
 // enqueueing HIP kernels on a stream through the C ABI (include/vqhip.h); nothing else is linked.
+// Passes that are one C call and have no adaptor class here:
+//     ResolveMSAA_DepthPrePass + DownsampleDepth   SceneRendering.cpp:484-499 -> vqhip_msaa_resolve_surfaces(.., hierarchy, flags): resolve + the whole depth chain
+//     DownsampleDepth alone (MSAA off, :491-499)   -> vqhip_depth_hierarchy
 // Header-only, C++17, needs the HIP runtime only for buffer allocation (hipMalloc/hipFree).
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -130,6 +130,19 @@ MSAA_SAMPLE_POSITIONS = ((-2, -6), (6, -2), (-6, 2), (2, 6))   # D3D's standard 
 class GBufferMSAA(C.Structure):   # vqhip_gbuffer_msaa: up to 4 fragment layers + their per-pixel sample masks (vqhip_forward_lighting_msaa)
     _fields_ = [("layer", GBuffer * MSAA_MAX_LAYERS), ("coverage", C.c_void_p * MSAA_MAX_LAYERS), ("layers", C.c_int32), ("coverage_pitch", C.c_int32)]
 
+
+class MSAASurfaces(C.Structure):   # vqhip_msaa_surfaces: the 4-sample depth + per-layer normals / roughness planes of vqhip_msaa_resolve_surfaces
+    _fields_ = [("depth_ms", C.c_void_p), ("coverage", C.c_void_p * MSAA_MAX_LAYERS), ("normals", C.c_void_p * MSAA_MAX_LAYERS),
+                ("roughness", C.c_void_p * MSAA_MAX_LAYERS), ("background", C.c_void_p),
+                ("normals_pitch_px", C.c_int32 * MSAA_MAX_LAYERS), ("roughness_pitch_px", C.c_int32 * MSAA_MAX_LAYERS),
+                ("width", C.c_int32), ("height", C.c_int32), ("layers", C.c_int32), ("coverage_pitch", C.c_int32),
+                ("depth_pitch_px", C.c_int32), ("background_pitch_px", C.c_int32), ("normals_fmt", C.c_int32), ("pad_", C.c_int32)]
+
+
+DEPTH_HIERARCHY_TRUE_TOP = 1     # VQHIP_DEPTH_HIERARCHY_TRUE_TOP
+DEPTH_HIERARCHY_MAX_DIM = 4096   # VQHIP_DEPTH_HIERARCHY_MAX_DIM
+
+
 class CommInfo(C.Structure):    # vqhip_comm_info
     _fields_ = [("world", C.c_int32), ("rank", C.c_int32), ("nranks_seen", C.c_int32), ("rank_seen", C.c_int32),
                 ("rccl_version", C.c_int32), ("reserved", C.c_int32), ("library_path", C.c_char * 232)]
@@ -198,6 +211,8 @@ _chk(Texture2D, 24, width=8, mips=16)
 _chk(MaterialDesc, 256, texDiffuse=80, texLocalAO=224)
 _chk(GBuffer, 48, width=32, row_pitch_px=40)
 _chk(GBufferMSAA, 232, coverage=192, layers=224, coverage_pitch=228)
+_chk(MSAASurfaces, 176, coverage=8, normals=40, roughness=72, background=104, normals_pitch_px=112, roughness_pitch_px=128, width=144, layers=152,
+     depth_pitch_px=160, normals_fmt=168)
 _chk(TonemapperParams, 16)
 _chk(BlurParams, 8)
 _chk(SSSRConstants, 512, bufferDimensions=448, roughnessThreshold=472, envMapSpecularIrradianceCubemapMipLevelCount=504)
@@ -218,6 +233,11 @@ def mip_dim(d0, level):
 
 def mip_chain_px(w0, h0, n_mips):
     return sum(mip_dim(w0, l) * mip_dim(h0, l) for l in range(n_mips))
+
+
+def depth_hierarchy_shapes(w, h):
+    """[(rows, cols)] of every level of the depth hierarchy of a w x h frame (vqhip_depth_hierarchy: floor-halved, clamped to 1)"""
+    return [(mip_dim(h, l), mip_dim(w, l)) for l in range(mip_level_count(w, h))]
 
 
 def specular_mip_count(res0):

@@ -46,6 +46,10 @@ def load_library():
                                              vp, i32, C.POINTER(abi.EnvMap), C.POINTER(abi.ShadowMaps), vp, i32, i32, C.POINTER(abi.PsmainTargets)]),
         "vqhip_forward_lighting_msaa": (i32, [vp, vp, C.POINTER(abi.GBufferMSAA), C.POINTER(abi.PerFrameData), C.POINTER(abi.PerViewLightingData),
                                               vp, i32, C.POINTER(abi.EnvMap), C.POINTER(abi.ShadowMaps), vp, i32, vp, i32, i32]),
+        "vqhip_msaa_resolve_surfaces": (i32, [vp, vp, C.POINTER(abi.MSAASurfaces), vp, i32, vp, i32, i32, vp, i32, i32, vp, C.c_uint]),
+        "vqhip_depth_hierarchy_bytes": (sz, [i32, i32]),
+        "vqhip_depth_hierarchy_level_offset_bytes": (sz, [i32, i32, i32]),
+        "vqhip_depth_hierarchy": (i32, [vp, vp, vp, i32, i32, i32, vp, C.c_uint]),
         "vqhip_gaussian_blur": (i32, [vp, vp, vp, vp, vp, C.POINTER(abi.BlurParams), i32]),
         "vqhip_gaussian_blur_x": (i32, [vp, vp, vp, vp, C.POINTER(abi.BlurParams), i32]),
         "vqhip_gaussian_blur_y": (i32, [vp, vp, vp, vp, vp, vp, i32, C.POINTER(abi.BlurParams), i32]),
@@ -122,6 +126,7 @@ EXPORTED_SYMBOLS = [
     "vqhip_fsr_easu_con", "vqhip_fsr_rcas_con", "vqhip_fsr_easu", "vqhip_fsr_rcas", "vqhip_visualize", "vqhip_apply_reflections", "vqhip_composite_reflections", "vqhip_ssr_environment_fallback",
     "vqhip_rowtile", "vqhip_comm_unique_id", "vqhip_comm_create", "vqhip_comm_adopt", "vqhip_comm_destroy", "vqhip_comm_query", "vqhip_comm_abort", "vqhip_comm_loopback", "vqhip_exchange_blur_halos",
     "vqhip_composite_tiles", "vqhip_forward_lighting_msaa",
+    "vqhip_msaa_resolve_surfaces", "vqhip_depth_hierarchy", "vqhip_depth_hierarchy_bytes", "vqhip_depth_hierarchy_level_offset_bytes",
 ]
 
 
@@ -383,6 +388,93 @@ class Context:
                                                       C.byref(env) if env is not None else None, C.byref(shadow) if shadow is not None else None,
                                                       _ptr(background), w, _ptr(out), w, out_fmt))
         return out
+
+    # ---- 4x MSAA surface resolve + depth hierarchy (ResolveMSAA_DepthPrePass / DownsampleDepth, SceneRendering.cpp:484-499) ------
+    def _hierarchy_views(self, flat, w, h):
+        views, off = [], 0
+        for (rows, cols) in abi.depth_hierarchy_shapes(w, h):
+            views.append(flat[off:off + rows * cols].view(rows, cols))
+            off += rows * cols
+        return views
+
+    def _hierarchy_buffer(self, w, h):
+        if max(w, h) > abi.DEPTH_HIERARCHY_MAX_DIM:
+            raise ValueError(f"depth hierarchy: frames above {abi.DEPTH_HIERARCHY_MAX_DIM} in either dimension are not supported (got {w} x {h})")
+        return torch.empty((sum(r * c for r, c in abi.depth_hierarchy_shapes(w, h)),), dtype=torch.float32, device=self.device)
+
+    def depth_hierarchy(self, depth, flags=0, stream=None):
+        """vqhip_depth_hierarchy: depth float32 cuda [H,W] (rows may be strided: a column slice of a wider plane) -> the levels of the min-depth
+        pyramid, level 0 first, as views of ONE flat tensor (views[0].storage). flags: abi.DEPTH_HIERARCHY_TRUE_TOP."""
+        if not (depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 2 and depth.stride(1) == 1 and depth.stride(0) >= depth.shape[1]):
+            raise ValueError(f"depth: expected cuda float32 [H,W] with unit column stride, got {tuple(depth.shape)} {depth.dtype} strides {depth.stride()}")
+        h, w = depth.shape
+        flat = self._hierarchy_buffer(w, h)
+        self._ck(self.lib.vqhip_depth_hierarchy(self._h, self._stream(stream), _ptr(depth), depth.stride(0), w, h, _ptr(flat), int(flags)))
+        return self._hierarchy_views(flat, w, h)
+
+    def msaa_resolve_surfaces(self, depth_ms, coverage=None, normals=None, normals_fmt=abi.FMT_R10G10B10A2_UNORM, roughness=None, background=None,
+                              out_depth=False, out_normals_fmt=None, scene_color=None, scene_fmt=FMT_RGBA16F, hierarchy=False, flags=0, stream=None):
+        """vqhip_msaa_resolve_surfaces (DepthResolve.hlsl). depth_ms: float32 cuda [H,W,4] (sample s at [..., s]); coverage: one uint8 [H,W] plane per
+        layer; normals: one plane per layer, int32 [H,W] (R10G10B10A2_UNORM words) or float32 [H,W,4]; roughness: one gb1 plane (float32 [H,W,4]) per layer;
+        background: the scene colour's background plane (scene_fmt) or None. Outputs — out_depth: True -> float32 [H,W]; out_normals_fmt: a format -> the
+        resolved normals in it; scene_color: an image of scene_fmt whose alpha is rewritten IN PLACE; hierarchy: True -> the fused depth hierarchy (list of
+        level views, `flags` as depth_hierarchy). Returns a dict with the keys of the outputs asked for."""
+        if not (depth_ms.is_cuda and depth_ms.is_contiguous() and depth_ms.dtype == torch.float32 and depth_ms.dim() == 3 and depth_ms.shape[2] == 4):
+            raise ValueError(f"depth_ms: expected contiguous cuda float32 [H,W,4], got {tuple(depth_ms.shape)} {depth_ms.dtype}")
+        h, w = depth_ms.shape[0], depth_ms.shape[1]
+        want_n, want_r = out_normals_fmt is not None, scene_color is not None
+        if not (out_depth or want_n or want_r or hierarchy):
+            raise ValueError("msaa_resolve_surfaces: at least one output is required")
+        s = abi.MSAASurfaces()
+        s.depth_ms, s.width, s.height, s.depth_pitch_px, s.coverage_pitch, s.normals_fmt = depth_ms.data_ptr(), w, h, w, w, normals_fmt
+        nl = len(coverage) if coverage is not None else 1
+        if not 1 <= nl <= abi.MSAA_MAX_LAYERS:
+            raise ValueError(f"msaa_resolve_surfaces: 1..{abi.MSAA_MAX_LAYERS} layers (got {nl})")
+        s.layers = nl
+        if want_n or want_r:
+            if coverage is None:
+                raise ValueError("msaa_resolve_surfaces: the normals / roughness outputs need the coverage planes")
+            for k, cov in enumerate(coverage):
+                if not (cov.is_cuda and cov.is_contiguous() and cov.dtype == torch.uint8 and tuple(cov.shape) == (h, w)):
+                    raise ValueError(f"coverage {k}: expected contiguous cuda uint8 tensor of shape {(h, w)}, got {tuple(cov.shape)} {cov.dtype} {cov.device}")
+                s.coverage[k] = cov.data_ptr()
+        res = {}
+        if want_n:
+            if normals_fmt not in (abi.FMT_R10G10B10A2_UNORM, FMT_RGBA32F) or out_normals_fmt not in (abi.FMT_R10G10B10A2_UNORM, FMT_RGBA32F):
+                raise ValueError("msaa_resolve_surfaces: normals are R10G10B10A2_UNORM or RGBA32F")
+            if normals is None or len(normals) != nl:
+                raise ValueError("msaa_resolve_surfaces: one normals plane per layer")
+            for k, n in enumerate(normals):
+                if normals_fmt == abi.FMT_R10G10B10A2_UNORM:
+                    if not (n.is_cuda and n.is_contiguous() and n.dtype == torch.int32 and tuple(n.shape) == (h, w)):
+                        raise ValueError(f"normals {k}: expected contiguous cuda int32 [H,W] (R10G10B10A2_UNORM words) of shape {(h, w)}")
+                else:
+                    _check_img(n, FMT_RGBA32F, f"normals {k}", (h, w))
+                s.normals[k], s.normals_pitch_px[k] = n.data_ptr(), w
+            res["normals"] = (torch.empty((h, w), dtype=torch.int32, device=self.device) if out_normals_fmt == abi.FMT_R10G10B10A2_UNORM
+                              else empty_image(h, w, FMT_RGBA32F, self.device))
+        if want_r:
+            _check_img(scene_color, scene_fmt, "scene_color", (h, w))
+            if roughness is None or len(roughness) != nl:
+                raise ValueError("msaa_resolve_surfaces: one roughness (gb1) plane per layer")
+            for k, g in enumerate(roughness):
+                _check_img(g, FMT_RGBA32F, f"roughness {k}", (h, w))
+                s.roughness[k], s.roughness_pitch_px[k] = g.data_ptr(), w
+            if background is not None:
+                _check_img(background, scene_fmt, "background", (h, w))
+                if background.data_ptr() == scene_color.data_ptr():
+                    raise ValueError("msaa_resolve_surfaces: background must not be scene_color")
+                s.background, s.background_pitch_px = background.data_ptr(), w
+            res["scene_color"] = scene_color
+        if out_depth:
+            res["depth"] = torch.empty((h, w), dtype=torch.float32, device=self.device)
+        flat = self._hierarchy_buffer(w, h) if hierarchy else None
+        self._ck(self.lib.vqhip_msaa_resolve_surfaces(self._h, self._stream(stream), C.byref(s), _ptr(res.get("depth")), w,
+                                                      _ptr(res.get("normals")), out_normals_fmt if want_n else 0, w,
+                                                      _ptr(scene_color), scene_fmt, w, _ptr(flat), int(flags)))
+        if hierarchy:
+            res["hierarchy"] = self._hierarchy_views(flat, w, h)
+        return res
 
     # ---- post-process (RenderPostProcess, SceneRendering.cpp:2507) ------------------------------------------
     def gaussian_blur(self, src, fmt, tmp=None, out=None, stream=None):

@@ -36,6 +36,9 @@ struct vqhip_ctx {
     // edge-pixel list of vqhip_forward_lighting_msaa (msaa.hip): a counter + 4 B per pixel. Its own buffer, not `scratch` (the post chain's two-kernel form keeps
     // BlurIntermediate there, possibly on another stream next to shading); `edgeFree` is recorded behind the kernel that reads it, the next call's stream waits for it
     void* edge = nullptr; size_t edgeBytes = 0; hipEvent_t edgeFree = nullptr; bool edgeUsed = false;
+    // per-tile minima of the depth hierarchy's TRUE_TOP form (depth.hip: k_depth_hierarchy writes them, k_depth_tail reduces them): kMaxDepthTiles floats, allocated
+    // on first use; `hierFree` orders calls on different streams, as `edgeFree` does for the edge list
+    void* hier = nullptr; hipEvent_t hierFree = nullptr; bool hierUsed = false;
     int pow5ExpLog = 0;            // vqhip_set_fresnel_pow
     int arithDxc = 0;              // vqhip_set_arithmetic
     vqk::Options opt;              // vqhip_set_option
@@ -283,6 +286,8 @@ void vqhip_destroy(vqhip_ctx* ctx) {
     if (ctx->recFree) (void)hipEventDestroy(ctx->recFree);
     if (ctx->edge) (void)hipFree(ctx->edge);
     if (ctx->edgeFree) (void)hipEventDestroy(ctx->edgeFree);
+    if (ctx->hier) (void)hipFree(ctx->hier);
+    if (ctx->hierFree) (void)hipEventDestroy(ctx->hierFree);
     for (int i = 0; i < vqhip_ctx::kLuts; ++i) {
         if (ctx->lut[i].table) (void)hipFree(ctx->lut[i].table);
         if (ctx->lut[i].built) (void)hipEventDestroy(ctx->lut[i].built);
@@ -734,6 +739,148 @@ int vqhip_mip_chain_min_rgba32f(vqhip_ctx* ctx, void* stream, void* mips, int w0
         float4* dst = (float4*)((char*)mips + vqhip_mip_level_offset_bytes(w0, h0, l));
         hipError_t e = launch_mip_min((hipStream_t)stream, src, dst, mipDim(w0, l - 1), mipDim(h0, l - 1), mipDim(w0, l), mipDim(h0, l));
         if (e != hipSuccess) return failHip(ctx, e, "mip_min launch");
+    }
+    return VQHIP_OK;
+}
+
+// ---- 4x MSAA surface resolve + depth hierarchy (depth.hip; docs/DESIGN_DETAILS.md §7.10) ------------------------------------------------
+static size_t depthLevelOffsetFloats(int w, int h, int level) {
+    size_t off = 0;
+    for (int l = 0; l < level; ++l) off += (size_t)mipDim(w, l) * mipDim(h, l);
+    return off;
+}
+size_t vqhip_depth_hierarchy_level_offset_bytes(int width, int height, int level) {
+    if (width <= 0 || height <= 0 || level < 0) return 0;
+    const int L = vqhip_mip_level_count(width, height);
+    return depthLevelOffsetFloats(width, height, level < L ? level : L) * 4;
+}
+size_t vqhip_depth_hierarchy_bytes(int width, int height) {
+    if (width <= 0 || height <= 0) return 0;
+    return depthLevelOffsetFloats(width, height, vqhip_mip_level_count(width, height)) * 4;
+}
+
+namespace {
+bool rangesOverlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
+// the hierarchy kernels over `src` (a plane, or the four samples per pixel) on `st`; arguments are validated by the callers
+int enqueueDepthHierarchy(vqhip_ctx* ctx, hipStream_t st, const float* src, int srcPitch, int W, int H, float* mips, unsigned flags, bool ms) {
+    HierArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.src = src; a.mips = mips; a.width = W; a.height = H; a.srcPitch = srcPitch; a.flags = (int)flags;
+    a.levels = vqhip_mip_level_count(W, H);
+    for (int l = 0; l < a.levels; ++l) a.off[l] = (uint32_t)depthLevelOffsetFloats(W, H, l);
+    // TRUE_TOP on a frame of more than one 64 x 64 tile: the tiles' minima pass from the first kernel to the second through the context's buffer
+    const bool shared = (flags & VQHIP_DEPTH_HIERARCHY_TRUE_TOP) && ((W + 63) / 64) * ((H + 63) / 64) > 1;
+    if (shared) {
+        if (!ctx->hier) HIP_TRY(ctx, hipMalloc(&ctx->hier, sizeof(float) * kMaxDepthTiles));
+        if (!ctx->hierFree) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->hierFree, hipEventDisableTiming));
+        if (ctx->hierUsed) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->hierFree, 0));
+        a.tileMin = (float*)ctx->hier;
+    }
+    hipError_t e = launch_depth_hierarchy(st, a, ms);
+    if (e != hipSuccess) return failHip(ctx, e, "depth_hierarchy launch");
+    if (shared) { HIP_TRY(ctx, hipEventRecord(ctx->hierFree, st)); ctx->hierUsed = true; }
+    return VQHIP_OK;
+}
+} // namespace
+
+int vqhip_depth_hierarchy(vqhip_ctx* ctx, void* stream, const float* depth, int depth_pitch_px, int width, int height, float* mips, unsigned flags) {
+    vqk::Range range_("DownsampleDepth");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "depth_hierarchy: ctx is NULL");
+    CTX_GUARD(ctx, "depth_hierarchy");
+    if (!depth || !mips) return fail(ctx, VQHIP_ERR_INVALID_ARG, "depth_hierarchy: NULL argument");
+    if (width <= 0 || height <= 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "depth_hierarchy: bad dimensions");
+    if (flags & ~VQHIP_DEPTH_HIERARCHY_TRUE_TOP) return fail(ctx, VQHIP_ERR_INVALID_ARG, "depth_hierarchy: unknown flag");
+    if (width > VQHIP_DEPTH_HIERARCHY_MAX_DIM || height > VQHIP_DEPTH_HIERARCHY_MAX_DIM)
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "depth_hierarchy: frames above 4096 in either dimension are not supported (the reference's SPD instance covers 12 reductions)");
+    const int pitch = depth_pitch_px ? depth_pitch_px : width;
+    if (pitch < width) return fail(ctx, VQHIP_ERR_INVALID_ARG, "depth_hierarchy: pitch below the width");
+    if (rangesOverlap(depth, ((size_t)(height - 1) * pitch + width) * 4, mips, vqhip_depth_hierarchy_bytes(width, height)))
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, "depth_hierarchy: mips overlaps depth");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return enqueueDepthHierarchy(ctx, (hipStream_t)stream, depth, pitch, width, height, mips, flags, false);
+}
+
+int vqhip_msaa_resolve_surfaces(vqhip_ctx* ctx, void* stream, const vqhip_msaa_surfaces* in,
+        float* outDepth, int outDepthPitchPx, void* outNormals, vqhip_format outNormalsFmt, int outNormalsPitchPx,
+        void* sceneColor, vqhip_format sceneFmt, int scenePitchPx, float* hierarchy, unsigned flags) {
+    vqk::Range range_("MSAAResolve");
+    const char* who = "msaa_resolve_surfaces";
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "msaa_resolve_surfaces: ctx is NULL");
+    CTX_GUARD(ctx, "msaa_resolve_surfaces");
+    auto bad = [&](int code, const char* m) { return fail(ctx, code, std::string(who) + ": " + m); };
+    if (!in) return bad(VQHIP_ERR_INVALID_ARG, "NULL argument");
+    if (!outDepth && !outNormals && !sceneColor && !hierarchy) return bad(VQHIP_ERR_INVALID_ARG, "every output is NULL (the reference has no such permutation)");
+    if (in->layers < 1 || in->layers > VQHIP_MSAA_MAX_LAYERS) return bad(VQHIP_ERR_INVALID_ARG, "layers must be 1..4");
+    const int W = in->width, H = in->height;
+    if (W <= 0 || H <= 0) return bad(VQHIP_ERR_INVALID_ARG, "bad dimensions");
+    if (!in->depth_ms) return bad(VQHIP_ERR_INVALID_ARG, "depth_ms is NULL");
+    if ((uintptr_t)in->depth_ms & 15u) return bad(VQHIP_ERR_INVALID_ARG, "depth_ms must be 16-byte aligned");
+    if (flags & ~VQHIP_DEPTH_HIERARCHY_TRUE_TOP) return bad(VQHIP_ERR_INVALID_ARG, "unknown flag");
+    auto pitchOf = [&](int p) { return p ? p : W; };
+    const int depthPitch = pitchOf(in->depth_pitch_px), covPitch = pitchOf(in->coverage_pitch), bgPitch = pitchOf(in->background_pitch_px);
+    const int odPitch = pitchOf(outDepthPitchPx), onPitch = pitchOf(outNormalsPitchPx), scPitch = pitchOf(scenePitchPx);
+    if (depthPitch < W || (outDepth && odPitch < W) || (outNormals && onPitch < W) || (sceneColor && scPitch < W)) return bad(VQHIP_ERR_INVALID_ARG, "pitch below the width");
+    const bool nIn32 = in->normals_fmt == VQHIP_FMT_RGBA32F, nOut32 = outNormalsFmt == VQHIP_FMT_RGBA32F;
+    if (outNormals && ((!nIn32 && in->normals_fmt != VQHIP_FMT_R10G10B10A2_UNORM) || (!nOut32 && outNormalsFmt != VQHIP_FMT_R10G10B10A2_UNORM)))
+        return bad(VQHIP_ERR_UNSUPPORTED, "normals must be R10G10B10A2_UNORM or RGBA32F");
+    if (sceneColor && !isImageFmt(sceneFmt)) return bad(VQHIP_ERR_UNSUPPORTED, "sceneFmt must be RGBA32F or RGBA16F");
+    if (hierarchy && (W > VQHIP_DEPTH_HIERARCHY_MAX_DIM || H > VQHIP_DEPTH_HIERARCHY_MAX_DIM))
+        return bad(VQHIP_ERR_UNSUPPORTED, "hierarchy: frames above 4096 in either dimension are not supported");
+    SurfArgs a;
+    std::memset(&a, 0, sizeof(a));
+    const size_t depthBytes = ((size_t)(H - 1) * depthPitch + W) * 16;
+    const size_t nPx = nIn32 ? 16 : 4, scPx = sceneFmt == VQHIP_FMT_RGBA32F ? 16 : 8;
+    struct Out { const void* p; size_t n; } outs[4] = {
+        { outDepth, ((size_t)(H - 1) * odPitch + W) * 4 }, { outNormals, ((size_t)(H - 1) * onPitch + W) * (nOut32 ? 16 : 4) },
+        { sceneColor, ((size_t)(H - 1) * scPitch + W) * scPx }, { hierarchy, vqhip_depth_hierarchy_bytes(W, H) } };
+    auto aliases = [&](const void* p, size_t n) { for (const Out& o : outs) if (rangesOverlap(p, n, o.p, o.n)) return true; return false; };
+    for (int i = 0; i < 4; ++i) for (int j = i + 1; j < 4; ++j)
+        if (rangesOverlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n)) return bad(VQHIP_ERR_INVALID_ARG, "outputs overlap each other");
+    if (aliases(in->depth_ms, depthBytes)) return bad(VQHIP_ERR_INVALID_ARG, "an output overlaps depth_ms");
+    if (outNormals || sceneColor) {
+        if (covPitch < W) return bad(VQHIP_ERR_INVALID_ARG, "pitch below the width");
+        for (int k = 0; k < in->layers; ++k) {
+            if (!in->coverage[k]) return bad(VQHIP_ERR_INVALID_ARG, "NULL coverage plane");
+            if (aliases(in->coverage[k], (size_t)(H - 1) * covPitch + W)) return bad(VQHIP_ERR_INVALID_ARG, "an output overlaps a coverage plane");
+            a.L[k].cov = in->coverage[k];
+            if (outNormals) {
+                const int p = pitchOf(in->normals_pitch_px[k]);
+                if (!in->normals[k]) return bad(VQHIP_ERR_INVALID_ARG, "NULL normals plane");
+                if (p < W) return bad(VQHIP_ERR_INVALID_ARG, "pitch below the width");
+                if (aliases(in->normals[k], ((size_t)(H - 1) * p + W) * nPx)) return bad(VQHIP_ERR_INVALID_ARG, "an output overlaps a normals plane");
+                a.L[k].normals = in->normals[k]; a.L[k].nPitch = p;
+            }
+            if (sceneColor) {
+                const int p = pitchOf(in->roughness_pitch_px[k]);
+                if (!in->roughness[k]) return bad(VQHIP_ERR_INVALID_ARG, "NULL roughness (gb1) plane");
+                if (p < W) return bad(VQHIP_ERR_INVALID_ARG, "pitch below the width");
+                if (aliases(in->roughness[k], ((size_t)(H - 1) * p + W) * 16)) return bad(VQHIP_ERR_INVALID_ARG, "an output overlaps a roughness plane");
+                a.L[k].gb1 = (const float4*)in->roughness[k]; a.L[k].rPitch = p;
+            }
+        }
+        if (sceneColor && in->background) {
+            if (bgPitch < W) return bad(VQHIP_ERR_INVALID_ARG, "pitch below the width");
+            if (aliases(in->background, ((size_t)(H - 1) * bgPitch + W) * scPx)) return bad(VQHIP_ERR_INVALID_ARG, "an output overlaps the background");
+            a.bg = in->background;
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    a.depthMS = (const float4*)in->depth_ms;
+    a.outDepth = outDepth; a.outNormals = outNormals; a.scene = sceneColor;
+    a.width = W; a.height = H; a.layers = in->layers; a.covPitch = covPitch; a.depthPitch = depthPitch; a.bgPitch = bgPitch;
+    a.outDepthPitch = odPitch; a.outNormalsPitch = onPitch; a.scenePitch = scPitch;
+    a.nInF32 = nIn32; a.nOutF32 = nOut32; a.sceneF32 = sceneFmt == VQHIP_FMT_RGBA32F; a.arithDxc = ctx->arithDxc;
+    if (hierarchy) {
+        int rc = enqueueDepthHierarchy(ctx, st, in->depth_ms, depthPitch, W, H, hierarchy, flags, true);
+        if (rc) return rc;
+    }
+    if (outDepth || outNormals || sceneColor) {
+        hipError_t e = launch_resolve_surfaces(st, a);
+        if (e != hipSuccess) return failHip(ctx, e, "msaa_resolve_surfaces launch");
     }
     return VQHIP_OK;
 }

@@ -157,6 +157,28 @@ struct MsaaArgs {
 };
 hipError_t launch_forward_lighting_msaa(hipStream_t s, const MsaaArgs& a, bool hasEnv, bool hasCasters, int outFmt, int arithDxc, int nCUs);
 
+// 4x MSAA surface resolve + depth hierarchy (vqhip_msaa_resolve_surfaces / vqhip_depth_hierarchy, depth.hip). Output pointers NULL = that output is not live.
+struct SurfLayer { const uint8_t* cov; const void* normals; const float4* gb1; int nPitch, rPitch; };
+struct SurfArgs {
+    SurfLayer L[VQHIP_MSAA_MAX_LAYERS];
+    const float4* depthMS;      // one float4 per pixel: the four samples
+    const void* bg;             // background plane in the scene colour's format, NULL = alpha 0
+    float* outDepth; void* outNormals; void* scene;
+    int width, height, layers, covPitch, depthPitch, bgPitch, outDepthPitch, outNormalsPitch, scenePitch;
+    int nInF32, nOutF32, sceneF32, arithDxc;
+};
+static constexpr int kMaxDepthLevels = 13;        // 4096 x 4096
+static constexpr int kMaxDepthTiles = 64 * 64;    // 64 x 64 tiles of level 0
+struct HierArgs {
+    const float* src;           // R32F plane (srcPitch floats per row) or, for the MSAA form, the four samples per pixel (srcPitch pixels per row)
+    float* mips;
+    float* tileMin;             // context-owned: kMaxDepthTiles per-tile minima (TRUE_TOP on a frame of more than one tile), else unused
+    uint32_t off[kMaxDepthLevels];   // start of level l in floats
+    int width, height, srcPitch, levels, flags;
+};
+hipError_t launch_resolve_surfaces(hipStream_t s, const SurfArgs& a);
+hipError_t launch_depth_hierarchy(hipStream_t s, const HierArgs& a, bool ms);
+
 // launchers (each returns the hipError_t of the launch)
 hipError_t launch_forward_lighting(hipStream_t s, const ShadeArgs& a, bool hasEnv, bool hasCasters, int outFmt, const Options& opt);
 hipError_t launch_blur_x(hipStream_t s, const void* in, void* out, int W, int H, int fmt, const Options& opt);

@@ -513,3 +513,54 @@ def gbuffer_msaa(width, height, layers=2, split_fraction=0.05, seed=0x4A4A, mode
         for k in range(layers):
             cov[k] |= ((ids[..., s] == k).astype(np.uint8) << s)
     return gbs, cov
+
+
+def depth_msaa(width, height, coverage, seed=0xD397, plant=False):
+    """Per-sample NDC depth float32 [H,W,4] consistent with the masks of gbuffer_msaa: every layer is a smooth depth field (a tilted plane with a
+    ripple) evaluated at D3D's 4x sample positions, so samples of one layer differ by the field's slope; nearer layers (lower index) are nearer; a sample
+    no layer owns holds the clear value 1.0. plant=True additionally plants, in seeded pixels, exact ties between samples (pairs, triples, all four equal)
+    and the exact values 0.0 and 1.0 on owned samples."""
+    layers = len(coverage)
+    rng = np.random.default_rng(seed)
+    pos = np.array(abi.MSAA_SAMPLE_POSITIONS, np.float64) / 16.0
+    sx = (np.arange(width) + 0.5)[None, :, None] + pos[None, None, :, 0]
+    sy = (np.arange(height) + 0.5)[:, None, None] + pos[None, None, :, 1]
+    depth = np.ones((height, width, 4), np.float32)
+    taken = np.zeros((height, width, 4), bool)
+    for k in range(layers):
+        gx, gy = rng.uniform(-0.04, 0.04, 2) / max(width, height)
+        ph, fr = rng.uniform(0, 2 * np.pi), rng.uniform(0.02, 0.08)
+        lo = 0.05 + 0.9 * k / layers                                           # layer k lies in [lo, lo + 0.9 / layers): nearer layers nearer
+        f = 0.5 + gx * (sx - width / 2) + gy * (sy - height / 2) + 0.2 * np.sin(fr * sx + ph) * np.cos(fr * sy)
+        d = (lo + (0.9 / layers) * np.clip(0.5 + 0.6 * (f - 0.5), 0.0, 0.999)).astype(np.float32)
+        mine = (((coverage[k][..., None] >> np.arange(4)) & 1) != 0) & ~taken
+        depth[mine] = d[mine]
+        taken |= mine
+    if plant:
+        n = min(max(8, width * height // 16), 20000)
+        ys, xs = rng.integers(0, height, n), rng.integers(0, width, n)
+        kind = rng.integers(0, 6, n)
+        for y, x, c in zip(ys, xs, kind):
+            px = depth[y, x]
+            if c == 0:
+                px[1] = px[0]
+            elif c == 1:
+                px[3] = px[2] = px[1]
+            elif c == 2:
+                px[:] = px[rng.integers(0, 4)]
+            elif c == 3:
+                px[rng.integers(0, 4)] = 0.0
+            elif c == 4:
+                px[rng.integers(0, 4)] = 1.0
+            else:
+                px[[0, 2]] = px[[0, 2]].min()
+    return depth
+
+
+def packed_unit_normals(shape, seed=0x9A11):
+    """Random unit vectors encoded n * 0.5 + 0.5 and packed to R10G10B10A2_UNORM words (alpha 3), uint32 of `shape` — per-layer pre-pass normals"""
+    r = np.random.default_rng(seed)
+    n = r.normal(size=tuple(shape) + (3,))
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    q = np.clip(np.floor((n * 0.5 + 0.5) * 1023.0 + 0.5), 0, 1023).astype(np.uint32)
+    return (q[..., 0] | (q[..., 1] << 10) | (q[..., 2] << 20) | (np.uint32(3) << 30)).astype(np.uint32)
