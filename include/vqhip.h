@@ -342,7 +342,8 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * 2 (round 4): + vqhip_set_arithmetic, vqhip_set_option, vqhip_ssr_environment_fallback, VQHIP_FMT_R10G10B10A2_UNORM; conv order default SEQUENTIAL;
                                * later in round 4, additions only: vqhip_forward_lighting_mrt, vqhip_forward_lighting_from_materials_mrt, vqhip_scene_normals_from_materials,
                                * vqhip_composite_reflections; vqhip_visualize reads R10G10B10A2 / RG16F / RG32F inputs.
-                               * Later additions to 3: vqhip_gbuffer_msaa, vqhip_forward_lighting_msaa; vqhip_msaa_surfaces, vqhip_msaa_resolve_surfaces, vqhip_depth_hierarchy (+ _bytes, _level_offset_bytes) */
+                               * Later additions to 3: vqhip_gbuffer_msaa, vqhip_forward_lighting_msaa; vqhip_msaa_surfaces, vqhip_msaa_resolve_surfaces, vqhip_depth_hierarchy (+ _bytes, _level_offset_bytes);
+                               * vqhip_ssr_classify, vqhip_ssr_intersect */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -736,7 +737,8 @@ VQHIP_API int vqhip_fsr_rcas(vqhip_ctx* ctx, void* stream, const void* in, void*
  * outFmt RGBA8_UNORM | RGBA16F | RGBA32F. */
 /* Replaces ApplyReflectionsPass::RecordCommands (ApplyReflections.cpp:45-80) == ApplyReflections.hlsl:CSMain :30-50 without
  * COMPOSITE_BOUNDING_VOLUMES: sceneColor.rgb += reflectionRadiance.rgb, alpha (roughness) kept; in place on the scene colour.
- * (The producer of the reflection radiance, FidelityFX SSSR + denoiser, is out of scope.) fmt: RGBA16F | RGBA32F for both. */
+ * (The reflection radiance comes from vqhip_ssr_environment_fallback + vqhip_ssr_classify + vqhip_ssr_intersect below; only the FidelityFX reflection DENOISER
+ * is out of scope.) fmt: RGBA16F | RGBA32F for both. */
 VQHIP_API int vqhip_apply_reflections(vqhip_ctx* ctx, void* stream, const void* reflectionRadiance, void* sceneColor,
         int width, int height, vqhip_format fmt);
 /* Replaces VQRenderer::CompositeReflections (SceneRendering.cpp:2362-2403): ApplyReflectionsPass in the permutation its parameters select
@@ -771,7 +773,8 @@ VQHIP_STATIC_ASSERT(offsetof(VQ_SSSRConstants, bufferDimensions) == 448 && offse
  * i.e. surfaces too rough for a traced ray get the environment's prefiltered reflection: view-space reflect of the view ray about the G-buffer normal,
  * g_environment_map.SampleLevel(envMapRotation * R_world, roughness * (mipCount - 1)) — a FRACTIONAL level: trilinear between cube mips, seamless
  * (csrc/vq_sampling.h:sample_cube_lod_rgba16f) — times EnvironmentBRDF(NdotV, roughness, metallic 1, ...) from the LUT (BRDF.hlsl:196-207).
- * The ray classification / ray list / denoiser tile list of the same dispatch (wave intrinsics, atomics) and the traced rays are FidelityFX SSSR: out of scope.
+ * The ray classification / ray list / denoiser tile list of the same dispatch is vqhip_ssr_classify, the traced rays are vqhip_ssr_intersect (below); what stays out
+ * of scope is the reflection denoiser (Reproject / Prefilter / ResolveTemporal, PrepareBlueNoiseTexture and its Sobol tables).
  *   sceneColorRoughness : g_roughness   == the scene colour whose alpha is the roughness (ForwardLighting.hlsl:380), RGBA16F | RGBA32F
  *   depth               : g_depth_buffer == mip 0 of the depth hierarchy, R32F, NDC z (far plane 1)
  *   normals             : g_normal      == Tex_SceneNormals, R10G10B10A2_UNORM (one uint32 per pixel, r in bits 0-9) | RGBA32F holding the same [0,1] values
@@ -787,6 +790,53 @@ VQHIP_API int vqhip_ssr_environment_fallback(vqhip_ctx* ctx, void* stream,
         const void* normals, vqhip_format normalFmt, int normalPitchPx,
         int width, int height, const VQ_SSSRConstants* cb, const vqhip_envmap* env,
         void* outRadiance, vqhip_format outFmt, int outPitchPx, uint8_t* outExtractedRoughness);
+
+/* The ray list of the same dispatch: ClassifyReflectionTiles.hlsl:ClassifyTiles :96-145,157-161 without the fallback radiance (that stays
+ * vqhip_ssr_environment_fallback). Per pixel, as written: needs_ray = on screen && depth < 1 && roughness < roughnessThreshold; needs_denoiser = needs_ray &&
+ * !(roughness < 0.04); IsBaseRay for samplesPerQuad 1 / 2 / other (:65-74) deactivates glossy rays, never mirror rays; with temporalVarianceGuidedTracingEnabled a
+ * deactivated pixel whose variance history exceeds varianceThreshold traces again; the three copy flags are read from the quad neighbours (lanes l^1, l^2, l^3 under
+ * FFX_DNSR_Reflections_RemapLane8x8). The reference appends with atomics, so any permutation is a valid reference result; this library's ORDER is part of its contract
+ * (docs/DESIGN_DETAILS.md §7.11): 8 x 8 tiles row-major, inside a tile lanes 0..63 of RemapLane8x8, rays compacted in that order, the tile list in tile order —
+ * built as count -> scan -> scatter (three launches; no workgroup waits for another). The frame is cb->bufferDimensions (each <= 4096, else VQHIP_ERR_UNSUPPORTED).
+ *   sceneColorRoughness : as vqhip_ssr_environment_fallback reads it (alpha = roughness), RGBA16F | RGBA32F
+ *   depth               : level 0 of the depth hierarchy (vqhip_depth_hierarchy), R32F
+ *   varianceHistory     : g_variance_history, an R16F plane (one half per pixel), or NULL = every pixel reads 0
+ *   cb                  : host pointer; bufferDimensions, roughnessThreshold, varianceThreshold, samplesPerQuad, temporalVarianceGuidedTracingEnabled are read
+ *   rayList             : uint32[width * height], PackRayCoords (Common.hlsl:62-71): x bits 0-14, y 15-28, copy horizontal 29, vertical 30, diagonal 31
+ *   counters            : uint32[2] = { ray count, denoiser tile count }
+ *   denoiserTileList    : NULL, or uint32[ceil(w/8) * ceil(h/8)]: (y << 16) | x of the first pixel of each tile in which some lane is glossy && depth < 1 — as written
+ *                         (:126) that test is not masked by the screen test, and lanes beyond the frame load 0: the partial tiles of the right / bottom edge are listed
+ * All outputs are device memory, written on `stream`; pitches in pixels (0 = width). */
+VQHIP_API int vqhip_ssr_classify(vqhip_ctx* ctx, void* stream,
+        const void* sceneColorRoughness, vqhip_format sceneFmt, int scenePitchPx,
+        const float* depth, int depthPitchPx,
+        const void* varianceHistory, int variancePitchPx,
+        const VQ_SSSRConstants* cb,
+        uint32_t* rayList, uint32_t* counters, uint32_t* denoiserTileList);
+
+/* Replaces the "FFX SSSR Intersection" dispatch == Intersect.hlsl:CSMain :145-216 + AMDFidelityFX/SSSR/ffx_sssr.h for every entry of the ray list: the GGX-VNDF
+ * reflection direction from the blue-noise sample, the hierarchical march through the min-depth pyramid, FFX_SSSR_ValidateHit, and
+ *     radiance.rgb = lerp(SampleEnvironmentMap(level 0), g_lit_scene at the hit, confidence),   radiance.a = world_ray_length
+ * written IN PLACE into the buffer vqhip_ssr_environment_fallback filled, at the ray's pixel and at its up to three copy targets (coords ^ 1). The ray count is read on
+ * the device (no host synchronisation). The float32 contract — expression order, load / convert rules, and the wave term: WaveActiveCountBits(true) <=
+ * minTraversalOccupancy is evaluated over the rays [64g, 64g + 64) of the list still in the loop, one wave per 64 consecutive rays — is docs/DESIGN_DETAILS.md §7.11.
+ *   rayList, counters   : as vqhip_ssr_classify wrote them (counters[0] rays; clamped to width * height)
+ *   litScene            : g_lit_scene, RGBA16F | RGBA32F; must not overlap `radiance`
+ *   hierarchy           : the buffer of vqhip_depth_hierarchy for the same frame size, whatever flags it was built with
+ *   normals             : g_normal, R10G10B10A2_UNORM | RGBA32F
+ *   extractedRoughness  : g_roughness == outExtractedRoughness of vqhip_ssr_environment_fallback, R8_UNORM, row pitch = width; decoded c / 255 correctly rounded
+ *   blueNoise           : g_blue_noise_texture, 128 x 128 R8G8_UNORM (two bytes per texel, row pitch 128 texels), provided by the caller
+ *   cb                  : host pointer; maxTraversalIntersections > 256 or mostDetailedMip > 5: VQHIP_ERR_UNSUPPORTED
+ *   env                 : specular_cube / spec_res0 / spec_mips and brdf_lut / lut_size are read (device pointers)
+ * The frame is cb->bufferDimensions (each <= 4096). Pitches in pixels (0 = width). PARITY UNPINNED like §7.9 / §7.10 (docs/WARP_CALIBRATION.md §6). */
+VQHIP_API int vqhip_ssr_intersect(vqhip_ctx* ctx, void* stream,
+        const uint32_t* rayList, const uint32_t* counters,
+        const void* litScene, vqhip_format litFmt, int litPitchPx,
+        const float* hierarchy,
+        const void* normals, vqhip_format normalFmt, int normalPitchPx,
+        const uint8_t* extractedRoughness, const uint8_t* blueNoise,
+        const VQ_SSSRConstants* cb, const vqhip_envmap* env,
+        void* radiance, vqhip_format radianceFmt, int radiancePitchPx);
 
 typedef struct VQ_VizParams { int32_t iDrawMode; int32_t iUnpackNormals; float fInputStrength; } VQ_VizParams;
 VQHIP_API int vqhip_visualize(vqhip_ctx* ctx, void* stream, const void* in, void* out, int width, int height,

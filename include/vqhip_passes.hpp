@@ -323,7 +323,7 @@ private:
 // SampleEnvironmentMap (ClassifyReflectionTiles.hlsl:78-94,146-153). FResourceParameters / FDrawParameters keep the fields of
 // ScreenSpaceReflections.h:33-75 this part reads (textures as device pointers, SRVs as the vqhip_envmap). Owns TexRadiance
 // (RGBA16F, :129) and TexExtractedRoughness (R8_UNORM, :135); the radiance is what vqhip_apply_reflections adds to the scene colour
-// when no ray was traced (the traced rays, the denoiser: FidelityFX SSSR, out of scope).
+// when no ray was traced; HipSSRIntersectPass below traces the rays into the same TexRadiance (the reflection denoiser: out of scope).
 // ---------------------------------------------------------------------------------------------------------------
 class HipSSREnvironmentFallbackPass : public RenderPassBase {
 public:
@@ -357,6 +357,57 @@ public:
     void* GetExtractedRoughness() const { return mExtractedRoughness; }  // R8_UNORM
 private:
     void* mRadiance = nullptr; void* mExtractedRoughness = nullptr;
+    unsigned mWidth = 0, mHeight = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// SSR rays == the ray list of the "FFX DNSR ClassifyTiles" dispatch + the "FFX SSSR Intersection" dispatch of
+// ScreenSpaceReflectionsPass::RecordCommands (ScreenSpaceReflections.cpp:262-320): vqhip_ssr_classify + vqhip_ssr_intersect. Owns TexRayList,
+// TexRayCounter and TexDenoiserTileList (ScreenSpaceReflections.cpp:118-127, as plain device buffers); traces IN PLACE into the TexRadiance that
+// HipSSREnvironmentFallbackPass owns and has filled on the same stream. Without a denoiser behind it, run it with ffxCBuffer.samplesPerQuad = 4: every
+// glossy pixel then traces its own ray and the radiance is directly what vqhip_composite_reflections consumes.
+// ---------------------------------------------------------------------------------------------------------------
+class HipSSRIntersectPass : public RenderPassBase {
+public:
+    struct FResourceParameters : public IRenderPassResourceCollection {};
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        VQ_SSSRConstants ffxCBuffer = {};                        // the same block HipSSREnvironmentFallbackPass gets
+        const void* TexSceneColorRoughness = nullptr;            // g_roughness (classify) and g_lit_scene (intersect): the RGBA16F scene colour, alpha = roughness
+        const float* TexDepthHierarchy = nullptr;                // ALL levels of Tex_DownsampledSceneDepth: the buffer of vqhip_depth_hierarchy / vqhip_msaa_resolve_surfaces
+        const void* TexNormals = nullptr;                        // Tex_SceneNormals, R10G10B10A2_UNORM
+        const void* TexVarianceHistory = nullptr;                // R16F, or nullptr (reads 0)
+        const uint8_t* TexExtractedRoughness = nullptr;          // HipSSREnvironmentFallbackPass::GetExtractedRoughness()
+        const uint8_t* TexBlueNoise = nullptr;                   // 128 x 128 R8G8_UNORM (the engine's PrepareBlueNoiseTexture output)
+        void* TexRadiance = nullptr;                             // HipSSREnvironmentFallbackPass::GetRadiance(), RGBA16F
+        const vqhip_envmap* SRVEnvironmentSpecularIrradianceCubemap_BRDFIntegrationLUT = nullptr;
+    };
+    explicit HipSSRIntersectPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    ~HipSSRIntersectPass() override { OnDestroyWindowSizeDependentResources(); }
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { OnDestroyWindowSizeDependentResources(); }
+    void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override {
+        OnDestroyWindowSizeDependentResources();
+        mWidth = Width; mHeight = Height;
+        mRayList = Alloc((size_t)Width * Height * 4); mRayCounter = Alloc(2 * 4);
+        mDenoiserTileList = Alloc((size_t)((Width + 7) / 8) * ((Height + 7) / 8) * 4);
+    }
+    void OnDestroyWindowSizeDependentResources() override { Free(mRayList); Free(mRayCounter); Free(mDenoiserTileList); mWidth = mHeight = 0; }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p || !mRayList || p->ffxCBuffer.bufferDimensions[0] != mWidth || p->ffxCBuffer.bufferDimensions[1] != mHeight) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        mStatus = vqhip_ssr_classify(mCtx, p->Stream, p->TexSceneColorRoughness, VQHIP_FMT_RGBA16F, 0, p->TexDepthHierarchy, 0, p->TexVarianceHistory, 0,
+                                     &p->ffxCBuffer, (uint32_t*)mRayList, (uint32_t*)mRayCounter, (uint32_t*)mDenoiserTileList);
+        if (mStatus != VQHIP_OK) return;
+        mStatus = vqhip_ssr_intersect(mCtx, p->Stream, (const uint32_t*)mRayList, (const uint32_t*)mRayCounter, p->TexSceneColorRoughness, VQHIP_FMT_RGBA16F, 0,
+                                      p->TexDepthHierarchy, p->TexNormals, VQHIP_FMT_R10G10B10A2_UNORM, 0, p->TexExtractedRoughness, p->TexBlueNoise, &p->ffxCBuffer,
+                                      p->SRVEnvironmentSpecularIrradianceCubemap_BRDFIntegrationLUT, p->TexRadiance, VQHIP_FMT_RGBA16F, 0);
+    }
+    const uint32_t* GetRayList() const { return (const uint32_t*)mRayList; }                  // PackRayCoords words, device
+    const uint32_t* GetRayCounter() const { return (const uint32_t*)mRayCounter; }            // { rays, denoiser tiles }, device
+    const uint32_t* GetDenoiserTileList() const { return (const uint32_t*)mDenoiserTileList; }
+private:
+    void* mRayList = nullptr; void* mRayCounter = nullptr; void* mDenoiserTileList = nullptr;
     unsigned mWidth = 0, mHeight = 0;
 };
 

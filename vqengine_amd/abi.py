@@ -246,3 +246,25 @@ def specular_mip_count(res0):
 
 def cube_px(res0, n_mips):
     return sum(6 * (res0 >> m) ** 2 for m in range(n_mips))
+
+
+# ---- vqhip_ssr_classify / vqhip_ssr_intersect (docs/DESIGN_DETAILS.md §7.11) ------------------------------------------------------------------
+SSR_MAX_TRAVERSAL_INTERSECTIONS = 256   # above: VQHIP_ERR_UNSUPPORTED (the engine's slider range)
+SSR_MAX_MOST_DETAILED_MIP = 5           # above: VQHIP_ERR_UNSUPPORTED
+SSR_BLUE_NOISE_SIZE = 128               # g_blue_noise_texture: 128 x 128 R8G8_UNORM
+
+
+def ssr_remap_lane8x8(lane):
+    """FFX_DNSR_Reflections_RemapLane8x8: lane 0..63 of an 8 x 8 tile -> (x, y) inside the tile; four neighbouring lanes form a 2 x 2 quad"""
+    return (lane & 1) | ((lane >> 2) & 6), ((lane >> 1) & 3) | ((lane >> 3) & 4)
+
+
+def pack_ray_coords(x, y, copy_horizontal=False, copy_vertical=False, copy_diagonal=False):
+    """PackRayCoords (Common.hlsl:62-71): x in bits 0-14, y in 15-28, the copy flags in 29 / 30 / 31"""
+    return (int(bool(copy_diagonal)) << 31) | (int(bool(copy_vertical)) << 30) | (int(bool(copy_horizontal)) << 29) | ((int(y) & 0x3FFF) << 15) | (int(x) & 0x7FFF)
+
+
+def unpack_ray_coords(packed):
+    """UnpackRayCoords (Common.hlsl:73-79): (x, y, copy_horizontal, copy_vertical, copy_diagonal)"""
+    packed = int(packed)
+    return packed & 0x7FFF, (packed >> 15) & 0x3FFF, bool((packed >> 29) & 1), bool((packed >> 30) & 1), bool((packed >> 31) & 1)

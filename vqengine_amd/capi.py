@@ -96,6 +96,9 @@ def load_library():
         "vqhip_composite_reflections": (i32, [vp, vp, vp, vp, vp, i32, i32, i32]),
         "vqhip_ssr_environment_fallback": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, C.POINTER(abi.SSSRConstants), C.POINTER(abi.EnvMap),
                                                  vp, i32, i32, vp]),
+        "vqhip_ssr_classify": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, i32, C.POINTER(abi.SSSRConstants), vp, vp, vp]),
+        "vqhip_ssr_intersect": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, C.POINTER(abi.SSSRConstants), C.POINTER(abi.EnvMap),
+                                      vp, i32, i32]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -127,6 +130,7 @@ EXPORTED_SYMBOLS = [
     "vqhip_rowtile", "vqhip_comm_unique_id", "vqhip_comm_create", "vqhip_comm_adopt", "vqhip_comm_destroy", "vqhip_comm_query", "vqhip_comm_abort", "vqhip_comm_loopback", "vqhip_exchange_blur_halos",
     "vqhip_composite_tiles", "vqhip_forward_lighting_msaa",
     "vqhip_msaa_resolve_surfaces", "vqhip_depth_hierarchy", "vqhip_depth_hierarchy_bytes", "vqhip_depth_hierarchy_level_offset_bytes",
+    "vqhip_ssr_classify", "vqhip_ssr_intersect",
 ]
 
 
@@ -707,6 +711,58 @@ class Context:
         self._ck(self.lib.vqhip_ssr_environment_fallback(self._h, self._stream(stream), _ptr(scene_color), scene_fmt, 0, _ptr(depth), 0, _ptr(normals), normal_fmt, 0,
                                                          w, h, C.byref(cb), C.byref(env), _ptr(out), out_fmt, 0, _ptr(rough) if rough is not None else None))
         return (out, rough) if extract_roughness else out
+
+    def ssr_classify(self, scene_color, scene_fmt, depth, cb, variance=None, tile_list=True, stream=None):
+        """vqhip_ssr_classify: the ray list of ClassifyReflectionTiles.hlsl in this library's order (8 x 8 tiles row-major, lanes of RemapLane8x8 inside a tile).
+        scene_color: [H,W,4] image whose alpha is the roughness; depth: float32 cuda [H,W], level 0 of the depth hierarchy (rows may be strided); variance: None or
+        float16 cuda [H,W] (g_variance_history); cb: abi.SSSRConstants with bufferDimensions == (W, H). Returns (ray_list int32 [H*W] — PackRayCoords words, only
+        the first counters[0] are written —, counters int32 [2] = (rays, denoiser tiles), tile_list int32 [tiles] | None); nothing is read back to the host."""
+        _check_img(scene_color, scene_fmt, "scene_color")
+        h, w = scene_color.shape[0], scene_color.shape[1]
+        if (cb.bufferDimensions[0], cb.bufferDimensions[1]) != (w, h):
+            raise ValueError(f"ssr_classify: cb.bufferDimensions {cb.bufferDimensions[0]} x {cb.bufferDimensions[1]} is not the frame {w} x {h}")
+        if not (depth.is_cuda and depth.dtype == torch.float32 and tuple(depth.shape) == (h, w) and depth.stride(1) == 1 and depth.stride(0) >= w):
+            raise ValueError(f"depth: expected cuda float32 {(h, w)} with unit column stride, got {tuple(depth.shape)} {depth.dtype} strides {depth.stride()}")
+        if variance is not None and not (variance.is_cuda and variance.is_contiguous() and variance.dtype == torch.float16 and tuple(variance.shape) == (h, w)):
+            raise ValueError(f"variance: expected contiguous cuda float16 {(h, w)}, got {tuple(variance.shape)} {variance.dtype}")
+        rays = torch.empty((h * w,), dtype=torch.int32, device=self.device)
+        counters = torch.empty((2,), dtype=torch.int32, device=self.device)
+        tiles = torch.empty((((w + 7) // 8) * ((h + 7) // 8),), dtype=torch.int32, device=self.device) if tile_list else None
+        self._ck(self.lib.vqhip_ssr_classify(self._h, self._stream(stream), _ptr(scene_color), scene_fmt, 0, _ptr(depth), depth.stride(0), _ptr(variance), 0,
+                                             C.byref(cb), _ptr(rays), _ptr(counters), _ptr(tiles)))
+        return rays, counters, tiles
+
+    def ssr_intersect(self, ray_list, counters, lit_scene, lit_fmt, hierarchy, normals, normal_fmt, roughness8, blue_noise, cb, env, radiance, radiance_fmt, stream=None):
+        """vqhip_ssr_intersect: Intersect.hlsl for every entry of the ray list, IN PLACE on `radiance` (the image ssr_environment_fallback filled; returned).
+        ray_list / counters: as ssr_classify returned them; hierarchy: the level views of depth_hierarchy (or their flat tensor); normals: int32 [H,W]
+        (R10G10B10A2_UNORM) or float32 [H,W,4]; roughness8: uint8 [H,W], the extracted roughness; blue_noise: uint8 [128,128,2]."""
+        _check_img(lit_scene, lit_fmt, "lit_scene")
+        h, w = lit_scene.shape[0], lit_scene.shape[1]
+        if (cb.bufferDimensions[0], cb.bufferDimensions[1]) != (w, h):
+            raise ValueError(f"ssr_intersect: cb.bufferDimensions {cb.bufferDimensions[0]} x {cb.bufferDimensions[1]} is not the frame {w} x {h}")
+        _check_img(radiance, radiance_fmt, "radiance", (h, w))
+        flat = hierarchy[0] if isinstance(hierarchy, (list, tuple)) else hierarchy
+        n_floats = sum(r * c for r, c in abi.depth_hierarchy_shapes(w, h))
+        if not (flat.is_cuda and flat.dtype == torch.float32 and flat.untyped_storage().nbytes() - flat.storage_offset() * 4 >= n_floats * 4):
+            raise ValueError("hierarchy: expected the cuda float32 buffer of depth_hierarchy for this frame size")
+        if normal_fmt == abi.FMT_R10G10B10A2_UNORM:
+            if not (normals.is_cuda and normals.dtype == torch.int32 and tuple(normals.shape) == (h, w) and normals.is_contiguous()):
+                raise ValueError(f"normals: expected contiguous cuda int32 {(h, w)} (R10G10B10A2_UNORM words)")
+        else:
+            _check_img(normals, normal_fmt, "normals", (h, w))
+        if not (roughness8.is_cuda and roughness8.dtype == torch.uint8 and tuple(roughness8.shape) == (h, w) and roughness8.is_contiguous()):
+            raise ValueError(f"roughness8: expected contiguous cuda uint8 {(h, w)}")
+        n = abi.SSR_BLUE_NOISE_SIZE
+        if not (blue_noise.is_cuda and blue_noise.dtype == torch.uint8 and tuple(blue_noise.shape) == (n, n, 2) and blue_noise.is_contiguous()):
+            raise ValueError(f"blue_noise: expected contiguous cuda uint8 {(n, n, 2)}")
+        if not (ray_list.is_cuda and ray_list.dtype == torch.int32 and ray_list.numel() >= h * w and ray_list.is_contiguous()):
+            raise ValueError(f"ray_list: expected contiguous cuda int32 [{h * w}]")
+        if not (counters.is_cuda and counters.dtype == torch.int32 and counters.numel() >= 2 and counters.is_contiguous()):
+            raise ValueError("counters: expected contiguous cuda int32 [2]")
+        self._ck(self.lib.vqhip_ssr_intersect(self._h, self._stream(stream), _ptr(ray_list), _ptr(counters), _ptr(lit_scene), lit_fmt, 0, _ptr(flat),
+                                              _ptr(normals), normal_fmt, 0, _ptr(roughness8), _ptr(blue_noise), C.byref(cb), C.byref(env),
+                                              _ptr(radiance), radiance_fmt, 0))
+        return radiance
 
     def visualize(self, src, in_fmt, params, out_fmt=None, out=None, stream=None):
         """Visualization.hlsl:CSMain (debug draw modes). params: abi.VizParams. src in the format of the target the mode shows: a colour image, the int32 [H,W]

@@ -39,6 +39,9 @@ struct vqhip_ctx {
     // per-tile minima of the depth hierarchy's TRUE_TOP form (depth.hip: k_depth_hierarchy writes them, k_depth_tail reduces them): kMaxDepthTiles floats, allocated
     // on first use; `hierFree` orders calls on different streams, as `edgeFree` does for the edge list
     void* hier = nullptr; hipEvent_t hierFree = nullptr; bool hierUsed = false;
+    // per-tile ray counts and tile flags of vqhip_ssr_classify (ssr_trace.hip: count -> scan -> scatter): 2 x kMaxSsrTiles dwords, allocated on first use;
+    // `ssrFree` orders calls on different streams, as `hierFree` does
+    void* ssrTiles = nullptr; hipEvent_t ssrFree = nullptr; bool ssrUsed = false;
     int pow5ExpLog = 0;            // vqhip_set_fresnel_pow
     int arithDxc = 0;              // vqhip_set_arithmetic
     vqk::Options opt;              // vqhip_set_option
@@ -288,6 +291,8 @@ void vqhip_destroy(vqhip_ctx* ctx) {
     if (ctx->edgeFree) (void)hipEventDestroy(ctx->edgeFree);
     if (ctx->hier) (void)hipFree(ctx->hier);
     if (ctx->hierFree) (void)hipEventDestroy(ctx->hierFree);
+    if (ctx->ssrTiles) (void)hipFree(ctx->ssrTiles);
+    if (ctx->ssrFree) (void)hipEventDestroy(ctx->ssrFree);
     for (int i = 0; i < vqhip_ctx::kLuts; ++i) {
         if (ctx->lut[i].table) (void)hipFree(ctx->lut[i].table);
         if (ctx->lut[i].built) (void)hipEventDestroy(ctx->lut[i].built);
@@ -1268,6 +1273,84 @@ int vqhip_ssr_environment_fallback(vqhip_ctx* ctx, void* stream, const void* sce
     a.pow5ExpLog = ctx->pow5ExpLog; a.arithDxc = ctx->arithDxc; a.env = *env;
     hipError_t e = launch_ssr_env_fallback((hipStream_t)stream, a, sceneFmt, normalFmt, outFmt);
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "ssr_environment_fallback launch");
+}
+
+// ---- SSR ray list + hierarchical march (ssr_trace.hip; docs/DESIGN_DETAILS.md §7.11) ------------------------------------------------------
+int vqhip_ssr_classify(vqhip_ctx* ctx, void* stream, const void* sceneColorRoughness, vqhip_format sceneFmt, int scenePitchPx,
+                       const float* depth, int depthPitchPx, const void* varianceHistory, int variancePitchPx, const VQ_SSSRConstants* cb,
+                       uint32_t* rayList, uint32_t* counters, uint32_t* denoiserTileList) {
+    vqk::Range range_("FFX DNSR ClassifyTiles");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "ssr_classify: ctx is NULL");
+    CTX_GUARD(ctx, "ssr_classify");
+    if (!sceneColorRoughness || !depth || !cb || !rayList || !counters) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_classify: NULL argument");
+    const uint32_t W = cb->bufferDimensions[0], H = cb->bufferDimensions[1];
+    if (W == 0 || H == 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_classify: bad bufferDimensions");
+    if (W > VQHIP_DEPTH_HIERARCHY_MAX_DIM || H > VQHIP_DEPTH_HIERARCHY_MAX_DIM)
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_classify: frames above 4096 in either dimension are not supported (the range of the depth hierarchy)");
+    if (!isImageFmt(sceneFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_classify: the scene colour must be RGBA32F or RGBA16F");
+    auto pitch = [&](int p) { return p ? p : (int)W; };
+    if (pitch(scenePitchPx) < (int)W || pitch(depthPitchPx) < (int)W || pitch(variancePitchPx) < (int)W) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_classify: pitch < width");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (!ctx->ssrTiles) HIP_TRY(ctx, hipMalloc(&ctx->ssrTiles, sizeof(uint32_t) * 2 * kMaxSsrTiles));
+    if (!ctx->ssrFree) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ssrFree, hipEventDisableTiming));
+    if (ctx->ssrUsed) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ssrFree, 0));
+    SsrClassifyArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.scene = sceneColorRoughness; a.depth = depth; a.variance = varianceHistory;
+    a.rayList = rayList; a.counters = counters; a.tileList = denoiserTileList;
+    a.tileRays = (uint32_t*)ctx->ssrTiles; a.tileFlag = a.tileRays + kMaxSsrTiles;
+    a.width = (int)W; a.height = (int)H; a.scenePitch = pitch(scenePitchPx); a.depthPitch = pitch(depthPitchPx); a.variancePitch = pitch(variancePitchPx);
+    a.sceneF32 = sceneFmt == VQHIP_FMT_RGBA32F;
+    a.tilesX = ((int)W + 7) / 8; a.tilesY = ((int)H + 7) / 8;
+    a.roughnessThreshold = cb->roughnessThreshold; a.varianceThreshold = cb->varianceThreshold;
+    a.samplesPerQuad = cb->samplesPerQuad; a.varianceGuided = cb->temporalVarianceGuidedTracingEnabled;
+    hipError_t e = launch_ssr_classify(st, a);
+    if (e != hipSuccess) return failHip(ctx, e, "ssr_classify launch");
+    HIP_TRY(ctx, hipEventRecord(ctx->ssrFree, st));
+    ctx->ssrUsed = true;
+    return VQHIP_OK;
+}
+
+int vqhip_ssr_intersect(vqhip_ctx* ctx, void* stream, const uint32_t* rayList, const uint32_t* counters,
+                        const void* litScene, vqhip_format litFmt, int litPitchPx, const float* hierarchy,
+                        const void* normals, vqhip_format normalFmt, int normalPitchPx,
+                        const uint8_t* extractedRoughness, const uint8_t* blueNoise,
+                        const VQ_SSSRConstants* cb, const vqhip_envmap* env,
+                        void* radiance, vqhip_format radianceFmt, int radiancePitchPx) {
+    vqk::Range range_("FFX SSSR Intersection");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "ssr_intersect: ctx is NULL");
+    CTX_GUARD(ctx, "ssr_intersect");
+    if (!rayList || !counters || !litScene || !hierarchy || !normals || !extractedRoughness || !blueNoise || !cb || !env || !radiance)
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: NULL argument");
+    const uint32_t W = cb->bufferDimensions[0], H = cb->bufferDimensions[1];
+    if (W == 0 || H == 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: bad bufferDimensions");
+    if (W > VQHIP_DEPTH_HIERARCHY_MAX_DIM || H > VQHIP_DEPTH_HIERARCHY_MAX_DIM)
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_intersect: frames above 4096 in either dimension are not supported (the range of the depth hierarchy)");
+    if (!isImageFmt(litFmt) || !isImageFmt(radianceFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_intersect: lit scene and radiance must be RGBA32F or RGBA16F");
+    if (normalFmt != VQHIP_FMT_R10G10B10A2_UNORM && normalFmt != VQHIP_FMT_RGBA32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_intersect: normals must be R10G10B10A2_UNORM or RGBA32F");
+    if (cb->maxTraversalIntersections > 256) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_intersect: maxTraversalIntersections above 256 (the engine's slider range) is not supported");
+    if (cb->mostDetailedMip > 5) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_intersect: mostDetailedMip above 5 is not supported");
+    if (!env->specular_cube || !env->brdf_lut || env->spec_res0 <= 0 || env->spec_mips <= 0 || env->lut_size <= 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: env needs the specular cube and the BRDF LUT");
+    auto pitch = [&](int p) { return p ? p : (int)W; };
+    if (pitch(litPitchPx) < (int)W || pitch(normalPitchPx) < (int)W || pitch(radiancePitchPx) < (int)W) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: pitch < width");
+    if (rangesOverlap(litScene, ((size_t)(H - 1) * pitch(litPitchPx) + W) * (litFmt == VQHIP_FMT_RGBA32F ? 16 : 8),
+                      radiance, ((size_t)(H - 1) * pitch(radiancePitchPx) + W) * (radianceFmt == VQHIP_FMT_RGBA32F ? 16 : 8)))
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: radiance overlaps the lit scene");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    SsrTraceArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.rayList = rayList; a.counters = counters; a.lit = litScene; a.mips = hierarchy; a.normals = normals; a.roughness = extractedRoughness; a.noise = blueNoise; a.out = radiance;
+    a.width = (int)W; a.height = (int)H; a.litPitch = pitch(litPitchPx); a.normalPitch = pitch(normalPitchPx); a.outPitch = pitch(radiancePitchPx);
+    a.litF32 = litFmt == VQHIP_FMT_RGBA32F; a.normF32 = normalFmt == VQHIP_FMT_RGBA32F; a.outF32 = radianceFmt == VQHIP_FMT_RGBA32F;
+    a.levels = vqhip_mip_level_count((int)W, (int)H);
+    a.invViewProj = cb->invViewProjection; a.proj = cb->projection; a.invProj = cb->invProjection; a.view = cb->view; a.invView = cb->invView;
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) a.rot[i][j] = cb->envMapRotation.m[i][j];
+    a.invDimX = cb->inverseBufferDimensions[0]; a.invDimY = cb->inverseBufferDimensions[1]; a.thickness = cb->depthBufferThickness;
+    a.maxIter = cb->maxTraversalIntersections; a.minOcc = cb->minTraversalOccupancy; a.mostDetailedMip = cb->mostDetailedMip;
+    a.pow5ExpLog = ctx->pow5ExpLog; a.arithDxc = ctx->arithDxc; a.env = *env;
+    hipError_t e = launch_ssr_intersect((hipStream_t)stream, a, ctx->nCUs);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "ssr_intersect launch");
 }
 
 int vqhip_specular_mip_count(int spec_res0) { return vqhip_mip_level_count(spec_res0, spec_res0) - 1; }

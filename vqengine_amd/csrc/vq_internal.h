@@ -144,6 +144,30 @@ struct SsrArgs {
 };
 hipError_t launch_ssr_env_fallback(hipStream_t s, const SsrArgs& a, int sceneFmt, int normalFmt, int outFmt);
 
+// SSR ray list + hierarchical march (vqhip_ssr_classify / vqhip_ssr_intersect, ssr_trace.hip; docs/DESIGN_DETAILS.md §7.11)
+static constexpr int kMaxSsrTiles = 512 * 512;    // 8 x 8 tiles of a 4096 x 4096 frame
+struct SsrClassifyArgs {
+    const void* scene; const float* depth; const void* variance;      // variance: R16F plane or NULL (reads 0)
+    uint32_t* rayList; uint32_t* counters; uint32_t* tileList;        // tileList may be NULL
+    uint32_t* tileRays; uint32_t* tileFlag;                           // context-owned, kMaxSsrTiles each: per-tile ray count / "has a glossy reflective pixel", scanned in place
+    int width, height, scenePitch, depthPitch, variancePitch, sceneF32, tilesX, tilesY;
+    float roughnessThreshold, varianceThreshold;
+    uint32_t samplesPerQuad, varianceGuided;
+};
+struct SsrTraceArgs {
+    const uint32_t* rayList; const uint32_t* counters;
+    const void* lit; const float* mips; const void* normals; const uint8_t* roughness; const uint8_t* noise; void* out;
+    int width, height, litPitch, normalPitch, outPitch, litF32, normF32, outF32, levels;
+    VQ_matrix invViewProj, proj, invProj, view, invView;
+    float rot[3][3];                      // upper-left 3x3 of envMapRotation
+    float invDimX, invDimY, thickness;
+    uint32_t maxIter, minOcc, mostDetailedMip;
+    int pow5ExpLog, arithDxc;
+    vqhip_envmap env;
+};
+hipError_t launch_ssr_classify(hipStream_t s, const SsrClassifyArgs& a);
+hipError_t launch_ssr_intersect(hipStream_t s, const SsrTraceArgs& a, int nCUs);
+
 // 4x MSAA lit draw + resolve (vqhip_forward_lighting_msaa, msaa.hip). Edge pixels (samples with more than one owner) are listed by the
 // shading kernel in edgeList[0 .. *edgeCount) as y * width + x; *edgeCount is zeroed on the call's stream before the launch.
 struct MsaaLayer { const float4* gb0; const float4* gb1; const float4* gb2; const float4* gb3; const uint8_t* cov; int pitch; };

@@ -459,6 +459,83 @@ def ssr_surfaces(width, height, seed=0x55E7, sky_fraction=0.1):
     return scene, depth, packed, n01
 
 
+def _matrix_of(m):
+    return np.array([[m.m[i][j] for j in range(4)] for i in range(4)], np.float64)
+
+
+def ssr_room(width, height, spec_mips=1, seed=0x5500A, **constants):
+    """A deterministic scene that SSR rays can actually hit, for vqhip_ssr_classify / vqhip_ssr_intersect: a floor (y = 0), a back wall and two side walls of a room
+    open to the sky, and a few axis-aligned boxes standing on the floor, ray-cast (float64) through the pixel centres of the LookAtLH / PerspectiveFovLH camera whose
+    matrices ssr_constants(width, height, spec_mips, **constants) fills. Returns a dict:
+      cb      abi.SSSRConstants (ssr_constants)
+      depth   float32 [H,W]   NDC z in [0, 1) of the nearest surface, sky = 1
+      packed  uint32 [H,W]    face normals, n * 0.5 + 0.5 quantised to R10G10B10A2_UNORM;   n01 float32 [H,W,4]: the decoded values
+      scene   float32 [H,W,4] the lit scene; alpha = roughness: the floor in world-space stripes of mirror (0.02), glossy (0.06 .. 0.16) and rough (0.6) bands, the back
+              wall glossy, the side walls rough, the boxes mirror / glossy / rough in turn; sky pixels 0.9
+      noise   uint8 [128,128,2] a seeded stand-in for g_blue_noise_texture (white, not blue: the contract only needs two UNORM8 numbers per pixel)"""
+    cb = ssr_constants(width, height, spec_mips, **constants)
+    view, proj = _matrix_of(cb.view), _matrix_of(cb.projection)
+    inv_view = np.linalg.inv(view)
+    eye = inv_view[3, :3]
+    xs = (np.arange(width) + 0.5) / width * 2.0 - 1.0
+    ys = 1.0 - (np.arange(height) + 0.5) / height * 2.0
+    dv = np.stack(np.broadcast_arrays(xs[None, :] / proj[0, 0], ys[:, None] / proj[1, 1], 1.0), -1)          # view-space direction with z = 1
+    d = dv @ inv_view[:3, :3]                                                                                  # row vectors
+    big = 1e30
+    t_best = np.full((height, width), big)
+    nrm = np.zeros((height, width, 3))
+    obj = np.full((height, width), -1, np.int64)
+
+    def plane(axis, value, normal, lo, hi, ident):
+        nonlocal t_best, nrm, obj
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = (value - eye[axis]) / d[..., axis]
+        p = eye + t[..., None] * d
+        ok = (t > 0) & (t < t_best) & np.isfinite(t)
+        for a in range(3):
+            if a != axis:
+                ok &= (p[..., a] >= lo[a]) & (p[..., a] <= hi[a])
+        t_best = np.where(ok, t, t_best)
+        nrm[ok] = normal
+        obj[ok] = ident
+
+    plane(1, 0.0, (0, 1, 0), (-45, 0, -90), (45, 0, 40), 0)          # floor
+    plane(2, 40.0, (0, 0, -1), (-45, 0, 0), (45, 32, 0), 1)          # back wall
+    plane(0, -45.0, (1, 0, 0), (0, 0, -90), (0, 32, 40), 2)          # side walls
+    plane(0, 45.0, (-1, 0, 0), (0, 0, -90), (0, 32, 40), 3)
+    boxes = [((-30, 0, 5), (-18, 14, 17)), ((-8, 0, -12), (4, 9, -2)), ((12, 0, 8), (26, 20, 22)), ((20, 0, -30), (28, 6, -22)), ((-26, 0, -34), (-16, 11, -26))]
+    for k, (lo, hi) in enumerate(boxes):
+        for axis in range(3):
+            for value, sgn in ((lo[axis], -1.0), (hi[axis], 1.0)):
+                n = [0.0, 0.0, 0.0]
+                n[axis] = sgn
+                plane(axis, float(value), tuple(n), lo, hi, 4 + k)
+    hit = obj >= 0
+    p = eye + np.where(hit, t_best, 1.0)[..., None] * d
+    pv = np.concatenate([p, np.ones((height, width, 1))], -1) @ view @ proj
+    depth = np.where(hit, pv[..., 2] / pv[..., 3], 1.0).astype(np.float32)
+    depth = np.where(hit, np.minimum(depth, np.nextafter(np.float32(1), np.float32(0))), np.float32(1.0)).astype(np.float32)
+    n = np.where(hit[..., None], nrm, [0.0, 0.0, -1.0])
+    q = np.clip(np.floor((n * 0.5 + 0.5) * 1023.0 + 0.5), 0, 1023).astype(np.uint32)
+    packed = (q[..., 0] | (q[..., 1] << 10) | (q[..., 2] << 20) | (np.uint32(3) << 30)).astype(np.uint32)
+    n01 = np.concatenate([q.astype(np.float32) / np.float32(1023.0), np.ones((height, width, 1), np.float32)], axis=-1)
+    stripe = np.floor((p[..., 0] + 45.0) / 7.5).astype(np.int64) % 6
+    floor_rough = np.array([0.02, 0.06, 0.6, 0.1, 0.02, 0.16])[stripe]
+    box_rough = np.array([0.02, 0.12, 0.5, 0.08, 0.02])
+    rough = np.full((height, width), 0.9)
+    rough = np.where(obj == 0, floor_rough, rough)
+    rough = np.where(obj == 1, 0.1, rough)
+    rough = np.where((obj == 2) | (obj == 3), 0.45, rough)
+    for k in range(len(boxes)):
+        rough = np.where(obj == 4 + k, box_rough[k], rough)
+    palette = np.array([[0.35, 0.33, 0.30], [0.9, 0.55, 0.2], [0.2, 0.5, 0.9], [0.3, 0.8, 0.4], [2.5, 0.4, 0.3], [0.3, 2.0, 0.6], [0.4, 0.5, 3.0], [1.5, 1.4, 0.2], [0.9, 0.2, 1.6]])
+    shade = 0.6 + 0.4 * np.sin(0.35 * p[..., 0]) * np.cos(0.27 * p[..., 1] + 0.19 * p[..., 2])
+    rgb = np.where(hit[..., None], palette[np.clip(obj, 0, len(palette) - 1)] * shade[..., None], [0.6, 0.7, 1.1])
+    scene = np.concatenate([rgb, rough[..., None]], -1).astype(np.float32)
+    noise = _chunk_rng(seed, 0).integers(0, 256, (abi.SSR_BLUE_NOISE_SIZE, abi.SSR_BLUE_NOISE_SIZE, 2), dtype=np.uint8)
+    return {"cb": cb, "depth": depth, "packed": packed, "n01": n01, "scene": scene, "noise": noise}
+
+
 def gbuffer_msaa(width, height, layers=2, split_fraction=0.05, seed=0x4A4A, mode="edges"):
     """Fragment layers of a 4x MSAA frame for vqhip_forward_lighting_msaa: (list of `layers` G-buffers as from gbuffer(), list of uint8 [H,W]
     coverage planes). mode "edges": layer 0 is gbuffer(width, height, seed); the others are other records. Random discs and triangles
