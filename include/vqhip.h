@@ -64,7 +64,9 @@ typedef enum vqhip_format {
     VQHIP_FMT_RGBA8_UNORM = 2,
     VQHIP_FMT_RG16F       = 3,
     VQHIP_FMT_RG32F       = 4,
-    VQHIP_FMT_R10G10B10A2_UNORM = 5   /* Tex_SceneNormals (RenderResources.cpp:185-197): output of vqhip_scene_normals_from_materials, input of vqhip_ssr_environment_fallback */
+    VQHIP_FMT_R10G10B10A2_UNORM = 5,  /* Tex_SceneNormals (RenderResources.cpp:185-197): output of vqhip_scene_normals_from_materials, input of vqhip_ssr_environment_fallback */
+    VQHIP_FMT_R11G11B10_FLOAT = 6     /* TexAverageRadiance of the reflection denoiser: one uint32 per texel, R bits 0-10, G 11-21, B 22-31; unsigned, 5-bit exponent (bias 15),
+                                       * 6 / 6 / 5 mantissa bits, denormals / inf / NaN as DXGI; decoded exactly. Read only: vqhip_ssr_prefilter, vqhip_ssr_resolve_temporal */
 } vqhip_format;
 
 /* ------------------------------------------------------------------------------------------------
@@ -343,7 +345,7 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * later in round 4, additions only: vqhip_forward_lighting_mrt, vqhip_forward_lighting_from_materials_mrt, vqhip_scene_normals_from_materials,
                                * vqhip_composite_reflections; vqhip_visualize reads R10G10B10A2 / RG16F / RG32F inputs.
                                * Later additions to 3: vqhip_gbuffer_msaa, vqhip_forward_lighting_msaa; vqhip_msaa_surfaces, vqhip_msaa_resolve_surfaces, vqhip_depth_hierarchy (+ _bytes, _level_offset_bytes);
-                               * vqhip_ssr_classify, vqhip_ssr_intersect */
+                               * vqhip_ssr_classify, vqhip_ssr_intersect; vqhip_ssr_prefilter, vqhip_ssr_resolve_temporal, VQHIP_FMT_R11G11B10_FLOAT */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -737,8 +739,8 @@ VQHIP_API int vqhip_fsr_rcas(vqhip_ctx* ctx, void* stream, const void* in, void*
  * outFmt RGBA8_UNORM | RGBA16F | RGBA32F. */
 /* Replaces ApplyReflectionsPass::RecordCommands (ApplyReflections.cpp:45-80) == ApplyReflections.hlsl:CSMain :30-50 without
  * COMPOSITE_BOUNDING_VOLUMES: sceneColor.rgb += reflectionRadiance.rgb, alpha (roughness) kept; in place on the scene colour.
- * (The reflection radiance comes from vqhip_ssr_environment_fallback + vqhip_ssr_classify + vqhip_ssr_intersect below; only the FidelityFX reflection DENOISER
- * is out of scope.) fmt: RGBA16F | RGBA32F for both. */
+ * (The reflection radiance comes from vqhip_ssr_environment_fallback + vqhip_ssr_classify + vqhip_ssr_intersect below, denoised by vqhip_ssr_prefilter +
+ * vqhip_ssr_resolve_temporal; of the FidelityFX reflection DENOISER only Reproject and PrepareBlueNoiseTexture are out of scope.) fmt: RGBA16F | RGBA32F for both. */
 VQHIP_API int vqhip_apply_reflections(vqhip_ctx* ctx, void* stream, const void* reflectionRadiance, void* sceneColor,
         int width, int height, vqhip_format fmt);
 /* Replaces VQRenderer::CompositeReflections (SceneRendering.cpp:2362-2403): ApplyReflectionsPass in the permutation its parameters select
@@ -773,8 +775,9 @@ VQHIP_STATIC_ASSERT(offsetof(VQ_SSSRConstants, bufferDimensions) == 448 && offse
  * i.e. surfaces too rough for a traced ray get the environment's prefiltered reflection: view-space reflect of the view ray about the G-buffer normal,
  * g_environment_map.SampleLevel(envMapRotation * R_world, roughness * (mipCount - 1)) — a FRACTIONAL level: trilinear between cube mips, seamless
  * (csrc/vq_sampling.h:sample_cube_lod_rgba16f) — times EnvironmentBRDF(NdotV, roughness, metallic 1, ...) from the LUT (BRDF.hlsl:196-207).
- * The ray classification / ray list / denoiser tile list of the same dispatch is vqhip_ssr_classify, the traced rays are vqhip_ssr_intersect (below); what stays out
- * of scope is the reflection denoiser (Reproject / Prefilter / ResolveTemporal, PrepareBlueNoiseTexture and its Sobol tables).
+ * The ray classification / ray list / denoiser tile list of the same dispatch is vqhip_ssr_classify, the traced rays are vqhip_ssr_intersect (below); the denoiser's
+ * Prefilter and ResolveTemporal are vqhip_ssr_prefilter / vqhip_ssr_resolve_temporal; what stays out of scope is the denoiser's Reproject pass and
+ * PrepareBlueNoiseTexture with its Sobol tables.
  *   sceneColorRoughness : g_roughness   == the scene colour whose alpha is the roughness (ForwardLighting.hlsl:380), RGBA16F | RGBA32F
  *   depth               : g_depth_buffer == mip 0 of the depth hierarchy, R32F, NDC z (far plane 1)
  *   normals             : g_normal      == Tex_SceneNormals, R10G10B10A2_UNORM (one uint32 per pixel, r in bits 0-9) | RGBA32F holding the same [0,1] values
@@ -837,6 +840,50 @@ VQHIP_API int vqhip_ssr_intersect(vqhip_ctx* ctx, void* stream,
         const uint8_t* extractedRoughness, const uint8_t* blueNoise,
         const VQ_SSSRConstants* cb, const vqhip_envmap* env,
         void* radiance, vqhip_format radianceFmt, int radiancePitchPx);
+
+/* Replaces the "FFX DNSR Prefilter" and "FFX DNSR Resolve Temporal" dispatches (ScreenSpaceReflections.cpp, between the march and the composite) ==
+ * Prefilter.hlsl:CSMain + ffx_denoiser_reflections_prefilter.h (15-tap edge-stopping spatial filter) and ResolveTemporal.hlsl:CSMain +
+ * ffx_denoiser_reflections_resolve_temporal.h (9 x 9 local moments, history clip, blend) for every 8 x 8 tile of the denoiser tile list. The float32 contract —
+ * expression order, the binary16 round trip of the values the reference packs into group-shared memory, exp(x) = exp2(x * 1.44269502f), loads outside the frame
+ * reading 0, FFX_DNSR_Reflections_RoundUp8 as written, the bilinear CLAMP fetch of the 1/8-resolution average radiance — is docs/DESIGN_DETAILS.md §7.12;
+ * tests/ssr_denoise_ref.py states it in numpy. Reproject (pass 1), which produces averageRadiance, variance, sampleCount and reprojectedRadiance, is not part of
+ * the library yet: the caller provides those planes.
+ *   denoiserTileList, counters : as vqhip_ssr_classify wrote them; counters[1] tiles, read on the device (no host synchronisation) and clamped to
+ *                                ceil(w/8) * ceil(h/8), the number of entries the list must hold. An entry is (y << 16) | x; its tile is DEFINED by this contract as (x >> 3, y >> 3) — for the 8-aligned entries
+ *                                vqhip_ssr_classify writes that is what CSMain computes; the shader itself gives an unaligned entry no single tile; an entry
+ *                                beyond the tile grid is skipped, duplicates and any order are fine. Pixels of unlisted tiles are not written.
+ *   depth                      : level 0 of the depth hierarchy, R32F
+ *   normals                    : g_normal, R10G10B10A2_UNORM | RGBA32F
+ *   extractedRoughness         : R8_UNORM, row pitch = width (vqhip_ssr_environment_fallback's output)
+ *   averageRadiance            : [ceil(h/8)][ceil(w/8)], tightly packed, R11G11B10_FLOAT | RGBA32F
+ *   radiance                   : RGBA16F | RGBA32F — the traced radiance (prefilter) / the prefiltered radiance (temporal resolve)
+ *   reprojectedRadiance        : RGBA16F | RGBA32F
+ *   variance, sampleCount      : R16F planes (one half per pixel)
+ *   cb                         : host pointer; bufferDimensions (each <= 4096, else VQHIP_ERR_UNSUPPORTED), roughnessThreshold, invProjection (prefilter),
+ *                                temporalStabilityFactor (temporal resolve) are read
+ *   outRadiance                : RGBA16F | RGBA32F, radiance.xyzz (alpha = blue); outVariance: R16F. Stores round to nearest even. The sample-count target the
+ *                                shaders declare is never written by them and is not an argument.
+ * Outputs must not overlap any input of the same call (the apron reads neighbours other tiles write; the engine ping-pongs): VQHIP_ERR_INVALID_ARG.
+ * Pitches in pixels (0 = width). PARITY UNPINNED like §7.9 - §7.11 (docs/WARP_CALIBRATION.md §7). */
+VQHIP_API int vqhip_ssr_prefilter(vqhip_ctx* ctx, void* stream,
+        const uint32_t* denoiserTileList, const uint32_t* counters,
+        const float* depth, int depthPitchPx,
+        const void* normals, vqhip_format normalFmt, int normalPitchPx,
+        const uint8_t* extractedRoughness,
+        const void* averageRadiance, vqhip_format avgFmt,
+        const void* radiance, vqhip_format radianceFmt, int radiancePitchPx,
+        const void* variance, int variancePitchPx,
+        const VQ_SSSRConstants* cb,
+        void* outRadiance, vqhip_format outFmt, int outPitchPx, void* outVariance, int outVariancePitchPx);
+VQHIP_API int vqhip_ssr_resolve_temporal(vqhip_ctx* ctx, void* stream,
+        const uint32_t* denoiserTileList, const uint32_t* counters,
+        const uint8_t* extractedRoughness,
+        const void* averageRadiance, vqhip_format avgFmt,
+        const void* radiance, vqhip_format radianceFmt, int radiancePitchPx,
+        const void* reprojectedRadiance, vqhip_format reprojectedFmt, int reprojectedPitchPx,
+        const void* variance, int variancePitchPx, const void* sampleCount, int sampleCountPitchPx,
+        const VQ_SSSRConstants* cb,
+        void* outRadiance, vqhip_format outFmt, int outPitchPx, void* outVariance, int outVariancePitchPx);
 
 typedef struct VQ_VizParams { int32_t iDrawMode; int32_t iUnpackNormals; float fInputStrength; } VQ_VizParams;
 VQHIP_API int vqhip_visualize(vqhip_ctx* ctx, void* stream, const void* in, void* out, int width, int height,

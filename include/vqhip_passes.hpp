@@ -364,7 +364,7 @@ private:
 // SSR rays == the ray list of the "FFX DNSR ClassifyTiles" dispatch + the "FFX SSSR Intersection" dispatch of
 // ScreenSpaceReflectionsPass::RecordCommands (ScreenSpaceReflections.cpp:262-320): vqhip_ssr_classify + vqhip_ssr_intersect. Owns TexRayList,
 // TexRayCounter and TexDenoiserTileList (ScreenSpaceReflections.cpp:118-127, as plain device buffers); traces IN PLACE into the TexRadiance that
-// HipSSREnvironmentFallbackPass owns and has filled on the same stream. Without a denoiser behind it, run it with ffxCBuffer.samplesPerQuad = 4: every
+// HipSSREnvironmentFallbackPass owns and has filled on the same stream. Without the denoiser passes behind it (HipSSRPrefilterPass / HipSSRResolveTemporalPass below; Reproject is the caller's), run it with ffxCBuffer.samplesPerQuad = 4: every
 // glossy pixel then traces its own ray and the radiance is directly what vqhip_composite_reflections consumes.
 // ---------------------------------------------------------------------------------------------------------------
 class HipSSRIntersectPass : public RenderPassBase {
@@ -409,6 +409,76 @@ public:
 private:
     void* mRayList = nullptr; void* mRayCounter = nullptr; void* mDenoiserTileList = nullptr;
     unsigned mWidth = 0, mHeight = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// Reflection denoiser, pass 2 == the "FFX DNSR Prefilter" dispatch of ScreenSpaceReflectionsPass::RecordCommands (ScreenSpaceReflections.cpp:387-397):
+// vqhip_ssr_prefilter. Reads TexRadiance[i] / TexVariance[i] / TexAvgRadiance[i] and writes TexRadiance[1 - i] / TexVariance[1 - i] (:1199-1212): the pass owns
+// nothing, the caller ping-pongs. Pixels of unlisted tiles are not written.
+// ---------------------------------------------------------------------------------------------------------------
+class HipSSRPrefilterPass : public RenderPassBase {
+public:
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        VQ_SSSRConstants ffxCBuffer = {};
+        const uint32_t* TexDenoiserTileList = nullptr;           // HipSSRIntersectPass::GetDenoiserTileList()
+        const uint32_t* TexRayCounter = nullptr;                 // HipSSRIntersectPass::GetRayCounter(): [1] = tiles
+        const float* TexDepthHierarchy = nullptr;                // mip 0, R32F
+        const void* TexNormals = nullptr;                        // R10G10B10A2_UNORM
+        const uint8_t* TexExtractedRoughness = nullptr;          // R8_UNORM
+        const void* TexAvgRadiance = nullptr;                    // R11G11B10_FLOAT, ceil(w/8) x ceil(h/8)
+        const void* TexRadianceIn = nullptr;                     // TexRadiance[i], RGBA16F
+        const void* TexVarianceIn = nullptr;                     // TexVariance[i], R16F
+        void* TexRadianceOut = nullptr;                          // TexRadiance[1 - i]
+        void* TexVarianceOut = nullptr;                          // TexVariance[1 - i]
+    };
+    explicit HipSSRPrefilterPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override {}
+    void OnCreateWindowSizeDependentResources(unsigned, unsigned, const IRenderPassResourceCollection* = nullptr) override {}
+    void OnDestroyWindowSizeDependentResources() override {}
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        mStatus = vqhip_ssr_prefilter(mCtx, p->Stream, p->TexDenoiserTileList, p->TexRayCounter, p->TexDepthHierarchy, 0, p->TexNormals, VQHIP_FMT_R10G10B10A2_UNORM, 0,
+                                      p->TexExtractedRoughness, p->TexAvgRadiance, VQHIP_FMT_R11G11B10_FLOAT, p->TexRadianceIn, VQHIP_FMT_RGBA16F, 0, p->TexVarianceIn, 0,
+                                      &p->ffxCBuffer, p->TexRadianceOut, VQHIP_FMT_RGBA16F, 0, p->TexVarianceOut, 0);
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// Reflection denoiser, pass 3 == the "FFX DNSR Resolve Temporal" dispatch (ScreenSpaceReflections.cpp:413-423): vqhip_ssr_resolve_temporal. Reads what the
+// prefilter wrote (TexRadiance[1 - i], TexVariance[1 - i]), TexReprojectedRadiance and TexSampleCount[1 - i] (:1214-1222), writes TexRadiance[i] / TexVariance[i] —
+// the image vqhip_composite_reflections consumes (:1230).
+// ---------------------------------------------------------------------------------------------------------------
+class HipSSRResolveTemporalPass : public RenderPassBase {
+public:
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        VQ_SSSRConstants ffxCBuffer = {};
+        const uint32_t* TexDenoiserTileList = nullptr;
+        const uint32_t* TexRayCounter = nullptr;
+        const uint8_t* TexExtractedRoughness = nullptr;
+        const void* TexAvgRadiance = nullptr;                    // R11G11B10_FLOAT
+        const void* TexRadianceIn = nullptr;                     // TexRadiance[1 - i], RGBA16F (the prefiltered radiance)
+        const void* TexReprojectedRadiance = nullptr;            // RGBA16F
+        const void* TexVarianceIn = nullptr;                     // TexVariance[1 - i], R16F
+        const void* TexSampleCountIn = nullptr;                  // TexSampleCount[1 - i], R16F
+        void* TexRadianceOut = nullptr;                          // TexRadiance[i]
+        void* TexVarianceOut = nullptr;                          // TexVariance[i]
+    };
+    explicit HipSSRResolveTemporalPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override {}
+    void OnCreateWindowSizeDependentResources(unsigned, unsigned, const IRenderPassResourceCollection* = nullptr) override {}
+    void OnDestroyWindowSizeDependentResources() override {}
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        mStatus = vqhip_ssr_resolve_temporal(mCtx, p->Stream, p->TexDenoiserTileList, p->TexRayCounter, p->TexExtractedRoughness, p->TexAvgRadiance, VQHIP_FMT_R11G11B10_FLOAT,
+                                             p->TexRadianceIn, VQHIP_FMT_RGBA16F, 0, p->TexReprojectedRadiance, VQHIP_FMT_RGBA16F, 0, p->TexVarianceIn, 0, p->TexSampleCountIn, 0,
+                                             &p->ffxCBuffer, p->TexRadianceOut, VQHIP_FMT_RGBA16F, 0, p->TexVarianceOut, 0);
+    }
 };
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,144 @@
+"""vqhip_ssr_prefilter and vqhip_ssr_resolve_temporal (docs/DESIGN_DETAILS.md §7.12) on synth.ssr_room at 3840 x 2160 (default; --size W H for others): one JSON
+line. Needs the GPU. In one process, alternating per step: a device-to-device copy of a buffer of the passes' traffic (the bandwidth yardstick), the prefilter,
+the temporal resolve; device events around each call, warm-up, the median over the steps. The tile list is the one vqhip_ssr_classify writes for the room; the
+planes Reproject would write are synth.ssr_denoise_planes around the room's lit scene (the kernels' time does not depend on where the radiance came from, only
+on which branches the pixels take — the branch shares are reported from the inputs).
+Bytes moved by construction, per listed tile: the 16 x 16 apron of every plane a pass reads with a neighbourhood, 8 x 8 of every plane it reads at the pixel and of
+both outputs (the 1/8-resolution average radiance is 4 texels per tile at most and is left out).
+  --variant-lib PATH  A/B: a second build of the library (for instance one whose csrc/ssr_denoise.hip keeps the apron in another LDS form) is loaded into the same
+                      process and its two passes are timed alternating with the committed library's, step by step; its outputs are compared bit for bit.
+  --mode resources    (CPU only) registers, scratch, LDS and occupancy of the two kernels from the compiler's own report: csrc/ssr_denoise.hip compiled with the
+                      flags `make -n` prints for ssr_denoise.o plus -Rpass-analysis=kernel-resource-usage; --source FILE reports another source the same way."""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from vqengine_amd import abi, synth   # noqa: E402
+
+F16, N10, R11 = abi.FMT_RGBA16F, abi.FMT_R10G10B10A2_UNORM, abi.FMT_R11G11B10_FLOAT
+# bytes per listed tile: apron texels x bytes + pixel texels x bytes
+PREFILTER_BYTES = 256 * (8 + 2 + 4 + 4) + 64 * (1 + 8 + 2)           # apron: radiance RGBA16F, variance R16F, normals, depth; pixel: roughness, out radiance, out variance
+RESOLVE_BYTES = 256 * 8 + 64 * (1 + 2 + 2 + 8 + 8 + 2)               # apron: radiance; pixel: roughness, variance, sample count, reprojected, out radiance, out variance
+
+
+def unorm8(x):
+    x = np.where(np.isnan(x), np.float32(0), np.clip(x, np.float32(0), np.float32(1))).astype(np.float32)
+    return (x * np.float32(255.0) + np.float32(0.5)).astype(np.uint8)
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "vqengine_amd", "csrc")
+
+
+def resources(source):
+    """the compiler's resource report for the kernels of `source`, built with the Makefile's own command line for ssr_denoise.o"""
+    line = [l for l in subprocess.run(["make", "-n", "-B", "ssr_denoise.o"], cwd=CSRC, capture_output=True, text=True, check=True).stdout.splitlines() if "ssr_denoise.hip" in l][0]
+    cmd = line.split()
+    cmd[cmd.index("-c") + 1] = os.path.abspath(source)
+    with tempfile.TemporaryDirectory() as d:
+        cmd[cmd.index("-o") + 1] = os.path.join(d, "o.o")
+        err = subprocess.run(cmd + ["-I", CSRC, "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, text=True, check=True).stderr
+    rows, cur = [], None
+    for l in err.splitlines():
+        m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", l)
+        if not m:
+            continue
+        if m.group(1) == "Function Name":
+            k = re.search(r"(k_ssr_\w+?)ENS", m.group(2))
+            cur = {"kernel": k.group(1) if k else m.group(2)}
+            rows.append(cur)
+        elif cur is not None:
+            cur[{"VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane", "Occupancy [waves/SIMD]": "waves_per_simd",
+                 "LDS Size [bytes/block]": "lds_bytes_per_workgroup"}[m.group(1)]] = int(m.group(2))
+    return {"bench": "ssr_denoise_resources", "source": os.path.relpath(os.path.abspath(source), ROOT), "flags": " ".join(c for c in cmd[1:] if c.startswith("-") and c not in ("-c", "-o")),
+            "kernels": rows}
+
+
+def second_context(capi, path):
+    """a Context bound to another build of the library, in this process"""
+    saved = capi._lib, capi._LIB_PATH
+    capi._lib, capi._LIB_PATH = None, os.path.abspath(path)
+    try:
+        return capi.Context(0)
+    finally:
+        capi._lib, capi._LIB_PATH = saved
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["time", "resources"], default="time")
+    ap.add_argument("--source", default=os.path.join(CSRC, "ssr_denoise.hip"))
+    ap.add_argument("--variant-lib", default=None)
+    ap.add_argument("--size", type=int, nargs=2, default=[3840, 2160])
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+    if a.mode == "resources":
+        print(json.dumps(resources(a.source)))
+        return
+    import torch
+    from vqengine_amd import capi
+    w, h = a.size
+    ctx = capi.Context(0)
+    ctx2 = second_context(capi, a.variant_lib) if a.variant_lib else None
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()   # noqa: E731
+    rm = synth.ssr_room(w, h, 1)
+    cb = rm["cb"]
+    pl = synth.ssr_denoise_planes(w, h, seed=0xBE10, radiance=rm["scene"])
+    scene = dev(rm["scene"].astype(np.float16))
+    depth, normals = dev(rm["depth"]), dev(rm["packed"].view(np.int32))
+    r8 = dev(unorm8(rm["scene"][..., 3]))
+    _, counters, tiles = ctx.ssr_classify(scene, F16, depth, cb)
+    avg, rad, rep = dev(pl["average_r11"].view(np.int32)), dev(pl["radiance"].astype(np.float16)), dev(pl["reprojected"].astype(np.float16))
+    var, cnt = dev(pl["variance"]), dev(pl["sample_count"])
+    p_r, p_v = torch.zeros_like(rad), torch.zeros_like(var)
+    t_r, t_v = torch.zeros_like(rad), torch.zeros_like(var)
+    n_tiles = int(counters.cpu().numpy().view(np.uint32)[1])
+    copy_bytes = max(PREFILTER_BYTES, RESOLVE_BYTES) * n_tiles // 2          # a copy reads and writes every byte: half the traffic each way
+    src, dst = torch.empty(copy_bytes, dtype=torch.uint8, device="cuda"), torch.empty(copy_bytes, dtype=torch.uint8, device="cuda")
+    calls = {"copy": lambda: dst.copy_(src),
+             "prefilter": lambda: ctx.ssr_prefilter(tiles, counters, depth, normals, N10, r8, avg, R11, rad, F16, var, cb, out=p_r, out_variance=p_v),
+             "resolve_temporal": lambda: ctx.ssr_resolve_temporal(tiles, counters, r8, avg, R11, p_r, F16, rep, F16, p_v, cnt, cb, out=t_r, out_variance=t_v)}
+    if ctx2 is not None:
+        v_r, v_v, u_r, u_v = torch.zeros_like(rad), torch.zeros_like(var), torch.zeros_like(rad), torch.zeros_like(var)
+        calls["variant_prefilter"] = lambda: ctx2.ssr_prefilter(tiles, counters, depth, normals, N10, r8, avg, R11, rad, F16, var, cb, out=v_r, out_variance=v_v)
+        calls["variant_resolve_temporal"] = lambda: ctx2.ssr_resolve_temporal(tiles, counters, r8, avg, R11, p_r, F16, rep, F16, p_v, cnt, cb, out=u_r, out_variance=u_v)
+    times = {k: [] for k in calls}
+    for step in range(a.warmup + a.steps):
+        for k, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record()
+            e1.synchronize()
+            if step >= a.warmup:
+                times[k].append(e0.elapsed_time(e1) * 1e3)
+    us = {k: float(np.median(v)) for k, v in times.items()}
+    copy_gbs = 2 * copy_bytes / us["copy"] / 1e3
+    rough = unorm8(rm["scene"][..., 3]).astype(np.float32) / np.float32(255.0)
+    glossy = rough < np.float32(cb.roughnessThreshold)
+    out = {"bench": "ssr_denoise", "width": w, "height": h, "steps": a.steps, "tiles": n_tiles, "tile_grid": ((w + 7) // 8) * ((h + 7) // 8),
+           "share_denoised_by_prefilter": round(float((glossy & ~(rough < np.float32(0.04)) & (pl["variance"] > 0)).mean()), 4), "share_glossy": round(float(glossy.mean()), 4),
+           "prefilter_us": round(us["prefilter"], 1), "resolve_temporal_us": round(us["resolve_temporal"], 1), "copy_us": round(us["copy"], 1),
+           "prefilter_bytes": PREFILTER_BYTES * n_tiles, "resolve_temporal_bytes": RESOLVE_BYTES * n_tiles, "copy_GBps": round(copy_gbs, 1),
+           "prefilter_fraction_of_copy_bandwidth": round(PREFILTER_BYTES * n_tiles / us["prefilter"] / 1e3 / copy_gbs, 4),
+           "resolve_temporal_fraction_of_copy_bandwidth": round(RESOLVE_BYTES * n_tiles / us["resolve_temporal"] / 1e3 / copy_gbs, 4)}
+    spread = lambda k: [round(float(min(times[k])), 1), round(float(max(times[k])), 1)]   # noqa: E731
+    out["prefilter_us_min_max"], out["resolve_temporal_us_min_max"] = spread("prefilter"), spread("resolve_temporal")
+    if ctx2 is not None:
+        same = lambda x, y: bool(torch.equal(x.view(torch.int16), y.view(torch.int16)))   # noqa: E731
+        out.update(variant_lib=os.path.basename(a.variant_lib), variant_prefilter_us=round(us["variant_prefilter"], 1), variant_resolve_temporal_us=round(us["variant_resolve_temporal"], 1),
+                   variant_prefilter_us_min_max=spread("variant_prefilter"), variant_resolve_temporal_us_min_max=spread("variant_resolve_temporal"),
+                   variant_bits_equal=same(p_r, v_r) and same(p_v, v_v) and same(t_r, u_r) and same(t_v, u_v))
+        ctx2.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

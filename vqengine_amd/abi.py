@@ -12,6 +12,7 @@ VQHIP_ERR_RCCL = -5
 
 FMT_RGBA32F, FMT_RGBA16F, FMT_RGBA8_UNORM, FMT_RG16F, FMT_RG32F = 0, 1, 2, 3, 4
 FMT_R10G10B10A2_UNORM = 5          # Tex_SceneNormals: input of ssr_environment_fallback only
+FMT_R11G11B10_FLOAT = 6            # TexAverageRadiance: input of ssr_prefilter / ssr_resolve_temporal only (one uint32 per texel)
 FMT_BPP = {FMT_RGBA32F: 16, FMT_RGBA16F: 8, FMT_RGBA8_UNORM: 4, FMT_RG16F: 4, FMT_RG32F: 8}
 CONV_SEQUENTIAL, CONV_WAVE64 = 0, 1
 ARITH_LITERAL, ARITH_DXC = 0, 1

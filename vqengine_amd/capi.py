@@ -99,6 +99,10 @@ def load_library():
         "vqhip_ssr_classify": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, i32, C.POINTER(abi.SSSRConstants), vp, vp, vp]),
         "vqhip_ssr_intersect": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, C.POINTER(abi.SSSRConstants), C.POINTER(abi.EnvMap),
                                       vp, i32, i32]),
+        "vqhip_ssr_prefilter": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, i32, i32, vp, i32, C.POINTER(abi.SSSRConstants),
+                                      vp, i32, i32, vp, i32]),
+        "vqhip_ssr_resolve_temporal": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, i32, vp, i32, C.POINTER(abi.SSSRConstants),
+                                             vp, i32, i32, vp, i32]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -130,7 +134,7 @@ EXPORTED_SYMBOLS = [
     "vqhip_rowtile", "vqhip_comm_unique_id", "vqhip_comm_create", "vqhip_comm_adopt", "vqhip_comm_destroy", "vqhip_comm_query", "vqhip_comm_abort", "vqhip_comm_loopback", "vqhip_exchange_blur_halos",
     "vqhip_composite_tiles", "vqhip_forward_lighting_msaa",
     "vqhip_msaa_resolve_surfaces", "vqhip_depth_hierarchy", "vqhip_depth_hierarchy_bytes", "vqhip_depth_hierarchy_level_offset_bytes",
-    "vqhip_ssr_classify", "vqhip_ssr_intersect",
+    "vqhip_ssr_classify", "vqhip_ssr_intersect", "vqhip_ssr_prefilter", "vqhip_ssr_resolve_temporal",
 ]
 
 
@@ -763,6 +767,69 @@ class Context:
                                               _ptr(normals), normal_fmt, 0, _ptr(roughness8), _ptr(blue_noise), C.byref(cb), C.byref(env),
                                               _ptr(radiance), radiance_fmt, 0))
         return radiance
+
+    # ---- SSR denoiser passes 2 and 3 (docs/DESIGN_DETAILS.md §7.12) ------------------------------------------------
+    def _denoise_common(self, who, tile_list, counters, roughness8, average, avg_fmt, cb, planes, out, out_fmt, out_variance):
+        w, h = int(cb.bufferDimensions[0]), int(cb.bufferDimensions[1])
+        tiles = ((w + 7) // 8) * ((h + 7) // 8)
+        if not (tile_list.is_cuda and tile_list.dtype == torch.int32 and tile_list.is_contiguous() and tile_list.numel() >= tiles):
+            raise ValueError(f"{who}: tile_list: expected contiguous cuda int32 [{tiles}]")
+        if not (counters.is_cuda and counters.dtype == torch.int32 and counters.numel() >= 2 and counters.is_contiguous()):
+            raise ValueError(f"{who}: counters: expected contiguous cuda int32 [2]")
+        if not (roughness8.is_cuda and roughness8.dtype == torch.uint8 and tuple(roughness8.shape) == (h, w) and roughness8.is_contiguous()):
+            raise ValueError(f"{who}: roughness8: expected contiguous cuda uint8 {(h, w)}")
+        h8, w8 = (h + 7) // 8, (w + 7) // 8
+        if avg_fmt == abi.FMT_R11G11B10_FLOAT:
+            if not (average.is_cuda and average.dtype == torch.int32 and tuple(average.shape) == (h8, w8) and average.is_contiguous()):
+                raise ValueError(f"{who}: average: expected contiguous cuda int32 {(h8, w8)} (R11G11B10_FLOAT words)")
+        else:
+            _check_img(average, avg_fmt, "average", (h8, w8))
+        for name, (t, fmt) in planes.items():
+            if fmt is None:                                                     # an R16F plane; rows may be strided
+                if not (t.is_cuda and t.dtype == torch.float16 and tuple(t.shape) == (h, w) and t.stride(1) == 1 and t.stride(0) >= w):
+                    raise ValueError(f"{who}: {name}: expected cuda float16 {(h, w)} with unit column stride")
+            else:
+                _check_img(t, fmt, name, (h, w))
+        if out is None:
+            out = empty_image(h, w, out_fmt, self.device)
+        _check_img(out, out_fmt, "out", (h, w))
+        if out_variance is None:
+            out_variance = torch.empty((h, w), dtype=torch.float16, device=self.device)
+        if not (out_variance.is_cuda and out_variance.dtype == torch.float16 and tuple(out_variance.shape) == (h, w) and out_variance.is_contiguous()):
+            raise ValueError(f"{who}: out_variance: expected contiguous cuda float16 {(h, w)}")
+        return out, out_variance
+
+    def ssr_prefilter(self, tile_list, counters, depth, normals, normal_fmt, roughness8, average, avg_fmt, radiance, radiance_fmt, variance, cb,
+                      out=None, out_fmt=FMT_RGBA16F, out_variance=None, stream=None):
+        """vqhip_ssr_prefilter: Prefilter.hlsl for every tile of the denoiser tile list (as ssr_classify returned it with its counters). depth: float32 [H,W]
+        (level 0 of the hierarchy, rows may be strided); normals: int32 [H,W] (R10G10B10A2_UNORM) or float32 [H,W,4]; average: int32 [H8,W8] (R11G11B10_FLOAT) or
+        float32 [H8,W8,4]; variance: float16 [H,W]. Pixels of unlisted tiles keep what `out` / `out_variance` held. Returns (out, out_variance)."""
+        w, h = int(cb.bufferDimensions[0]), int(cb.bufferDimensions[1])
+        if not (depth.is_cuda and depth.dtype == torch.float32 and tuple(depth.shape) == (h, w) and depth.stride(1) == 1 and depth.stride(0) >= w):
+            raise ValueError(f"depth: expected cuda float32 {(h, w)} with unit column stride")
+        if normal_fmt == abi.FMT_R10G10B10A2_UNORM:
+            if not (normals.is_cuda and normals.dtype == torch.int32 and tuple(normals.shape) == (h, w) and normals.is_contiguous()):
+                raise ValueError(f"normals: expected contiguous cuda int32 {(h, w)} (R10G10B10A2_UNORM words)")
+        else:
+            _check_img(normals, normal_fmt, "normals", (h, w))
+        out, out_variance = self._denoise_common("ssr_prefilter", tile_list, counters, roughness8, average, avg_fmt, cb,
+                                                 {"radiance": (radiance, radiance_fmt), "variance": (variance, None)}, out, out_fmt, out_variance)
+        self._ck(self.lib.vqhip_ssr_prefilter(self._h, self._stream(stream), _ptr(tile_list), _ptr(counters), _ptr(depth), depth.stride(0), _ptr(normals), normal_fmt, 0,
+                                              _ptr(roughness8), _ptr(average), avg_fmt, _ptr(radiance), radiance_fmt, 0, _ptr(variance), variance.stride(0),
+                                              C.byref(cb), _ptr(out), out_fmt, 0, _ptr(out_variance), 0))
+        return out, out_variance
+
+    def ssr_resolve_temporal(self, tile_list, counters, roughness8, average, avg_fmt, radiance, radiance_fmt, reprojected, reprojected_fmt, variance, sample_count, cb,
+                             out=None, out_fmt=FMT_RGBA16F, out_variance=None, stream=None):
+        """vqhip_ssr_resolve_temporal: ResolveTemporal.hlsl for every tile of the list. radiance: the prefiltered radiance; reprojected: [H,W,4] image; variance /
+        sample_count: float16 [H,W]. Returns (out, out_variance); pixels of unlisted tiles keep what they held."""
+        out, out_variance = self._denoise_common("ssr_resolve_temporal", tile_list, counters, roughness8, average, avg_fmt, cb,
+                                                 {"radiance": (radiance, radiance_fmt), "reprojected": (reprojected, reprojected_fmt), "variance": (variance, None),
+                                                  "sample_count": (sample_count, None)}, out, out_fmt, out_variance)
+        self._ck(self.lib.vqhip_ssr_resolve_temporal(self._h, self._stream(stream), _ptr(tile_list), _ptr(counters), _ptr(roughness8), _ptr(average), avg_fmt,
+                                                     _ptr(radiance), radiance_fmt, 0, _ptr(reprojected), reprojected_fmt, 0, _ptr(variance), variance.stride(0),
+                                                     _ptr(sample_count), sample_count.stride(0), C.byref(cb), _ptr(out), out_fmt, 0, _ptr(out_variance), 0))
+        return out, out_variance
 
     def visualize(self, src, in_fmt, params, out_fmt=None, out=None, stream=None):
         """Visualization.hlsl:CSMain (debug draw modes). params: abi.VizParams. src in the format of the target the mode shows: a colour image, the int32 [H,W]

@@ -1353,6 +1353,101 @@ int vqhip_ssr_intersect(vqhip_ctx* ctx, void* stream, const uint32_t* rayList, c
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "ssr_intersect launch");
 }
 
+// ---- SSR denoiser passes 2 and 3 (ssr_denoise.hip; docs/DESIGN_DETAILS.md §7.12) -----------------------------------------------------------
+namespace {
+struct DenoisePlane { const void* p; int pitch; size_t bpp; const char* name; };
+// fills what both passes share and validates it; returns VQHIP_OK or the failure already recorded in ctx
+int denoiseCommon(vqhip_ctx* ctx, const char* who, const VQ_SSSRConstants* cb, vqhip_format avgFmt, vqhip_format radianceFmt, vqhip_format outFmt,
+                  const DenoisePlane* in, int nIn, const uint32_t* tileList, const uint32_t* counters, const void* avg, void* outRadiance, int outPitchPx, void* outVariance, int outVariancePitchPx, SsrDenoiseArgs* a) {
+    const std::string w(who);
+    const uint32_t W = cb->bufferDimensions[0], H = cb->bufferDimensions[1];
+    if (W == 0 || H == 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": bad bufferDimensions");
+    if (W > VQHIP_DEPTH_HIERARCHY_MAX_DIM || H > VQHIP_DEPTH_HIERARCHY_MAX_DIM)
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": frames above 4096 in either dimension are not supported");
+    if (!isImageFmt(radianceFmt) || !isImageFmt(outFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": radiance and output radiance must be RGBA32F or RGBA16F");
+    if (avgFmt != VQHIP_FMT_R11G11B10_FLOAT && avgFmt != VQHIP_FMT_RGBA32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": the average radiance must be R11G11B10_FLOAT or RGBA32F");
+    auto pitch = [&](int p) { return p ? p : (int)W; };
+    if (pitch(outPitchPx) < (int)W || pitch(outVariancePitchPx) < (int)W) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": pitch < width");
+    for (int i = 0; i < nIn; ++i) if (pitch(in[i].pitch) < (int)W) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": pitch < width");
+    const int tilesX = ((int)W + 7) / 8, tilesY = ((int)H + 7) / 8;
+    const size_t outBytes = ((size_t)(H - 1) * pitch(outPitchPx) + W) * (outFmt == VQHIP_FMT_RGBA32F ? 16 : 8);
+    const size_t varBytes = ((size_t)(H - 1) * pitch(outVariancePitchPx) + W) * 2;
+    if (rangesOverlap(outRadiance, outBytes, outVariance, varBytes)) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": the outputs overlap each other");
+    auto hitsOutput = [&](const void* p, size_t n) { return rangesOverlap(p, n, outRadiance, outBytes) || rangesOverlap(p, n, outVariance, varBytes); };
+    for (int i = 0; i < nIn; ++i)
+        if (hitsOutput(in[i].p, ((size_t)(H - 1) * pitch(in[i].pitch) + W) * in[i].bpp))
+            return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": an output overlaps the input " + in[i].name + " (the apron reads neighbours that other tiles write)");
+    if (hitsOutput(avg, (size_t)tilesX * tilesY * (avgFmt == VQHIP_FMT_RGBA32F ? 16 : 4)))
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": an output overlaps the input averageRadiance");
+    if (hitsOutput(tileList, (size_t)tilesX * tilesY * 4) || hitsOutput(counters, 8))
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": an output overlaps the tile list or its counters");
+    a->width = (int)W; a->height = (int)H; a->tilesX = tilesX; a->tilesY = tilesY; a->avgW = tilesX; a->avgH = tilesY;
+    a->avg = avg; a->avgF32 = avgFmt == VQHIP_FMT_RGBA32F; a->radF32 = radianceFmt == VQHIP_FMT_RGBA32F; a->outF32 = outFmt == VQHIP_FMT_RGBA32F;
+    a->outRadiance = outRadiance; a->outVariance = outVariance; a->outPitch = pitch(outPitchPx); a->outVariancePitch = pitch(outVariancePitchPx);
+    a->arithDxc = ctx->arithDxc; a->roughnessThreshold = cb->roughnessThreshold; a->temporalStability = cb->temporalStabilityFactor;
+    auto roundUp8 = [](uint32_t v) { return (v & ~7u) == v ? v : v + 8u; };                       // FFX_DNSR_Reflections_RoundUp8 as written
+    a->roundUp8W = (float)roundUp8(W); a->roundUp8H = (float)roundUp8(H);
+    return VQHIP_OK;
+}
+} // namespace
+
+int vqhip_ssr_prefilter(vqhip_ctx* ctx, void* stream, const uint32_t* denoiserTileList, const uint32_t* counters,
+                        const float* depth, int depthPitchPx, const void* normals, vqhip_format normalFmt, int normalPitchPx,
+                        const uint8_t* extractedRoughness, const void* averageRadiance, vqhip_format avgFmt,
+                        const void* radiance, vqhip_format radianceFmt, int radiancePitchPx, const void* variance, int variancePitchPx,
+                        const VQ_SSSRConstants* cb, void* outRadiance, vqhip_format outFmt, int outPitchPx, void* outVariance, int outVariancePitchPx) {
+    vqk::Range range_("FFX DNSR Prefilter");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "ssr_prefilter: ctx is NULL");
+    CTX_GUARD(ctx, "ssr_prefilter");
+    if (!denoiserTileList || !counters || !depth || !normals || !extractedRoughness || !averageRadiance || !radiance || !variance || !cb || !outRadiance || !outVariance)
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_prefilter: NULL argument");
+    if (normalFmt != VQHIP_FMT_R10G10B10A2_UNORM && normalFmt != VQHIP_FMT_RGBA32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_prefilter: normals must be R10G10B10A2_UNORM or RGBA32F");
+    SsrDenoiseArgs a;
+    std::memset(&a, 0, sizeof(a));
+    const DenoisePlane in[] = { { depth, depthPitchPx, 4, "depth" }, { normals, normalPitchPx, normalFmt == VQHIP_FMT_RGBA32F ? (size_t)16 : (size_t)4, "normals" },
+                                { extractedRoughness, 0, 1, "extractedRoughness" }, { radiance, radiancePitchPx, radianceFmt == VQHIP_FMT_RGBA32F ? (size_t)16 : (size_t)8, "radiance" },
+                                { variance, variancePitchPx, 2, "variance" } };
+    int rc = denoiseCommon(ctx, "ssr_prefilter", cb, avgFmt, radianceFmt, outFmt, in, 5, denoiserTileList, counters, averageRadiance, outRadiance, outPitchPx, outVariance, outVariancePitchPx, &a);
+    if (rc) return rc;
+    auto pitch = [&](int p) { return p ? p : a.width; };
+    a.tileList = denoiserTileList; a.counters = counters; a.depth = depth; a.normals = normals; a.roughness = extractedRoughness; a.radiance = radiance; a.variance = variance;
+    a.depthPitch = pitch(depthPitchPx); a.normalPitch = pitch(normalPitchPx); a.radiancePitch = pitch(radiancePitchPx); a.variancePitch = pitch(variancePitchPx);
+    a.normF32 = normalFmt == VQHIP_FMT_RGBA32F;
+    for (int i = 0; i < 4; ++i) { a.ipZ[i] = cb->invProjection.m[i][2]; a.ipW[i] = cb->invProjection.m[i][3]; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipError_t e = launch_ssr_prefilter((hipStream_t)stream, a, ctx->nCUs);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "ssr_prefilter launch");
+}
+
+int vqhip_ssr_resolve_temporal(vqhip_ctx* ctx, void* stream, const uint32_t* denoiserTileList, const uint32_t* counters,
+                               const uint8_t* extractedRoughness, const void* averageRadiance, vqhip_format avgFmt,
+                               const void* radiance, vqhip_format radianceFmt, int radiancePitchPx,
+                               const void* reprojectedRadiance, vqhip_format reprojectedFmt, int reprojectedPitchPx,
+                               const void* variance, int variancePitchPx, const void* sampleCount, int sampleCountPitchPx,
+                               const VQ_SSSRConstants* cb, void* outRadiance, vqhip_format outFmt, int outPitchPx, void* outVariance, int outVariancePitchPx) {
+    vqk::Range range_("FFX DNSR Resolve Temporal");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "ssr_resolve_temporal: ctx is NULL");
+    CTX_GUARD(ctx, "ssr_resolve_temporal");
+    if (!denoiserTileList || !counters || !extractedRoughness || !averageRadiance || !radiance || !reprojectedRadiance || !variance || !sampleCount || !cb || !outRadiance || !outVariance)
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_resolve_temporal: NULL argument");
+    if (!isImageFmt(reprojectedFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_resolve_temporal: the reprojected radiance must be RGBA32F or RGBA16F");
+    SsrDenoiseArgs a;
+    std::memset(&a, 0, sizeof(a));
+    const DenoisePlane in[] = { { extractedRoughness, 0, 1, "extractedRoughness" }, { radiance, radiancePitchPx, radianceFmt == VQHIP_FMT_RGBA32F ? (size_t)16 : (size_t)8, "radiance" },
+                                { reprojectedRadiance, reprojectedPitchPx, reprojectedFmt == VQHIP_FMT_RGBA32F ? (size_t)16 : (size_t)8, "reprojectedRadiance" },
+                                { variance, variancePitchPx, 2, "variance" }, { sampleCount, sampleCountPitchPx, 2, "sampleCount" } };
+    int rc = denoiseCommon(ctx, "ssr_resolve_temporal", cb, avgFmt, radianceFmt, outFmt, in, 5, denoiserTileList, counters, averageRadiance, outRadiance, outPitchPx, outVariance, outVariancePitchPx, &a);
+    if (rc) return rc;
+    auto pitch = [&](int p) { return p ? p : a.width; };
+    a.tileList = denoiserTileList; a.counters = counters; a.roughness = extractedRoughness; a.radiance = radiance; a.reprojected = reprojectedRadiance;
+    a.variance = variance; a.sampleCount = sampleCount;
+    a.radiancePitch = pitch(radiancePitchPx); a.reprojectedPitch = pitch(reprojectedPitchPx); a.variancePitch = pitch(variancePitchPx); a.sampleCountPitch = pitch(sampleCountPitchPx);
+    a.reprojF32 = reprojectedFmt == VQHIP_FMT_RGBA32F;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipError_t e = launch_ssr_resolve_temporal((hipStream_t)stream, a, ctx->nCUs);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "ssr_resolve_temporal launch");
+}
+
 int vqhip_specular_mip_count(int spec_res0) { return vqhip_mip_level_count(spec_res0, spec_res0) - 1; }
 size_t vqhip_cube_bytes(int res0, int nMips, vqhip_format fmt) {
     const size_t bpp = fmt == VQHIP_FMT_RGBA32F ? 16 : 8;

@@ -168,6 +168,23 @@ struct SsrTraceArgs {
 hipError_t launch_ssr_classify(hipStream_t s, const SsrClassifyArgs& a);
 hipError_t launch_ssr_intersect(hipStream_t s, const SsrTraceArgs& a, int nCUs);
 
+// SSR denoiser passes 2 and 3 (vqhip_ssr_prefilter / vqhip_ssr_resolve_temporal, ssr_denoise.hip; docs/DESIGN_DETAILS.md §7.12). One argument block for both:
+// the prefilter leaves reprojected / sampleCount NULL, the temporal resolve depth / normals. Pitches in pixels.
+struct SsrDenoiseArgs {
+    const uint32_t* tileList; const uint32_t* counters;               // counters[1] tiles, read on the device and clamped to tilesX * tilesY
+    const float* depth; const void* normals; const uint8_t* roughness; const void* avg;
+    const void* radiance; const void* reprojected; const void* variance; const void* sampleCount;
+    void* outRadiance; void* outVariance;
+    int width, height, tilesX, tilesY, avgW, avgH;
+    int depthPitch, normalPitch, radiancePitch, reprojectedPitch, variancePitch, sampleCountPitch, outPitch, outVariancePitch;
+    int normF32, avgF32, radF32, reprojF32, outF32, arithDxc;
+    float ipZ[4], ipW[4];                                             // columns 2 and 3 of invProjection: all GetLinearDepth reads
+    float roughnessThreshold, temporalStability;
+    float roundUp8W, roundUp8H;                                       // float2(FFX_DNSR_Reflections_RoundUp8(screen_size)), as written: value + 8 unless a multiple of 8
+};
+hipError_t launch_ssr_prefilter(hipStream_t s, const SsrDenoiseArgs& a, int nCUs);
+hipError_t launch_ssr_resolve_temporal(hipStream_t s, const SsrDenoiseArgs& a, int nCUs);
+
 // 4x MSAA lit draw + resolve (vqhip_forward_lighting_msaa, msaa.hip). Edge pixels (samples with more than one owner) are listed by the
 // shading kernel in edgeList[0 .. *edgeCount) as y * width + x; *edgeCount is zeroed on the call's stream before the launch.
 struct MsaaLayer { const float4* gb0; const float4* gb1; const float4* gb2; const float4* gb3; const uint8_t* cov; int pitch; };

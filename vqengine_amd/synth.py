@@ -641,3 +641,60 @@ def packed_unit_normals(shape, seed=0x9A11):
     n /= np.linalg.norm(n, axis=-1, keepdims=True)
     q = np.clip(np.floor((n * 0.5 + 0.5) * 1023.0 + 0.5), 0, 1023).astype(np.uint32)
     return (q[..., 0] | (q[..., 1] << 10) | (q[..., 2] << 20) | (np.uint32(3) << 30)).astype(np.uint32)
+
+
+def encode_r11g11b10(rgb):
+    """float [..., 3] (>= 0, or +inf) -> DXGI R11G11B10_FLOAT words uint32 [...]: each channel through binary16 (round to nearest even), the mantissa then cut to
+    6 / 6 / 5 bits — one valid encoder; the library only decodes the format"""
+    with np.errstate(over="ignore"):
+        hb = np.maximum(np.asarray(rgb, np.float32), np.float32(0)).astype(np.float16).view(np.uint16).astype(np.uint32)
+    return ((hb[..., 0] >> 4) | ((hb[..., 1] >> 4) << 11) | ((hb[..., 2] >> 5) << 22)).astype(np.uint32)
+
+
+def ssr_denoise_planes(width, height, seed=0xD6E0, radiance=None, history_amplitude=0.6, average_amplitude=0.25, zero_variance_fraction=0.15):
+    """Stand-ins for the planes the denoiser's Reproject pass hands to vqhip_ssr_prefilter / vqhip_ssr_resolve_temporal, seeded. radiance: None = white noise
+    U[0, 4) float32 [H,W,4] (alpha a ray length), or the traced radiance to build the other planes around. Returns a dict:
+      radiance     float32 [H,W,4]
+      variance     float16 [H,W]    U[0, 0.5), `zero_variance_fraction` of the pixels exactly 0 (those are copied by the prefilter)
+      sample_count float16 [H,W]    integers 0 .. 32, a tenth of them 0 and a tenth 1
+      reprojected  float32 [H,W,4]  radiance * (1 + history_amplitude * U[-1, 1)) per channel: part of it inside the clip box, part outside
+      average      float32 [H8,W8,4] the 8 x 8 block mean of the radiance (partial blocks over their pixels) * (1 + average_amplitude * U[-1, 1)), alpha 0
+      average_r11  uint32 [H8,W8]   the same texture encoded R11G11B10_FLOAT (encode_r11g11b10)
+      roughness8   uint8 [H,W]      R8_UNORM roughness: 15 % mirror (< 0.04), 60 % glossy below the 0.2 threshold, 25 % rough"""
+    r = _chunk_rng(seed, 0)
+    h, w = height, width
+    if radiance is None:
+        radiance = r.random((h, w, 4), dtype=np.float32) * np.float32(4.0)
+    rad = np.asarray(radiance).astype(np.float32)
+    variance = (r.random((h, w), dtype=np.float32) * np.float32(0.5)).astype(np.float16)
+    variance[r.random((h, w), dtype=np.float32) < zero_variance_fraction] = 0
+    pick = r.random((h, w), dtype=np.float32)
+    count = np.where(pick < 0.1, 0, np.where(pick < 0.2, 1, r.integers(2, 33, (h, w)))).astype(np.float16)
+    rep = rad.copy()
+    rep[..., :3] *= (1.0 + history_amplitude * (2.0 * r.random((h, w, 3), dtype=np.float32) - 1.0)).astype(np.float32)
+    h8, w8 = (h + 7) // 8, (w + 7) // 8
+    pad = np.zeros((h8 * 8, w8 * 8, 3), np.float64)
+    cnt = np.zeros((h8 * 8, w8 * 8, 1), np.float64)
+    pad[:h, :w], cnt[:h, :w] = np.where(np.isfinite(rad[..., :3]), rad[..., :3], 0.0), 1.0
+    mean = pad.reshape(h8, 8, w8, 8, 3).sum((1, 3)) / cnt.reshape(h8, 8, w8, 8, 1).sum((1, 3))
+    avg = np.zeros((h8, w8, 4), np.float32)
+    avg[..., :3] = (mean * (1.0 + average_amplitude * (2.0 * r.random((h8, w8, 3)) - 1.0))).astype(np.float32)
+    kind = r.random((h, w), dtype=np.float32)
+    rough = np.where(kind < 0.15, r.integers(0, 11, (h, w)), np.where(kind < 0.75, r.integers(11, 51, (h, w)), r.integers(51, 256, (h, w)))).astype(np.uint8)
+    return {"radiance": rad, "variance": variance, "sample_count": count, "reprojected": rep, "average": avg, "average_r11": encode_r11g11b10(avg[..., :3]),
+            "roughness8": rough}
+
+
+def ssr_smooth_surfaces(width, height, seed=0x5A00):
+    """(NDC depth float32 [H,W], normals as R10G10B10A2_UNORM uint32 [H,W], decoded float32 [H,W,4]) of one gently curved surface: normals within a few degrees of
+    one direction, depth a shallow ramp — neighbouring pixels pass the prefilter's pow(dot, 512) and depth weights, so all 15 taps of a pixel carry weight (on
+    ssr_surfaces' white noise nearly every tap's weight vanishes)"""
+    r = _chunk_rng(seed, 0)
+    ys, xs = np.mgrid[0:height, 0:width]
+    n = np.array([0.2, 0.9, -0.4])[None, None, :] + 0.02 * r.normal(size=(height, width, 3)) + 0.03 * np.stack([np.sin(0.3 * xs), np.cos(0.2 * ys), np.sin(0.1 * (xs + ys))], -1)
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    q = np.clip(np.floor((n * 0.5 + 0.5) * 1023.0 + 0.5), 0, 1023).astype(np.uint32)
+    packed = (q[..., 0] | (q[..., 1] << 10) | (q[..., 2] << 20) | (np.uint32(3) << 30)).astype(np.uint32)
+    n01 = np.concatenate([q.astype(np.float32) / np.float32(1023.0), np.ones((height, width, 1), np.float32)], axis=-1)
+    depth = (0.5 + 0.02 * (xs + 2.0 * ys) / (width + 2.0 * height) + 0.002 * r.random((height, width))).astype(np.float32)
+    return depth, packed, n01
