@@ -66,7 +66,7 @@ typedef enum vqhip_format {
     VQHIP_FMT_RG32F       = 4,
     VQHIP_FMT_R10G10B10A2_UNORM = 5,  /* Tex_SceneNormals (RenderResources.cpp:185-197): output of vqhip_scene_normals_from_materials, input of vqhip_ssr_environment_fallback */
     VQHIP_FMT_R11G11B10_FLOAT = 6     /* TexAverageRadiance of the reflection denoiser: one uint32 per texel, R bits 0-10, G 11-21, B 22-31; unsigned, 5-bit exponent (bias 15),
-                                       * 6 / 6 / 5 mantissa bits, denormals / inf / NaN as DXGI; decoded exactly. Read only: vqhip_ssr_prefilter, vqhip_ssr_resolve_temporal */
+                                       * 6 / 6 / 5 mantissa bits, denormals / inf / NaN as DXGI; decoded exactly. Read by vqhip_ssr_prefilter, vqhip_ssr_resolve_temporal; written by vqhip_ssr_reproject */
 } vqhip_format;
 
 /* ------------------------------------------------------------------------------------------------
@@ -345,7 +345,7 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * later in round 4, additions only: vqhip_forward_lighting_mrt, vqhip_forward_lighting_from_materials_mrt, vqhip_scene_normals_from_materials,
                                * vqhip_composite_reflections; vqhip_visualize reads R10G10B10A2 / RG16F / RG32F inputs.
                                * Later additions to 3: vqhip_gbuffer_msaa, vqhip_forward_lighting_msaa; vqhip_msaa_surfaces, vqhip_msaa_resolve_surfaces, vqhip_depth_hierarchy (+ _bytes, _level_offset_bytes);
-                               * vqhip_ssr_classify, vqhip_ssr_intersect; vqhip_ssr_prefilter, vqhip_ssr_resolve_temporal, VQHIP_FMT_R11G11B10_FLOAT */
+                               * vqhip_ssr_classify, vqhip_ssr_intersect; vqhip_ssr_prefilter, vqhip_ssr_resolve_temporal, VQHIP_FMT_R11G11B10_FLOAT; vqhip_ssr_reproject, vqhip_ssr_reproject_surfaces */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -739,8 +739,8 @@ VQHIP_API int vqhip_fsr_rcas(vqhip_ctx* ctx, void* stream, const void* in, void*
  * outFmt RGBA8_UNORM | RGBA16F | RGBA32F. */
 /* Replaces ApplyReflectionsPass::RecordCommands (ApplyReflections.cpp:45-80) == ApplyReflections.hlsl:CSMain :30-50 without
  * COMPOSITE_BOUNDING_VOLUMES: sceneColor.rgb += reflectionRadiance.rgb, alpha (roughness) kept; in place on the scene colour.
- * (The reflection radiance comes from vqhip_ssr_environment_fallback + vqhip_ssr_classify + vqhip_ssr_intersect below, denoised by vqhip_ssr_prefilter +
- * vqhip_ssr_resolve_temporal; of the FidelityFX reflection DENOISER only Reproject and PrepareBlueNoiseTexture are out of scope.) fmt: RGBA16F | RGBA32F for both. */
+ * (The reflection radiance comes from vqhip_ssr_environment_fallback + vqhip_ssr_classify + vqhip_ssr_intersect below, denoised by vqhip_ssr_reproject +
+ * vqhip_ssr_prefilter + vqhip_ssr_resolve_temporal; of the FidelityFX reflection DENOISER only PrepareBlueNoiseTexture is out of scope.) fmt: RGBA16F | RGBA32F for both. */
 VQHIP_API int vqhip_apply_reflections(vqhip_ctx* ctx, void* stream, const void* reflectionRadiance, void* sceneColor,
         int width, int height, vqhip_format fmt);
 /* Replaces VQRenderer::CompositeReflections (SceneRendering.cpp:2362-2403): ApplyReflectionsPass in the permutation its parameters select
@@ -776,7 +776,7 @@ VQHIP_STATIC_ASSERT(offsetof(VQ_SSSRConstants, bufferDimensions) == 448 && offse
  * g_environment_map.SampleLevel(envMapRotation * R_world, roughness * (mipCount - 1)) — a FRACTIONAL level: trilinear between cube mips, seamless
  * (csrc/vq_sampling.h:sample_cube_lod_rgba16f) — times EnvironmentBRDF(NdotV, roughness, metallic 1, ...) from the LUT (BRDF.hlsl:196-207).
  * The ray classification / ray list / denoiser tile list of the same dispatch is vqhip_ssr_classify, the traced rays are vqhip_ssr_intersect (below); the denoiser's
- * Prefilter and ResolveTemporal are vqhip_ssr_prefilter / vqhip_ssr_resolve_temporal; what stays out of scope is the denoiser's Reproject pass and
+ * Reproject, Prefilter and ResolveTemporal are vqhip_ssr_reproject / vqhip_ssr_prefilter / vqhip_ssr_resolve_temporal; what stays out of scope is
  * PrepareBlueNoiseTexture with its Sobol tables.
  *   sceneColorRoughness : g_roughness   == the scene colour whose alpha is the roughness (ForwardLighting.hlsl:380), RGBA16F | RGBA32F
  *   depth               : g_depth_buffer == mip 0 of the depth hierarchy, R32F, NDC z (far plane 1)
@@ -846,8 +846,8 @@ VQHIP_API int vqhip_ssr_intersect(vqhip_ctx* ctx, void* stream,
  * ffx_denoiser_reflections_resolve_temporal.h (9 x 9 local moments, history clip, blend) for every 8 x 8 tile of the denoiser tile list. The float32 contract —
  * expression order, the binary16 round trip of the values the reference packs into group-shared memory, exp(x) = exp2(x * 1.44269502f), loads outside the frame
  * reading 0, FFX_DNSR_Reflections_RoundUp8 as written, the bilinear CLAMP fetch of the 1/8-resolution average radiance — is docs/DESIGN_DETAILS.md §7.12;
- * tests/ssr_denoise_ref.py states it in numpy. Reproject (pass 1), which produces averageRadiance, variance, sampleCount and reprojectedRadiance, is not part of
- * the library yet: the caller provides those planes.
+ * tests/ssr_denoise_ref.py states it in numpy. Reproject (pass 1), which produces averageRadiance, variance, sampleCount and reprojectedRadiance, is
+ * vqhip_ssr_reproject (below).
  *   denoiserTileList, counters : as vqhip_ssr_classify wrote them; counters[1] tiles, read on the device (no host synchronisation) and clamped to
  *                                ceil(w/8) * ceil(h/8), the number of entries the list must hold. An entry is (y << 16) | x; its tile is DEFINED by this contract as (x >> 3, y >> 3) — for the 8-aligned entries
  *                                vqhip_ssr_classify writes that is what CSMain computes; the shader itself gives an unaligned entry no single tile; an entry
@@ -884,6 +884,58 @@ VQHIP_API int vqhip_ssr_resolve_temporal(vqhip_ctx* ctx, void* stream,
         const void* variance, int variancePitchPx, const void* sampleCount, int sampleCountPitchPx,
         const VQ_SSSRConstants* cb,
         void* outRadiance, vqhip_format outFmt, int outPitchPx, void* outVariance, int outVariancePitchPx);
+
+/* Replaces the "FFX DNSR Reproject" dispatch (ScreenSpaceReflections.cpp, the first of the denoiser's three between the march and the composite) ==
+ * Reproject.hlsl:CSMain + ffx_denoiser_reflections_reproject.h for every 8 x 8 tile of the denoiser tile list: the 9 x 9 local moments of the traced radiance, the
+ * choice between hit-point and surface (motion-vector) reprojection, the 3 x 3 search and the 2 x 2 path where the history is disoccluded, the temporal variance and
+ * sample count, and the 1/8-resolution average radiance. It writes the four planes vqhip_ssr_prefilter / vqhip_ssr_resolve_temporal consume. The float32 contract is
+ * docs/DESIGN_DETAILS.md §7.13 (tile-list semantics, loads outside the frame, exp, the two arithmetic readings as §7.11 / §7.12; bilinear history fetches: texels
+ * decoded to binary32, CLAMP, 8-bit fractions; the centre radiance is not rounded through binary16; a discarded history stores (0,0,0) / 1 / 1);
+ * tests/ssr_reproject_ref.py states it in numpy. g_blue_noise_texture and g_average_radiance_history are bound by the engine but never read by the shader: they are
+ * not arguments. Clearing the history (the engine's bClearHistoryBuffers) is a plain clear of the history planes by the caller.
+ *   tile_list, counters          : as vqhip_ssr_classify wrote them (semantics as vqhip_ssr_prefilter)
+ *   depth, depth_history         : R32F (level 0 of the depth hierarchy of this frame / of the previous one)
+ *   normals, normal_history      : R10G10B10A2_UNORM | RGBA32F, each with its own format
+ *   roughness, roughness_history : R8_UNORM (vqhip_ssr_environment_fallback's extracted roughness)
+ *   radiance                     : RGBA16F | RGBA32F, the traced radiance; alpha = ray length
+ *   radiance_history             : RGBA16F | RGBA32F, last frame's vqhip_ssr_resolve_temporal output
+ *   motion_vectors               : RG16F | RG32F as vqhip_forward_lighting_mrt writes them
+ *   variance_history, sample_count_history : R16F (last frame's resolved variance / this pass's sample count of last frame)
+ *   out_reprojected              : RGBA16F | RGBA32F; alpha is written as 0 (the shader stores a float3)
+ *   out_average                  : [ceil(h/8)][ceil(w/8)], tightly packed, R11G11B10_FLOAT | RGBA32F (alpha 0); written for listed tiles only. R11G11B10: one rounding to
+ *                                  nearest even from binary32, overflow to inf, negative and -0 to 0, NaN to exponent 31 with a non-zero mantissa, denormals kept
+ *   out_variance, out_sample_count : R16F. A pixel with roughness >= roughnessThreshold stores nothing to the three full-resolution outputs.
+ *   cb                           : host pointer; bufferDimensions (each <= 4096, else VQHIP_ERR_UNSUPPORTED), invProjection, invView, prevViewProjection,
+ *                                  roughnessThreshold are read (temporalStabilityFactor is passed to the shader function and never used there)
+ * An output overlapping an input or another output: VQHIP_ERR_INVALID_ARG (the engine ping-pongs). Pitches in pixels, 0 = width. PARITY UNPINNED (docs/WARP_CALIBRATION.md §7). */
+typedef struct vqhip_ssr_reproject_surfaces {
+    const uint32_t* tile_list;
+    const uint32_t* counters;
+    const float*    depth;
+    const void*     normals;
+    const uint8_t*  roughness;
+    const float*    depth_history;
+    const void*     normal_history;
+    const uint8_t*  roughness_history;
+    const void*     radiance;
+    const void*     radiance_history;
+    const void*     motion_vectors;
+    const void*     variance_history;
+    const void*     sample_count_history;
+    void*           out_reprojected;
+    void*           out_average;
+    void*           out_variance;
+    void*           out_sample_count;
+    int32_t         depth_pitch_px, normals_pitch_px, roughness_pitch_px, depth_history_pitch_px, normal_history_pitch_px, roughness_history_pitch_px;
+    int32_t         radiance_pitch_px, radiance_history_pitch_px, motion_pitch_px, variance_history_pitch_px, sample_count_history_pitch_px;
+    int32_t         out_reprojected_pitch_px, out_variance_pitch_px, out_sample_count_pitch_px;
+    int32_t         normals_fmt, normal_history_fmt, radiance_fmt, radiance_history_fmt, motion_fmt, out_reprojected_fmt, out_average_fmt;   /* vqhip_format */
+    int32_t         pad_;
+} vqhip_ssr_reproject_surfaces;
+VQHIP_STATIC_ASSERT(sizeof(vqhip_ssr_reproject_surfaces) == 224 && offsetof(vqhip_ssr_reproject_surfaces, radiance) == 64 &&
+                    offsetof(vqhip_ssr_reproject_surfaces, out_reprojected) == 104 && offsetof(vqhip_ssr_reproject_surfaces, depth_pitch_px) == 136 &&
+                    offsetof(vqhip_ssr_reproject_surfaces, normals_fmt) == 192, "vqhip_ssr_reproject_surfaces layout");
+VQHIP_API int vqhip_ssr_reproject(vqhip_ctx* ctx, void* stream, const vqhip_ssr_reproject_surfaces* io, const VQ_SSSRConstants* cb);
 
 typedef struct VQ_VizParams { int32_t iDrawMode; int32_t iUnpackNormals; float fInputStrength; } VQ_VizParams;
 VQHIP_API int vqhip_visualize(vqhip_ctx* ctx, void* stream, const void* in, void* out, int width, int height,

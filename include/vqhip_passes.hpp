@@ -364,7 +364,7 @@ private:
 // SSR rays == the ray list of the "FFX DNSR ClassifyTiles" dispatch + the "FFX SSSR Intersection" dispatch of
 // ScreenSpaceReflectionsPass::RecordCommands (ScreenSpaceReflections.cpp:262-320): vqhip_ssr_classify + vqhip_ssr_intersect. Owns TexRayList,
 // TexRayCounter and TexDenoiserTileList (ScreenSpaceReflections.cpp:118-127, as plain device buffers); traces IN PLACE into the TexRadiance that
-// HipSSREnvironmentFallbackPass owns and has filled on the same stream. Without the denoiser passes behind it (HipSSRPrefilterPass / HipSSRResolveTemporalPass below; Reproject is the caller's), run it with ffxCBuffer.samplesPerQuad = 4: every
+// HipSSREnvironmentFallbackPass owns and has filled on the same stream. Without the denoiser passes behind it (HipSSRReprojectPass / HipSSRPrefilterPass / HipSSRResolveTemporalPass below), run it with ffxCBuffer.samplesPerQuad = 4: every
 // glossy pixel then traces its own ray and the radiance is directly what vqhip_composite_reflections consumes.
 // ---------------------------------------------------------------------------------------------------------------
 class HipSSRIntersectPass : public RenderPassBase {
@@ -409,6 +409,58 @@ public:
 private:
     void* mRayList = nullptr; void* mRayCounter = nullptr; void* mDenoiserTileList = nullptr;
     unsigned mWidth = 0, mHeight = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// Reflection denoiser, pass 1 == the "FFX DNSR Reproject" dispatch of ScreenSpaceReflectionsPass::RecordCommands: vqhip_ssr_reproject. Buffer roles as
+// ScreenSpaceReflections.cpp:1177-1198 binds them for frame index i: reads the surfaces of this frame and their history copies, TexRadiance[i] (what the march
+// wrote), TexRadiance[1 - i] (last frame's resolved radiance), the motion vectors, TexVariance[1 - i] and TexSampleCount[1 - i]; writes TexReprojectedRadiance,
+// TexAvgRadiance[i], TexVariance[i], TexSampleCount[i]. TexAvgRadiance[1 - i] and the blue noise are bound by the engine and never read by the shader: not
+// parameters. The pass owns nothing, the caller ping-pongs; the engine's bClearHistoryBuffers is a plain clear of the history planes by the caller.
+// ---------------------------------------------------------------------------------------------------------------
+class HipSSRReprojectPass : public RenderPassBase {
+public:
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        VQ_SSSRConstants ffxCBuffer = {};
+        const uint32_t* TexDenoiserTileList = nullptr;           // HipSSRIntersectPass::GetDenoiserTileList()
+        const uint32_t* TexRayCounter = nullptr;                 // HipSSRIntersectPass::GetRayCounter(): [1] = tiles
+        const float* TexDepthHierarchy = nullptr;                // mip 0, R32F
+        const uint8_t* TexExtractedRoughness = nullptr;          // R8_UNORM
+        const void* TexNormals = nullptr;                        // R10G10B10A2_UNORM
+        const float* TexDepthHistory = nullptr;                  // R32F
+        const uint8_t* TexRoughnessHistory = nullptr;            // R8_UNORM
+        const void* TexNormalsHistory = nullptr;                 // R10G10B10A2_UNORM
+        const void* TexRadianceIn = nullptr;                     // TexRadiance[i], RGBA16F (alpha = ray length)
+        const void* TexRadianceHistory = nullptr;                // TexRadiance[1 - i], RGBA16F
+        const void* TexMotionVectors = nullptr;                  // Tex_SceneMotionVectors, RG16F
+        const void* TexVarianceHistory = nullptr;                // TexVariance[1 - i], R16F
+        const void* TexSampleCountHistory = nullptr;             // TexSampleCount[1 - i], R16F
+        void* TexReprojectedRadiance = nullptr;                  // RGBA16F
+        void* TexAvgRadianceOut = nullptr;                       // TexAvgRadiance[i], R11G11B10_FLOAT, ceil(w/8) x ceil(h/8)
+        void* TexVarianceOut = nullptr;                          // TexVariance[i], R16F
+        void* TexSampleCountOut = nullptr;                       // TexSampleCount[i], R16F
+    };
+    explicit HipSSRReprojectPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override {}
+    void OnCreateWindowSizeDependentResources(unsigned, unsigned, const IRenderPassResourceCollection* = nullptr) override {}
+    void OnDestroyWindowSizeDependentResources() override {}
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        vqhip_ssr_reproject_surfaces s = {};
+        s.tile_list = p->TexDenoiserTileList; s.counters = p->TexRayCounter;
+        s.depth = p->TexDepthHierarchy; s.normals = p->TexNormals; s.roughness = p->TexExtractedRoughness;
+        s.depth_history = p->TexDepthHistory; s.normal_history = p->TexNormalsHistory; s.roughness_history = p->TexRoughnessHistory;
+        s.radiance = p->TexRadianceIn; s.radiance_history = p->TexRadianceHistory; s.motion_vectors = p->TexMotionVectors;
+        s.variance_history = p->TexVarianceHistory; s.sample_count_history = p->TexSampleCountHistory;
+        s.out_reprojected = p->TexReprojectedRadiance; s.out_average = p->TexAvgRadianceOut; s.out_variance = p->TexVarianceOut; s.out_sample_count = p->TexSampleCountOut;
+        s.normals_fmt = s.normal_history_fmt = VQHIP_FMT_R10G10B10A2_UNORM;
+        s.radiance_fmt = s.radiance_history_fmt = s.out_reprojected_fmt = VQHIP_FMT_RGBA16F;
+        s.motion_fmt = VQHIP_FMT_RG16F; s.out_average_fmt = VQHIP_FMT_R11G11B10_FLOAT;
+        mStatus = vqhip_ssr_reproject(mCtx, p->Stream, &s, &p->ffxCBuffer);
+    }
 };
 
 // ---------------------------------------------------------------------------------------------------------------

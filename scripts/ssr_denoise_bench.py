@@ -1,14 +1,18 @@
-"""vqhip_ssr_prefilter and vqhip_ssr_resolve_temporal (docs/DESIGN_DETAILS.md §7.12) on synth.ssr_room at 3840 x 2160 (default; --size W H for others): one JSON
-line. Needs the GPU. In one process, alternating per step: a device-to-device copy of a buffer of the passes' traffic (the bandwidth yardstick), the prefilter,
-the temporal resolve; device events around each call, warm-up, the median over the steps. The tile list is the one vqhip_ssr_classify writes for the room; the
-planes Reproject would write are synth.ssr_denoise_planes around the room's lit scene (the kernels' time does not depend on where the radiance came from, only
-on which branches the pixels take — the branch shares are reported from the inputs).
+"""The reflection denoiser as its three passes — vqhip_ssr_reproject (docs/DESIGN_DETAILS.md §7.13), vqhip_ssr_prefilter and vqhip_ssr_resolve_temporal (§7.12) — on
+synth.ssr_room at 3840 x 2160 (default; --size W H for others): one JSON line. Needs the GPU. In one process, alternating per step: a device-to-device copy of a
+buffer of the passes' traffic (the bandwidth yardstick), reproject, the prefilter, the temporal resolve; device events around each call, warm-up, the median over
+the steps. The tile list is the one vqhip_ssr_classify writes for the room. Reproject runs on the room seen from a camera that moved since the previous frame
+(history depth / normals / roughness: the room from the previous camera; motion vectors: synth.ssr_motion_vectors; history radiance, variance and sample count:
+synth.ssr_denoise_planes around the lit scene) and writes the four planes the other two passes then consume — its real outputs, not stand-ins.
 Bytes moved by construction, per listed tile: the 16 x 16 apron of every plane a pass reads with a neighbourhood, 8 x 8 of every plane it reads at the pixel and of
-both outputs (the 1/8-resolution average radiance is 4 texels per tile at most and is left out).
-  --variant-lib PATH  A/B: a second build of the library (for instance one whose csrc/ssr_denoise.hip keeps the apron in another LDS form) is loaded into the same
-                      process and its two passes are timed alternating with the committed library's, step by step; its outputs are compared bit for bit.
-  --mode resources    (CPU only) registers, scratch, LDS and occupancy of the two kernels from the compiler's own report: csrc/ssr_denoise.hip compiled with the
-                      flags `make -n` prints for ssr_denoise.o plus -Rpass-analysis=kernel-resource-usage; --source FILE reports another source the same way."""
+both outputs (the 1/8-resolution average radiance is 4 texels per tile at most and is left out). Reproject's history gathers are counted as one read of each
+history texel of the tile (the footprints of neighbouring pixels overlap; what the caches do not absorb comes on top).
+  --variant-lib PATH  A/B: a second build of the library (for instance one whose csrc/ssr_denoise.hip keeps the apron in another LDS form, or whose csrc/ssr_reproject.hip has another
+                      register budget) is loaded into the same
+                      process and its three passes are timed alternating with the committed library's, step by step; its outputs are compared bit for bit.
+  --mode resources    (CPU only) registers, scratch, LDS and occupancy of the kernels of one source from the compiler's own report: csrc/ssr_denoise.hip (the prefilter and the
+                      temporal resolve) compiled with the flags `make -n` prints for ssr_denoise.o plus -Rpass-analysis=kernel-resource-usage; --source FILE reports another
+                      source the same way (csrc/ssr_reproject.hip, built with the same flags, for the third kernel)."""
 import argparse
 import json
 import os
@@ -26,6 +30,8 @@ F16, N10, R11 = abi.FMT_RGBA16F, abi.FMT_R10G10B10A2_UNORM, abi.FMT_R11G11B10_FL
 # bytes per listed tile: apron texels x bytes + pixel texels x bytes
 PREFILTER_BYTES = 256 * (8 + 2 + 4 + 4) + 64 * (1 + 8 + 2)           # apron: radiance RGBA16F, variance R16F, normals, depth; pixel: roughness, out radiance, out variance
 RESOLVE_BYTES = 256 * 8 + 64 * (1 + 2 + 2 + 8 + 8 + 2)               # apron: radiance; pixel: roughness, variance, sample count, reprojected, out radiance, out variance
+# apron: radiance; pixel: roughness, normals, depth, motion; history, once per texel: depth, normals, roughness, radiance, variance, sample count; out: reprojected, variance, sample count
+REPROJECT_BYTES = 256 * 8 + 64 * (1 + 4 + 4 + 4) + 64 * (4 + 4 + 1 + 8 + 2 + 2) + 64 * (8 + 2 + 2)
 
 
 def unorm8(x):
@@ -91,6 +97,8 @@ def main():
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()   # noqa: E731
     rm = synth.ssr_room(w, h, 1)
     cb = rm["cb"]
+    rm_prev = synth.ssr_room(w, h, 1, camera=(3.2, 10.0, -59.8))                                  # the previous frame's camera
+    synth._set_matrix(cb.prevViewProjection, synth._matrix_of(rm_prev["cb"].view) @ synth._matrix_of(rm_prev["cb"].projection))
     pl = synth.ssr_denoise_planes(w, h, seed=0xBE10, radiance=rm["scene"])
     scene = dev(rm["scene"].astype(np.float16))
     depth, normals = dev(rm["depth"]), dev(rm["packed"].view(np.int32))
@@ -98,18 +106,27 @@ def main():
     _, counters, tiles = ctx.ssr_classify(scene, F16, depth, cb)
     avg, rad, rep = dev(pl["average_r11"].view(np.int32)), dev(pl["radiance"].astype(np.float16)), dev(pl["reprojected"].astype(np.float16))
     var, cnt = dev(pl["variance"]), dev(pl["sample_count"])
+    M16 = abi.FMT_RG16F
+    h_depth, h_normals, h_r8 = dev(rm_prev["depth"]), dev(rm_prev["packed"].view(np.int32)), dev(unorm8(rm_prev["scene"][..., 3]))
+    motion = dev(synth.ssr_motion_vectors(rm["depth"], cb).astype(np.float16))
+    j_rep, j_avg, j_var, j_cnt = torch.zeros_like(rad), torch.zeros_like(avg), torch.zeros_like(var), torch.zeros_like(cnt)    # Reproject's outputs
+    reproject = lambda c, o: c.ssr_reproject(tiles, counters, depth, normals, N10, r8, h_depth, h_normals, N10, h_r8, rad, F16, rep, F16, motion, M16, var, cnt, cb,   # noqa: E731
+                                             out_reprojected=o[0], out_average=o[1], out_variance=o[2], out_sample_count=o[3])
     p_r, p_v = torch.zeros_like(rad), torch.zeros_like(var)
     t_r, t_v = torch.zeros_like(rad), torch.zeros_like(var)
     n_tiles = int(counters.cpu().numpy().view(np.uint32)[1])
-    copy_bytes = max(PREFILTER_BYTES, RESOLVE_BYTES) * n_tiles // 2          # a copy reads and writes every byte: half the traffic each way
+    copy_bytes = max(PREFILTER_BYTES, RESOLVE_BYTES, REPROJECT_BYTES) * n_tiles // 2          # a copy reads and writes every byte: half the traffic each way
     src, dst = torch.empty(copy_bytes, dtype=torch.uint8, device="cuda"), torch.empty(copy_bytes, dtype=torch.uint8, device="cuda")
     calls = {"copy": lambda: dst.copy_(src),
-             "prefilter": lambda: ctx.ssr_prefilter(tiles, counters, depth, normals, N10, r8, avg, R11, rad, F16, var, cb, out=p_r, out_variance=p_v),
-             "resolve_temporal": lambda: ctx.ssr_resolve_temporal(tiles, counters, r8, avg, R11, p_r, F16, rep, F16, p_v, cnt, cb, out=t_r, out_variance=t_v)}
+             "reproject": lambda: reproject(ctx, (j_rep, j_avg, j_var, j_cnt)),
+             "prefilter": lambda: ctx.ssr_prefilter(tiles, counters, depth, normals, N10, r8, j_avg, R11, rad, F16, j_var, cb, out=p_r, out_variance=p_v),
+             "resolve_temporal": lambda: ctx.ssr_resolve_temporal(tiles, counters, r8, j_avg, R11, p_r, F16, j_rep, F16, p_v, j_cnt, cb, out=t_r, out_variance=t_v)}
     if ctx2 is not None:
         v_r, v_v, u_r, u_v = torch.zeros_like(rad), torch.zeros_like(var), torch.zeros_like(rad), torch.zeros_like(var)
-        calls["variant_prefilter"] = lambda: ctx2.ssr_prefilter(tiles, counters, depth, normals, N10, r8, avg, R11, rad, F16, var, cb, out=v_r, out_variance=v_v)
-        calls["variant_resolve_temporal"] = lambda: ctx2.ssr_resolve_temporal(tiles, counters, r8, avg, R11, p_r, F16, rep, F16, p_v, cnt, cb, out=u_r, out_variance=u_v)
+        k_out = (torch.zeros_like(rad), torch.zeros_like(avg), torch.zeros_like(var), torch.zeros_like(cnt))
+        calls["variant_reproject"] = lambda: reproject(ctx2, k_out)
+        calls["variant_prefilter"] = lambda: ctx2.ssr_prefilter(tiles, counters, depth, normals, N10, r8, j_avg, R11, rad, F16, j_var, cb, out=v_r, out_variance=v_v)
+        calls["variant_resolve_temporal"] = lambda: ctx2.ssr_resolve_temporal(tiles, counters, r8, j_avg, R11, p_r, F16, j_rep, F16, p_v, j_cnt, cb, out=u_r, out_variance=u_v)
     times = {k: [] for k in calls}
     for step in range(a.warmup + a.steps):
         for k, fn in calls.items():
@@ -123,18 +140,23 @@ def main():
     rough = unorm8(rm["scene"][..., 3]).astype(np.float32) / np.float32(255.0)
     glossy = rough < np.float32(cb.roughnessThreshold)
     out = {"bench": "ssr_denoise", "width": w, "height": h, "steps": a.steps, "tiles": n_tiles, "tile_grid": ((w + 7) // 8) * ((h + 7) // 8),
-           "share_denoised_by_prefilter": round(float((glossy & ~(rough < np.float32(0.04)) & (pl["variance"] > 0)).mean()), 4), "share_glossy": round(float(glossy.mean()), 4),
+           "share_denoised_by_prefilter": round(float((glossy & ~(rough < np.float32(0.04)) & (j_var.cpu().numpy() > 0)).mean()), 4), "share_glossy": round(float(glossy.mean()), 4),
+           "share_history_kept_by_reproject": round(float((j_cnt.cpu().numpy() > 1).mean()), 4),
+           "reproject_us": round(us["reproject"], 1), "reproject_bytes": REPROJECT_BYTES * n_tiles,
+           "reproject_fraction_of_copy_bandwidth": round(REPROJECT_BYTES * n_tiles / us["reproject"] / 1e3 / copy_gbs, 4), "denoiser_us": round(us["reproject"] + us["prefilter"] + us["resolve_temporal"], 1),
            "prefilter_us": round(us["prefilter"], 1), "resolve_temporal_us": round(us["resolve_temporal"], 1), "copy_us": round(us["copy"], 1),
            "prefilter_bytes": PREFILTER_BYTES * n_tiles, "resolve_temporal_bytes": RESOLVE_BYTES * n_tiles, "copy_GBps": round(copy_gbs, 1),
            "prefilter_fraction_of_copy_bandwidth": round(PREFILTER_BYTES * n_tiles / us["prefilter"] / 1e3 / copy_gbs, 4),
            "resolve_temporal_fraction_of_copy_bandwidth": round(RESOLVE_BYTES * n_tiles / us["resolve_temporal"] / 1e3 / copy_gbs, 4)}
     spread = lambda k: [round(float(min(times[k])), 1), round(float(max(times[k])), 1)]   # noqa: E731
-    out["prefilter_us_min_max"], out["resolve_temporal_us_min_max"] = spread("prefilter"), spread("resolve_temporal")
+    out["reproject_us_min_max"], out["prefilter_us_min_max"], out["resolve_temporal_us_min_max"] = spread("reproject"), spread("prefilter"), spread("resolve_temporal")
     if ctx2 is not None:
         same = lambda x, y: bool(torch.equal(x.view(torch.int16), y.view(torch.int16)))   # noqa: E731
-        out.update(variant_lib=os.path.basename(a.variant_lib), variant_prefilter_us=round(us["variant_prefilter"], 1), variant_resolve_temporal_us=round(us["variant_resolve_temporal"], 1),
+        out.update(variant_lib=os.path.basename(a.variant_lib), variant_reproject_us=round(us["variant_reproject"], 1), variant_reproject_us_min_max=spread("variant_reproject"),
+                   variant_prefilter_us=round(us["variant_prefilter"], 1), variant_resolve_temporal_us=round(us["variant_resolve_temporal"], 1),
                    variant_prefilter_us_min_max=spread("variant_prefilter"), variant_resolve_temporal_us_min_max=spread("variant_resolve_temporal"),
-                   variant_bits_equal=same(p_r, v_r) and same(p_v, v_v) and same(t_r, u_r) and same(t_v, u_v))
+                   variant_bits_equal=same(p_r, v_r) and same(p_v, v_v) and same(t_r, u_r) and same(t_v, u_v) and same(j_rep, k_out[0]) and bool(torch.equal(j_avg, k_out[1]))
+                   and same(j_var, k_out[2]) and same(j_cnt, k_out[3]))
         ctx2.close()
     ctx.close()
     print(json.dumps(out))

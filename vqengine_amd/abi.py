@@ -12,7 +12,7 @@ VQHIP_ERR_RCCL = -5
 
 FMT_RGBA32F, FMT_RGBA16F, FMT_RGBA8_UNORM, FMT_RG16F, FMT_RG32F = 0, 1, 2, 3, 4
 FMT_R10G10B10A2_UNORM = 5          # Tex_SceneNormals: input of ssr_environment_fallback only
-FMT_R11G11B10_FLOAT = 6            # TexAverageRadiance: input of ssr_prefilter / ssr_resolve_temporal only (one uint32 per texel)
+FMT_R11G11B10_FLOAT = 6            # TexAverageRadiance: written by ssr_reproject, read by ssr_prefilter / ssr_resolve_temporal (one uint32 per texel)
 FMT_BPP = {FMT_RGBA32F: 16, FMT_RGBA16F: 8, FMT_RGBA8_UNORM: 4, FMT_RG16F: 4, FMT_RG32F: 8}
 CONV_SEQUENTIAL, CONV_WAVE64 = 0, 1
 ARITH_LITERAL, ARITH_DXC = 0, 1
@@ -139,6 +139,19 @@ class MSAASurfaces(C.Structure):   # vqhip_msaa_surfaces: the 4-sample depth + p
                 ("width", C.c_int32), ("height", C.c_int32), ("layers", C.c_int32), ("coverage_pitch", C.c_int32),
                 ("depth_pitch_px", C.c_int32), ("background_pitch_px", C.c_int32), ("normals_fmt", C.c_int32), ("pad_", C.c_int32)]
 
+
+class SSRReprojectSurfaces(C.Structure):   # vqhip_ssr_reproject_surfaces: every plane, pitch and format of vqhip_ssr_reproject
+    _fields_ = ([(n, C.c_void_p) for n in ("tile_list", "counters", "depth", "normals", "roughness", "depth_history", "normal_history", "roughness_history", "radiance",
+                                            "radiance_history", "motion_vectors", "variance_history", "sample_count_history", "out_reprojected", "out_average",
+                                            "out_variance", "out_sample_count")]
+                + [(n, C.c_int32) for n in ("depth_pitch_px", "normals_pitch_px", "roughness_pitch_px", "depth_history_pitch_px", "normal_history_pitch_px",
+                                            "roughness_history_pitch_px", "radiance_pitch_px", "radiance_history_pitch_px", "motion_pitch_px", "variance_history_pitch_px",
+                                            "sample_count_history_pitch_px", "out_reprojected_pitch_px", "out_variance_pitch_px", "out_sample_count_pitch_px",
+                                            "normals_fmt", "normal_history_fmt", "radiance_fmt", "radiance_history_fmt", "motion_fmt", "out_reprojected_fmt", "out_average_fmt",
+                                            "pad_")])
+
+
+assert C.sizeof(SSRReprojectSurfaces) == 224
 
 DEPTH_HIERARCHY_TRUE_TOP = 1     # VQHIP_DEPTH_HIERARCHY_TRUE_TOP
 DEPTH_HIERARCHY_MAX_DIM = 4096   # VQHIP_DEPTH_HIERARCHY_MAX_DIM

@@ -103,6 +103,7 @@ def load_library():
                                       vp, i32, i32, vp, i32]),
         "vqhip_ssr_resolve_temporal": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, i32, vp, i32, C.POINTER(abi.SSSRConstants),
                                              vp, i32, i32, vp, i32]),
+        "vqhip_ssr_reproject": (i32, [vp, vp, C.POINTER(abi.SSRReprojectSurfaces), C.POINTER(abi.SSSRConstants)]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -134,7 +135,7 @@ EXPORTED_SYMBOLS = [
     "vqhip_rowtile", "vqhip_comm_unique_id", "vqhip_comm_create", "vqhip_comm_adopt", "vqhip_comm_destroy", "vqhip_comm_query", "vqhip_comm_abort", "vqhip_comm_loopback", "vqhip_exchange_blur_halos",
     "vqhip_composite_tiles", "vqhip_forward_lighting_msaa",
     "vqhip_msaa_resolve_surfaces", "vqhip_depth_hierarchy", "vqhip_depth_hierarchy_bytes", "vqhip_depth_hierarchy_level_offset_bytes",
-    "vqhip_ssr_classify", "vqhip_ssr_intersect", "vqhip_ssr_prefilter", "vqhip_ssr_resolve_temporal",
+    "vqhip_ssr_classify", "vqhip_ssr_intersect", "vqhip_ssr_prefilter", "vqhip_ssr_resolve_temporal", "vqhip_ssr_reproject",
 ]
 
 
@@ -830,6 +831,75 @@ class Context:
                                                      _ptr(radiance), radiance_fmt, 0, _ptr(reprojected), reprojected_fmt, 0, _ptr(variance), variance.stride(0),
                                                      _ptr(sample_count), sample_count.stride(0), C.byref(cb), _ptr(out), out_fmt, 0, _ptr(out_variance), 0))
         return out, out_variance
+
+    # ---- SSR denoiser pass 1 (docs/DESIGN_DETAILS.md §7.13) ---------------------------------------------------------
+    def ssr_reproject(self, tile_list, counters, depth, normals, normal_fmt, roughness8, depth_history, normal_history, normal_history_fmt, roughness8_history,
+                      radiance, radiance_fmt, radiance_history, radiance_history_fmt, motion, motion_fmt, variance_history, sample_count_history, cb,
+                      out_reprojected=None, out_fmt=FMT_RGBA16F, out_average=None, avg_fmt=abi.FMT_R11G11B10_FLOAT, out_variance=None, out_sample_count=None, stream=None):
+        """vqhip_ssr_reproject: Reproject.hlsl for every tile of the denoiser tile list. depth / depth_history: float32 [H,W] (rows may be strided); normals /
+        normal_history: int32 [H,W] (R10G10B10A2_UNORM) or float32 [H,W,4]; roughness8 / roughness8_history: uint8 [H,W]; radiance (alpha = ray length) /
+        radiance_history: [H,W,4] images; motion: [H,W,2] RG16F | RG32F; variance_history / sample_count_history: float16 [H,W]. Outputs that are not given are
+        allocated ZEROED (the pass writes listed tiles and glossy pixels only). Returns (out_reprojected, out_average, out_variance, out_sample_count); out_average
+        is int32 [H8,W8] (R11G11B10_FLOAT words) or float32 [H8,W8,4]."""
+        w, h = int(cb.bufferDimensions[0]), int(cb.bufferDimensions[1])
+        h8, w8 = (h + 7) // 8, (w + 7) // 8
+        if not (tile_list.is_cuda and tile_list.dtype == torch.int32 and tile_list.is_contiguous() and tile_list.numel() >= h8 * w8):
+            raise ValueError(f"ssr_reproject: tile_list: expected contiguous cuda int32 [{h8 * w8}]")
+        if not (counters.is_cuda and counters.dtype == torch.int32 and counters.numel() >= 2 and counters.is_contiguous()):
+            raise ValueError("ssr_reproject: counters: expected contiguous cuda int32 [2]")
+
+        def plane(t, name, dtype):                                                  # one element per pixel, rows may be strided
+            if not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == (h, w) and t.stride(1) == 1 and t.stride(0) >= w):
+                raise ValueError(f"ssr_reproject: {name}: expected cuda {dtype} {(h, w)} with unit column stride")
+            return t.stride(0)
+
+        def normal_plane(t, fmt, name):
+            if fmt == abi.FMT_R10G10B10A2_UNORM:
+                if not (t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (h, w) and t.is_contiguous()):
+                    raise ValueError(f"ssr_reproject: {name}: expected contiguous cuda int32 {(h, w)} (R10G10B10A2_UNORM words)")
+            else:
+                _check_img(t, fmt, name, (h, w))
+        s = abi.SSRReprojectSurfaces()
+        s.depth_pitch_px, s.depth_history_pitch_px = plane(depth, "depth", torch.float32), plane(depth_history, "depth_history", torch.float32)
+        s.roughness_pitch_px, s.roughness_history_pitch_px = plane(roughness8, "roughness8", torch.uint8), plane(roughness8_history, "roughness8_history", torch.uint8)
+        s.variance_history_pitch_px = plane(variance_history, "variance_history", torch.float16)
+        s.sample_count_history_pitch_px = plane(sample_count_history, "sample_count_history", torch.float16)
+        normal_plane(normals, normal_fmt, "normals")
+        normal_plane(normal_history, normal_history_fmt, "normal_history")
+        _check_img(radiance, radiance_fmt, "radiance", (h, w))
+        _check_img(radiance_history, radiance_history_fmt, "radiance_history", (h, w))
+        if motion_fmt not in (abi.FMT_RG16F, abi.FMT_RG32F):
+            raise ValueError("ssr_reproject: motion_fmt must be RG16F or RG32F")
+        _check_img(motion, motion_fmt, "motion", (h, w))
+        if out_reprojected is None:
+            out_reprojected = torch.zeros((h, w, 4), dtype=_TORCH_DTYPE[out_fmt][0], device=self.device)
+        _check_img(out_reprojected, out_fmt, "out_reprojected", (h, w))
+        if avg_fmt == abi.FMT_R11G11B10_FLOAT:
+            if out_average is None:
+                out_average = torch.zeros((h8, w8), dtype=torch.int32, device=self.device)
+            if not (out_average.is_cuda and out_average.dtype == torch.int32 and tuple(out_average.shape) == (h8, w8) and out_average.is_contiguous()):
+                raise ValueError(f"ssr_reproject: out_average: expected contiguous cuda int32 {(h8, w8)} (R11G11B10_FLOAT words)")
+        else:
+            if out_average is None:
+                out_average = torch.zeros((h8, w8, 4), dtype=torch.float32, device=self.device)
+            _check_img(out_average, avg_fmt, "out_average", (h8, w8))
+        outs = []
+        for t, name in ((out_variance, "out_variance"), (out_sample_count, "out_sample_count")):
+            if t is None:
+                t = torch.zeros((h, w), dtype=torch.float16, device=self.device)
+            if not (t.is_cuda and t.dtype == torch.float16 and tuple(t.shape) == (h, w) and t.is_contiguous()):
+                raise ValueError(f"ssr_reproject: {name}: expected contiguous cuda float16 {(h, w)}")
+            outs.append(t)
+        out_variance, out_sample_count = outs
+        for name, t in (("tile_list", tile_list), ("counters", counters), ("depth", depth), ("normals", normals), ("roughness", roughness8), ("depth_history", depth_history),
+                        ("normal_history", normal_history), ("roughness_history", roughness8_history), ("radiance", radiance), ("radiance_history", radiance_history),
+                        ("motion_vectors", motion), ("variance_history", variance_history), ("sample_count_history", sample_count_history),
+                        ("out_reprojected", out_reprojected), ("out_average", out_average), ("out_variance", out_variance), ("out_sample_count", out_sample_count)):
+            setattr(s, name, t.data_ptr())
+        s.normals_fmt, s.normal_history_fmt, s.radiance_fmt, s.radiance_history_fmt = normal_fmt, normal_history_fmt, radiance_fmt, radiance_history_fmt
+        s.motion_fmt, s.out_reprojected_fmt, s.out_average_fmt = motion_fmt, out_fmt, avg_fmt
+        self._ck(self.lib.vqhip_ssr_reproject(self._h, self._stream(stream), C.byref(s), C.byref(cb)))
+        return out_reprojected, out_average, out_variance, out_sample_count
 
     def visualize(self, src, in_fmt, params, out_fmt=None, out=None, stream=None):
         """Visualization.hlsl:CSMain (debug draw modes). params: abi.VizParams. src in the format of the target the mode shows: a colour image, the int32 [H,W]

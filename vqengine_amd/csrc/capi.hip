@@ -1448,6 +1448,77 @@ int vqhip_ssr_resolve_temporal(vqhip_ctx* ctx, void* stream, const uint32_t* den
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "ssr_resolve_temporal launch");
 }
 
+// ---- SSR denoiser pass 1 (ssr_reproject.hip; docs/DESIGN_DETAILS.md §7.13) --------------------------------------------------------------------
+int vqhip_ssr_reproject(vqhip_ctx* ctx, void* stream, const vqhip_ssr_reproject_surfaces* io, const VQ_SSSRConstants* cb) {
+    vqk::Range range_("FFX DNSR Reproject");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "ssr_reproject: ctx is NULL");
+    CTX_GUARD(ctx, "ssr_reproject");
+    if (!io || !cb) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_reproject: NULL argument");
+    if (!io->tile_list || !io->counters || !io->depth || !io->normals || !io->roughness || !io->depth_history || !io->normal_history || !io->roughness_history ||
+        !io->radiance || !io->radiance_history || !io->motion_vectors || !io->variance_history || !io->sample_count_history ||
+        !io->out_reprojected || !io->out_average || !io->out_variance || !io->out_sample_count)
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_reproject: NULL plane");
+    const uint32_t W = cb->bufferDimensions[0], H = cb->bufferDimensions[1];
+    if (W == 0 || H == 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_reproject: bad bufferDimensions");
+    if (W > VQHIP_DEPTH_HIERARCHY_MAX_DIM || H > VQHIP_DEPTH_HIERARCHY_MAX_DIM)
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_reproject: frames above 4096 in either dimension are not supported");
+    auto isNormalFmt = [](int f) { return f == VQHIP_FMT_R10G10B10A2_UNORM || f == VQHIP_FMT_RGBA32F; };
+    if (!isNormalFmt(io->normals_fmt) || !isNormalFmt(io->normal_history_fmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_reproject: normals must be R10G10B10A2_UNORM or RGBA32F");
+    if (!isImageFmt(io->radiance_fmt) || !isImageFmt(io->radiance_history_fmt) || !isImageFmt(io->out_reprojected_fmt))
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_reproject: radiance, its history and the reprojected radiance must be RGBA32F or RGBA16F");
+    if (io->motion_fmt != VQHIP_FMT_RG16F && io->motion_fmt != VQHIP_FMT_RG32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_reproject: motion vectors must be RG16F or RG32F");
+    if (io->out_average_fmt != VQHIP_FMT_R11G11B10_FLOAT && io->out_average_fmt != VQHIP_FMT_RGBA32F)
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_reproject: the average radiance must be R11G11B10_FLOAT or RGBA32F");
+    auto pitch = [&](int p) { return p ? p : (int)W; };
+    auto imgBpp = [](int f) { return f == VQHIP_FMT_RGBA32F ? (size_t)16 : (size_t)8; };
+    auto nrmBpp = [](int f) { return f == VQHIP_FMT_RGBA32F ? (size_t)16 : (size_t)4; };
+    const int tilesX = ((int)W + 7) / 8, tilesY = ((int)H + 7) / 8;
+    struct Plane { const void* p; int pitch; size_t bpp; const char* name; };
+    const Plane in[] = { { io->depth, io->depth_pitch_px, 4, "depth" }, { io->normals, io->normals_pitch_px, nrmBpp(io->normals_fmt), "normals" },
+                         { io->roughness, io->roughness_pitch_px, 1, "roughness" }, { io->depth_history, io->depth_history_pitch_px, 4, "depth_history" },
+                         { io->normal_history, io->normal_history_pitch_px, nrmBpp(io->normal_history_fmt), "normal_history" },
+                         { io->roughness_history, io->roughness_history_pitch_px, 1, "roughness_history" }, { io->radiance, io->radiance_pitch_px, imgBpp(io->radiance_fmt), "radiance" },
+                         { io->radiance_history, io->radiance_history_pitch_px, imgBpp(io->radiance_history_fmt), "radiance_history" },
+                         { io->motion_vectors, io->motion_pitch_px, io->motion_fmt == VQHIP_FMT_RG32F ? (size_t)8 : (size_t)4, "motion_vectors" },
+                         { io->variance_history, io->variance_history_pitch_px, 2, "variance_history" }, { io->sample_count_history, io->sample_count_history_pitch_px, 2, "sample_count_history" } };
+    const Plane outFull[] = { { io->out_reprojected, io->out_reprojected_pitch_px, imgBpp(io->out_reprojected_fmt), "out_reprojected" },
+                              { io->out_variance, io->out_variance_pitch_px, 2, "out_variance" }, { io->out_sample_count, io->out_sample_count_pitch_px, 2, "out_sample_count" } };
+    for (const Plane& p : in) if (pitch(p.pitch) < (int)W) return fail(ctx, VQHIP_ERR_INVALID_ARG, std::string("ssr_reproject: pitch < width: ") + p.name);
+    for (const Plane& p : outFull) if (pitch(p.pitch) < (int)W) return fail(ctx, VQHIP_ERR_INVALID_ARG, std::string("ssr_reproject: pitch < width: ") + p.name);
+    auto bytes = [&](const Plane& p) { return ((size_t)(H - 1) * pitch(p.pitch) + W) * p.bpp; };
+    struct Span { const void* p; size_t n; const char* name; };
+    const Span outs[] = { { outFull[0].p, bytes(outFull[0]), outFull[0].name }, { outFull[1].p, bytes(outFull[1]), outFull[1].name }, { outFull[2].p, bytes(outFull[2]), outFull[2].name },
+                          { io->out_average, (size_t)tilesX * tilesY * (io->out_average_fmt == VQHIP_FMT_RGBA32F ? 16 : 4), "out_average" } };
+    for (int i = 0; i < 4; ++i) for (int j = i + 1; j < 4; ++j)
+        if (rangesOverlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_reproject: the outputs overlap each other");
+    for (const Span& o : outs) {
+        for (const Plane& p : in)
+            if (rangesOverlap(p.p, bytes(p), o.p, o.n))
+                return fail(ctx, VQHIP_ERR_INVALID_ARG, std::string("ssr_reproject: ") + o.name + " overlaps the input " + p.name + " (tiles read what other tiles would write; ping-pong the history)");
+        if (rangesOverlap(io->tile_list, (size_t)tilesX * tilesY * 4, o.p, o.n) || rangesOverlap(io->counters, 8, o.p, o.n))
+            return fail(ctx, VQHIP_ERR_INVALID_ARG, std::string("ssr_reproject: ") + o.name + " overlaps the tile list or its counters");
+    }
+    SsrReprojectArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.tileList = io->tile_list; a.counters = io->counters; a.depth = io->depth; a.normals = io->normals; a.roughness = io->roughness;
+    a.depthHist = io->depth_history; a.normalHist = io->normal_history; a.roughnessHist = io->roughness_history;
+    a.radiance = io->radiance; a.radianceHist = io->radiance_history; a.motion = io->motion_vectors; a.varianceHist = io->variance_history; a.sampleCountHist = io->sample_count_history;
+    a.outReprojected = io->out_reprojected; a.outAverage = io->out_average; a.outVariance = io->out_variance; a.outSampleCount = io->out_sample_count;
+    a.width = (int)W; a.height = (int)H; a.tilesX = tilesX; a.tilesY = tilesY;
+    a.depthPitch = pitch(io->depth_pitch_px); a.normalPitch = pitch(io->normals_pitch_px); a.roughnessPitch = pitch(io->roughness_pitch_px);
+    a.depthHistPitch = pitch(io->depth_history_pitch_px); a.normalHistPitch = pitch(io->normal_history_pitch_px); a.roughnessHistPitch = pitch(io->roughness_history_pitch_px);
+    a.radiancePitch = pitch(io->radiance_pitch_px); a.radianceHistPitch = pitch(io->radiance_history_pitch_px); a.motionPitch = pitch(io->motion_pitch_px);
+    a.varianceHistPitch = pitch(io->variance_history_pitch_px); a.sampleCountHistPitch = pitch(io->sample_count_history_pitch_px);
+    a.outReprojectedPitch = pitch(io->out_reprojected_pitch_px); a.outVariancePitch = pitch(io->out_variance_pitch_px); a.outSampleCountPitch = pitch(io->out_sample_count_pitch_px);
+    a.normF32 = io->normals_fmt == VQHIP_FMT_RGBA32F; a.normHistF32 = io->normal_history_fmt == VQHIP_FMT_RGBA32F; a.radF32 = io->radiance_fmt == VQHIP_FMT_RGBA32F;
+    a.radHistF32 = io->radiance_history_fmt == VQHIP_FMT_RGBA32F; a.motionF32 = io->motion_fmt == VQHIP_FMT_RG32F; a.outF32 = io->out_reprojected_fmt == VQHIP_FMT_RGBA32F;
+    a.avgF32 = io->out_average_fmt == VQHIP_FMT_RGBA32F; a.arithDxc = ctx->arithDxc;
+    a.invProj = cb->invProjection; a.invView = cb->invView; a.prevViewProj = cb->prevViewProjection; a.roughnessThreshold = cb->roughnessThreshold;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipError_t e = launch_ssr_reproject((hipStream_t)stream, a, ctx->nCUs);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "ssr_reproject launch");
+}
+
 int vqhip_specular_mip_count(int spec_res0) { return vqhip_mip_level_count(spec_res0, spec_res0) - 1; }
 size_t vqhip_cube_bytes(int res0, int nMips, vqhip_format fmt) {
     const size_t bpp = fmt == VQHIP_FMT_RGBA32F ? 16 : 8;

@@ -10,6 +10,7 @@
 #include "vq_internal.h"
 #include "vq_devmath.h"
 #include "vq_sampling.h"
+#include "vq_ssr_denoise.h"
 
 using namespace vqd;
 
@@ -17,23 +18,12 @@ namespace vqk {
 
 namespace {
 
-// min / max as §7.11 pins them: the second operand unless the first one wins
-VQD float max2(float a, float b) { return (b > a || a != a) ? b : a; }
-VQD float exp_(float x) { return exp2_(x * __uint_as_float(0x3FB8AA3Bu)); }                                       // the binary32 nearest log2(e): DXC's lowering
-VQD float lerp_w(float a, float b, float t) { return a + t * (b - a); }
-
-// the wave's own LDS traffic: make its stores visible to its loads (and its loads complete before the next tile's stores) without a workgroup barrier
-VQD void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using namespace dnsr;
 
 VQD uint32_t pack2(float a, float b) {
     const _Float16 ha = to_f16(a), hb = to_f16(b);
     return (uint32_t)__builtin_bit_cast(uint16_t, ha) | ((uint32_t)__builtin_bit_cast(uint16_t, hb) << 16);
 }
-VQD float rh(float x) { return (float)to_f16(x); }                                                                // through binary16 and back: what f32tof16 / f16tof32 leave
 VQD float lo16(uint32_t u) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(u & 0xffffu)); }
 VQD float hi16(uint32_t u) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(u >> 16)); }
 
@@ -62,25 +52,12 @@ VQD f3 sample_average(const SsrDenoiseArgs& a, uint32_t px, uint32_t py) {
     const float4 r = blend4(load_avg(a, x0, y0), load_avg(a, x1, y0), load_avg(a, x0, y1), load_avg(a, x1, y1), wx, wy);
     return mk3(r.x, r.y, r.z);
 }
-VQD f3 load_rgb(const void* img, int f32, size_t i) {
-    const float4 c = f32 ? load_px<0>(img, i) : load_px<1>(img, i);
-    return mk3(c.x, c.y, c.z);
-}
-VQD float load_r16f(const void* plane, size_t i) { return (float)((const _Float16*)plane)[i]; }
 VQD void store_out(const SsrDenoiseArgs& a, uint32_t x, uint32_t y, f3 c, float var) {
     if (x >= (uint32_t)a.width || y >= (uint32_t)a.height) return;                                                // a store outside the UAV is dropped
     const float4 v = make_float4(c.x, c.y, c.z, c.z);                                                             // radiance.xyzz
     if (a.outF32) store_px<0>(a.outRadiance, (size_t)y * a.outPitch + x, v); else store_px<1>(a.outRadiance, (size_t)y * a.outPitch + x, v);
     ((_Float16*)a.outVariance)[(size_t)y * a.outVariancePitch + x] = to_f16(var);
 }
-// the tile of list entry g: false when it lies beyond the tile grid (then nothing of the entry is used as an index)
-VQD bool tile_origin(const SsrDenoiseArgs& a, uint32_t g, int* x0, int* y0) {
-    const uint32_t e = a.tileList[g];
-    const uint32_t tx = (e & 0xffffu) >> 3, ty = (e >> 16) >> 3;
-    *x0 = (int)(tx * 8u); *y0 = (int)(ty * 8u);
-    return tx < (uint32_t)a.tilesX && ty < (uint32_t)a.tilesY;
-}
-
 // FFX_DNSR_Reflections_GetRadianceWeight
 VQD float radiance_weight(f3 avg, f3 rad, float variance, bool dxc) {
     return max2(exp_(-(0.6f + variance * 0.1f) * length_rt(sub(avg, rad), dxc)), 1.0e-2f);
@@ -101,7 +78,7 @@ __global__ __launch_bounds__(256) void k_ssr_prefilter(SsrDenoiseArgs a) {
     const float fW = (float)a.width, fH = (float)a.height;
     for (uint32_t g = blockIdx.x * 4u + wave; g < n; g += gridDim.x * 4u) {
         int x0, y0;
-        if (!tile_origin(a, g, &x0, &y0)) continue;                                                               // wave-uniform
+        if (!tile_origin(a.tileList, g, a.tilesX, a.tilesY, &x0, &y0)) continue;                            // wave-uniform
         #pragma unroll
         for (int k = 0; k < 4; ++k) {                                                                             // FFX_DNSR_Reflections_LoadNeighborhood, Prefilter.hlsl:51-66
             const int idx = (int)lane + 64 * k, qx = x0 - 4 + (idx & 15), qy = y0 - 4 + (idx >> 4);
@@ -166,11 +143,6 @@ __global__ __launch_bounds__(256) void k_ssr_prefilter(SsrDenoiseArgs a) {
     }
 }
 
-// FFX_DNSR_Reflections_LocalNeighborhoodKernelWeight(i) = exp((-3 i^2) / 25) for |i| = 0..4 under the contract's exp (tests/test_ssr_denoise_cpu.py pins the words)
-VQD float kernel_weight(int i) {
-    const int m = i < 0 ? -i : i;
-    return __uint_as_float(m == 0 ? 0x3f800000u : m == 1 ? 0x3f630d38u : m == 2 ? 0x3f1e6897u : m == 3 ? 0x3eaddf76u : 0x3e162023u);
-}
 // FFX_DNSR_Reflections_ClipAABB, ffx_denoiser_reflections_common.h:105-128
 VQD f3 clip_aabb(f3 lo, f3 hi, f3 prev) {
     const f3 centre = mk3(0.5f * (hi.x + lo.x), 0.5f * (hi.y + lo.y), 0.5f * (hi.z + lo.z));
@@ -181,13 +153,6 @@ VQD f3 clip_aabb(f3 lo, f3 hi, f3 prev) {
     if (mx > 1.0f) return mk3(centre.x + fdiv_(vec.x, mx), centre.y + fdiv_(vec.y, mx), centre.z + fdiv_(vec.z, mx));
     return prev;
 }
-VQD float luminance(f3 c, bool dxc) { return max2(dot_rt(c, mk3(0.299f, 0.587f, 0.114f), dxc), 0.001f); }
-VQD float temporal_variance(f3 history, f3 rad, bool dxc) {
-    const float hl = luminance(history, dxc), l = luminance(rad, dxc);
-    const float diff = fdiv_(abs_(hl - l), max2(max2(hl, l), 0.5f));
-    return diff * diff;
-}
-VQD bool not_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
 
 __global__ __launch_bounds__(256) void k_ssr_resolve_temporal(SsrDenoiseArgs a) {
     __shared__ float sA[4][3][256];                                                                               // radiance x | y | z, already rounded through binary16
@@ -197,7 +162,7 @@ __global__ __launch_bounds__(256) void k_ssr_resolve_temporal(SsrDenoiseArgs a) 
     const bool dxc = a.arithDxc != 0;
     for (uint32_t g = blockIdx.x * 4u + wave; g < n; g += gridDim.x * 4u) {
         int x0, y0;
-        if (!tile_origin(a, g, &x0, &y0)) continue;
+        if (!tile_origin(a.tileList, g, a.tilesX, a.tilesY, &x0, &y0)) continue;
         #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int idx = (int)lane + 64 * k, qx = x0 - 4 + (idx & 15), qy = y0 - 4 + (idx >> 4);
@@ -256,30 +221,16 @@ __global__ __launch_bounds__(256) void k_ssr_resolve_temporal(SsrDenoiseArgs a) 
     }
 }
 
-// every CU filled once with as many workgroups as the kernel's registers and LDS admit; never more workgroups than the tile grid can list
-template <typename K> hipError_t launch(hipStream_t s, K kernel, int perCU, const SsrDenoiseArgs& a, int nCUs) {
-    if (nCUs <= 0) nCUs = 256;
-    const uint32_t maxTiles = (uint32_t)a.tilesX * (uint32_t)a.tilesY;
-    uint32_t blocks = (uint32_t)(perCU * nCUs);
-    if (blocks > (maxTiles + 3u) / 4u) blocks = (maxTiles + 3u) / 4u;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-template <typename K> int blocks_per_cu(K kernel) {
-    int n = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, 0) == hipSuccess && n > 0 ? n : 2;
-}
-
 } // namespace
 
 hipError_t launch_ssr_prefilter(hipStream_t s, const SsrDenoiseArgs& a, int nCUs) {
     static const int perCU = blocks_per_cu(k_ssr_prefilter);
-    return launch(s, k_ssr_prefilter, perCU, a, nCUs);
+    return launch_tiles(s, k_ssr_prefilter, perCU, a, nCUs);
 }
 
 hipError_t launch_ssr_resolve_temporal(hipStream_t s, const SsrDenoiseArgs& a, int nCUs) {
     static const int perCU = blocks_per_cu(k_ssr_resolve_temporal);
-    return launch(s, k_ssr_resolve_temporal, perCU, a, nCUs);
+    return launch_tiles(s, k_ssr_resolve_temporal, perCU, a, nCUs);
 }
 
 } // namespace vqk

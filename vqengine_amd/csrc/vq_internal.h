@@ -185,6 +185,22 @@ struct SsrDenoiseArgs {
 hipError_t launch_ssr_prefilter(hipStream_t s, const SsrDenoiseArgs& a, int nCUs);
 hipError_t launch_ssr_resolve_temporal(hipStream_t s, const SsrDenoiseArgs& a, int nCUs);
 
+// SSR denoiser pass 1 (vqhip_ssr_reproject, ssr_reproject.hip; docs/DESIGN_DETAILS.md §7.13). Pitches in pixels.
+struct SsrReprojectArgs {
+    const uint32_t* tileList; const uint32_t* counters;               // counters[1] tiles, read on the device and clamped to tilesX * tilesY
+    const float* depth; const void* normals; const uint8_t* roughness;
+    const float* depthHist; const void* normalHist; const uint8_t* roughnessHist;
+    const void* radiance; const void* radianceHist; const void* motion; const void* varianceHist; const void* sampleCountHist;
+    void* outReprojected; void* outAverage; void* outVariance; void* outSampleCount;
+    int width, height, tilesX, tilesY;
+    int depthPitch, normalPitch, roughnessPitch, depthHistPitch, normalHistPitch, roughnessHistPitch, radiancePitch, radianceHistPitch, motionPitch,
+        varianceHistPitch, sampleCountHistPitch, outReprojectedPitch, outVariancePitch, outSampleCountPitch;
+    int normF32, normHistF32, radF32, radHistF32, motionF32, outF32, avgF32, arithDxc;
+    VQ_matrix invProj, invView, prevViewProj;
+    float roughnessThreshold;
+};
+hipError_t launch_ssr_reproject(hipStream_t s, const SsrReprojectArgs& a, int nCUs);
+
 // 4x MSAA lit draw + resolve (vqhip_forward_lighting_msaa, msaa.hip). Edge pixels (samples with more than one owner) are listed by the
 // shading kernel in edgeList[0 .. *edgeCount) as y * width + x; *edgeCount is zeroed on the call's stream before the launch.
 struct MsaaLayer { const float4* gb0; const float4* gb1; const float4* gb2; const float4* gb3; const uint8_t* cov; int pitch; };

@@ -698,3 +698,104 @@ def ssr_smooth_surfaces(width, height, seed=0x5A00):
     n01 = np.concatenate([q.astype(np.float32) / np.float32(1023.0), np.ones((height, width, 1), np.float32)], axis=-1)
     depth = (0.5 + 0.02 * (xs + 2.0 * ys) / (width + 2.0 * height) + 0.002 * r.random((height, width))).astype(np.float32)
     return depth, packed, n01
+
+
+def _pack_normals(n):
+    q = np.clip(np.floor((n * 0.5 + 0.5) * 1023.0 + 0.5), 0, 1023).astype(np.uint32)
+    packed = (q[..., 0] | (q[..., 1] << 10) | (q[..., 2] << 20) | (np.uint32(3) << 30)).astype(np.uint32)
+    return packed, np.concatenate([q.astype(np.float32) / np.float32(1023.0), np.ones(n.shape[:2] + (1,), np.float32)], axis=-1)
+
+
+def ssr_reproject_frames(width, height, seed=0x4E90):
+    """A designed pair of frames for vqhip_ssr_reproject (docs/DESIGN_DETAILS.md §7.13): the current frame and the history the previous one left, with a camera that
+    moved in between (cb.prevViewProjection is the previous camera's). Column bands, left to right:
+      A  x < 0.30 w          flat near-mirror (roughness 5 / 255), identical normals, no motion: the hit-point reprojection wins and the early-out is taken
+      B  0.30 w .. 0.55 w    glossy, normals perturbed by a few degrees, moved one pixel per frame; the history is the current frame shifted: surface reprojection accepted
+      C  0.55 w .. 0.70 w    upper half: as B with the history radiance far from the local mean: discarded. lower half: white-noise normals that differ between the
+                             frames and a depth step: the 3 x 3 search and the 2 x 2 path
+      E  0.70 w .. 0.82 w    as B with motion vectors of 3 (1.5 in uv): the surface uv leaves [0, 1] and is sampled clamped
+      F  x >= 0.82 w         rough (>= 0.6): not glossy
+    A frame whose size is no multiple of 8 has partial tiles on its right and bottom edges. Returns a dict: cb; depth, depth_hist float32 [H,W]; packed, packed_hist uint32
+    [H,W] with n01, n01_hist float32 [H,W,4]; roughness8, roughness8_hist uint8 [H,W]; radiance (alpha = ray length), radiance_hist float32 [H,W,4]; motion float32
+    [H,W,2]; variance_hist, sample_count_hist float16 [H,W]."""
+    r = _chunk_rng(seed, 0)
+    h, w = height, width
+    cb = ssr_constants(w, h, 1)
+    prev = ssr_constants(w, h, 1, camera=(3.2, 10.0, -59.9))
+    _set_matrix(cb.prevViewProjection, _matrix_of(prev.view) @ _matrix_of(prev.projection))
+    ys, xs = np.mgrid[0:h, 0:w]
+    band = np.digitize(xs / w, [0.30, 0.55, 0.70, 0.82])                          # 0 A, 1 B, 2 C, 3 E, 4 F
+    lower = ys >= h // 2
+    edges = (band == 2) & lower
+    depth = (0.990 + 0.004 * (xs + 2.0 * ys) / (w + 2.0 * h) + 0.0002 * r.random((h, w))).astype(np.float32)           # 10 .. 17 units from the camera
+    depth = np.where(edges & ((xs + ys) % 7 < 3), depth + np.float32(0.005), depth).astype(np.float32)
+    base = np.array([0.2, 0.9, -0.4])
+    n = base[None, None, :] + np.where((band == 0)[..., None], 0.0, 0.06 * r.normal(size=(h, w, 3)))
+    wild = r.normal(size=(h, w, 3))
+    n = np.where(edges[..., None], wild, n)
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    packed, n01 = _pack_normals(n)
+    rough = np.select([band == 0, band == 4], [5, r.integers(153, 256, (h, w))], r.integers(20, 31, (h, w))).astype(np.uint8)
+    colour = np.array([1.2, 0.8, 0.5], np.float32)
+    rad = np.empty((h, w, 4), np.float32)
+    rad[..., :3] = colour * (0.6 + 0.8 * r.random((h, w, 3), dtype=np.float32))
+    rad[..., 3] = 4.0 * r.random((h, w), dtype=np.float32)
+    dx = np.where(band == 0, 0, 1)                                                # pixels per frame; band E's vectors are overwritten below
+    motion = np.zeros((h, w, 2), np.float32)
+    motion[..., 0] = (2.0 * dx / w).astype(np.float32)
+    motion[band == 3] = (3.0, -0.5)
+
+    def shifted(a):                                                               # history[y, x - 1] = current[y, x] where the surface moved
+        return np.where((dx > 0).reshape(dx.shape + (1,) * (a.ndim - 2)), np.roll(a, -1, axis=1), a)
+    depth_hist = shifted(depth)
+    n_hist = shifted(n)
+    other = r.normal(size=(h, w, 3))
+    n_hist = np.where(edges[..., None], other / np.linalg.norm(other, axis=-1, keepdims=True), n_hist)
+    packed_hist, n01_hist = _pack_normals(n_hist)
+    rough_hist = shifted(rough)
+    rad_hist = np.empty((h, w, 4), np.float32)
+    rad_hist[..., :3] = colour * (0.95 + 0.1 * r.random((h, w, 3), dtype=np.float32))
+    rad_hist[..., 3] = 0.0
+    rad_hist[(band == 2) & ~lower, :3] += np.float32(4.0)
+    variance_hist = (r.random((h, w), dtype=np.float32) * np.float32(0.5)).astype(np.float16)
+    count_hist = r.integers(0, 33, (h, w)).astype(np.float16)
+    return {"cb": cb, "depth": depth, "depth_hist": depth_hist, "packed": packed, "n01": n01, "packed_hist": packed_hist, "n01_hist": n01_hist,
+            "roughness8": rough, "roughness8_hist": rough_hist, "radiance": rad, "radiance_hist": rad_hist, "motion": motion,
+            "variance_hist": variance_hist, "sample_count_hist": count_hist}
+
+
+def ssr_reproject_threshold_frames():
+    """16 x 16 frames for vqhip_ssr_reproject in which every glossy pixel's disocclusion factor is EXACTLY 0.9 (word 3f666666), in both arithmetic readings: RGBA32F
+    normals, the pixel's own (0, 1, 0) exactly, the history's normalize((2 hx - 1, 1, 0)) with hx the word 3f34ae3a — then dot(n, hn) is hn.y and
+    exp((-|1 - hn.y|) * 1.4) rounds to 0.9 under the contract's exp; no motion, a camera that did not move, one depth everywhere (the depth term is exp(-0) = 1) and the
+    history radiance within the local variance (surface reprojection is accepted; the hit candidate fails the 0.9999 similarity). 0.9 is neither > 0.9 nor < 0.9:
+    no early-out, no search, no 2 x 2 path, the history is kept. The 8 x 8 pixels in the middle are glossy (their 9 x 9 neighbourhoods lie inside the frame), the rest rough. Same dict as ssr_reproject_frames."""
+    w = h = 16
+    f = ssr_reproject_frames(w, h, seed=0x0909)
+    rng = np.random.default_rng(0x0909)
+    f["cb"].prevViewProjection = ssr_constants(w, h, 1).prevViewProjection
+    f["roughness8"][:] = 200
+    f["roughness8"][4:12, 4:12] = 25
+    f["roughness8_hist"][:] = 25
+    f["motion"][:] = 0
+    f["depth"][:] = 0.99
+    f["depth_hist"][:] = 0.99
+    f["radiance"][..., :3] = 1.0 + 0.6 * (rng.random((h, w, 3), dtype=np.float32) - 0.5)
+    f["radiance"][..., 3] = 0.0
+    f["radiance_hist"][..., :3] = 1.0
+    f["n01"][..., :3] = (0.5, 1.0, 0.5)
+    f["n01_hist"][..., :3] = (np.array([0x3F34AE3A], np.uint32).view(np.float32)[0], 1.0, 0.5)
+    return f
+
+
+def ssr_motion_vectors(depth, cb):
+    """float32 [H,W,2]: the screen-space motion (NDC units: current minus previous position, as vqhip_forward_lighting_mrt writes it) of a STATIC scene seen at
+    NDC depth `depth` through cb's camera, whose previous camera is cb.prevViewProjection — float64, rounded once. Sky pixels (depth 1) move like the far plane."""
+    h, w = depth.shape
+    x = (np.arange(w) + 0.5) / w * 2.0 - 1.0
+    y = 1.0 - (np.arange(h) + 0.5) / h * 2.0
+    ndc = np.stack(np.broadcast_arrays(x[None, :], y[:, None], depth.astype(np.float64), 1.0), -1)
+    world = ndc @ _matrix_of(cb.invViewProjection)
+    world /= world[..., 3:]
+    prev = world @ _matrix_of(cb.prevViewProjection)
+    return (ndc[..., :2] - prev[..., :2] / prev[..., 3:]).astype(np.float32)
