@@ -283,8 +283,8 @@ typedef struct vqhip_interpolants {
     int32_t width, height, row_pitch_px;
 } vqhip_interpolants;
 
-/* texScreenSpaceAO (t9): R8_UNORM [height][width] (RenderResources.cpp:358-371), or NULL when SSAO is
- * off (the reference then clears the target to 1.0, SceneRendering.cpp:1543-1553). */
+/* texScreenSpaceAO (t9): R8_UNORM [height][width] (RenderResources.cpp:358-371) — the plane vqhip_cacao writes (FidelityFX CACAO, below) —, or NULL when
+ * SSAO is off (the reference then clears the target to 1.0, SceneRendering.cpp:1543-1553). */
 typedef struct vqhip_ssao {
     const void* texels; int32_t width, height;
 } vqhip_ssao;
@@ -345,7 +345,8 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * later in round 4, additions only: vqhip_forward_lighting_mrt, vqhip_forward_lighting_from_materials_mrt, vqhip_scene_normals_from_materials,
                                * vqhip_composite_reflections; vqhip_visualize reads R10G10B10A2 / RG16F / RG32F inputs.
                                * Later additions to 3: vqhip_gbuffer_msaa, vqhip_forward_lighting_msaa; vqhip_msaa_surfaces, vqhip_msaa_resolve_surfaces, vqhip_depth_hierarchy (+ _bytes, _level_offset_bytes);
-                               * vqhip_ssr_classify, vqhip_ssr_intersect; vqhip_ssr_prefilter, vqhip_ssr_resolve_temporal, VQHIP_FMT_R11G11B10_FLOAT; vqhip_ssr_reproject, vqhip_ssr_reproject_surfaces */
+                               * vqhip_ssr_classify, vqhip_ssr_intersect; vqhip_ssr_prefilter, vqhip_ssr_resolve_temporal, VQHIP_FMT_R11G11B10_FLOAT; vqhip_ssr_reproject, vqhip_ssr_reproject_surfaces;
+                               * VQ_CacaoConstants, vqhip_cacao (+ _work_bytes, _plane_offset_bytes) */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -997,6 +998,62 @@ VQHIP_API int  vqhip_exchange_blur_halos(vqhip_comm* comm, void* stream, const v
  * root == VQHIP_ALL_RANKS: every rank receives it. Transfers are grouped point-to-point messages straight into the frame. */
 VQHIP_API int  vqhip_composite_tiles(vqhip_comm* comm, void* stream, const void* tile, int width, int frame_height,
         vqhip_format fmt, int root, void* frame);
+
+/* ---- FidelityFX CACAO ambient occlusion (VQRenderer::RenderAmbientOcclusion, SceneRendering.cpp:1503-1555; AmbientOcclusionPass -> FFX_CACAO_D3D12Draw,
+ * AMDFidelityFX/CACAO/ffx_cacao_impl.cpp:1922-2259; Shaders/AMDFidelityFX/CACAO/ffx_cacao.hlsl). docs/DESIGN_DETAILS.md §7.14; tests/cacao_ref.py states it in numpy.
+ * Writes Tex_AmbientOcclusion (R8_UNORM), the texScreenSpaceAO of the lit draw, from Tex_SceneDepthResolve (R32F) and Tex_SceneNormals at native resolution:
+ *   CSPrepareNativeDepthsAndMips -> CSPrepareNativeNormalsFromInputNormals -> CSGenerateQ2 x 4 passes -> CSEdgeSensitiveBlur<blurPassCount> x 4 -> CSApply,
+ * five kernels on `stream` (the four passes of a stage are ONE launch), no host synchronisation, no allocation: every intermediate lives in `work`.
+ * Implemented: quality HIGH (FFX_CACAO_QUALITY_HIGH), useDownsampledSsao off, generateNormals off. HIGHEST (the adaptive stage on top of this pipeline), the lower
+ * levels, the downsampled path and normal generation return VQHIP_ERR_UNSUPPORTED.
+ * VQ_CacaoConstants == FFX_CACAO_Constants (ffx_cacao.h:95-154): the engine keeps calling FFX_CACAO_UpdateBufferSizeInfo / _UpdateConstants /
+ * _UpdatePerPassConstants (ffx_cacao.cpp:48-262) and hands the shared block and the four per-pass blocks over as FFX_CACAO_D3D12Draw uploads them. */
+typedef struct VQ_CacaoConstants {
+    float DepthUnpackConsts[2], CameraTanHalfFOV[2], NDCToViewMul[2], NDCToViewAdd[2], DepthBufferUVToViewMul[2], DepthBufferUVToViewAdd[2];
+    float EffectRadius, EffectShadowStrength, EffectShadowPow, EffectShadowClamp;
+    float EffectFadeOutMul, EffectFadeOutAdd, EffectHorizonAngleThreshold, EffectSamplingRadiusNearLimitRec;
+    float DepthPrecisionOffsetMod, NegRecEffectRadius, LoadCounterAvgDiv, AdaptiveSampleCountLimit;
+    float InvSharpness; int32_t PassIndex; float BilateralSigmaSquared, BilateralSimilarityDistanceSigma;
+    float PatternRotScaleMatrices[5][4];
+    float NormalsUnpackMul, NormalsUnpackAdd, DetailAOStrength, Dummy0;
+    float SSAOBufferDimensions[2], SSAOBufferInverseDimensions[2], DepthBufferDimensions[2], DepthBufferInverseDimensions[2];
+    int32_t DepthBufferOffset[2]; float PerPassFullResUVOffset[2];
+    float InputOutputBufferDimensions[2], InputOutputBufferInverseDimensions[2], ImportanceMapDimensions[2], ImportanceMapInverseDimensions[2];
+    float DeinterleavedDepthBufferDimensions[2], DeinterleavedDepthBufferInverseDimensions[2], DeinterleavedDepthBufferOffset[2], DeinterleavedDepthBufferNormalisedOffset[2];
+    struct { float m[4][4]; } NormalsWorldToViewspaceMatrix;   /* FFX_CACAO_Matrix4x4: row-major floats; the shader's cbuffer reads them column-major (§7.14) */
+} VQ_CacaoConstants;
+VQHIP_STATIC_ASSERT(sizeof(VQ_CacaoConstants) == 384 && offsetof(VQ_CacaoConstants, EffectRadius) == 48 && offsetof(VQ_CacaoConstants, InvSharpness) == 96 &&
+                    offsetof(VQ_CacaoConstants, PassIndex) == 100 && offsetof(VQ_CacaoConstants, PatternRotScaleMatrices) == 112 &&
+                    offsetof(VQ_CacaoConstants, NormalsUnpackMul) == 192 && offsetof(VQ_CacaoConstants, SSAOBufferDimensions) == 208 &&
+                    offsetof(VQ_CacaoConstants, DepthBufferOffset) == 240 && offsetof(VQ_CacaoConstants, DeinterleavedDepthBufferNormalisedOffset) == 312 &&
+                    offsetof(VQ_CacaoConstants, NormalsWorldToViewspaceMatrix) == 320, "VQ_CacaoConstants layout");
+typedef enum vqhip_cacao_quality {   /* FFX_CACAO_Quality */
+    VQHIP_CACAO_QUALITY_LOWEST = 0, VQHIP_CACAO_QUALITY_LOW = 1, VQHIP_CACAO_QUALITY_MEDIUM = 2, VQHIP_CACAO_QUALITY_HIGH = 3, VQHIP_CACAO_QUALITY_HIGHEST = 4
+} vqhip_cacao_quality;
+typedef enum vqhip_cacao_plane {
+    VQHIP_CACAO_PLANE_DEPTHS = 0,    /* deinterleaved view-space depths, R16F: slice 0..3, mip 0..3; mip k is max(1, hw >> k) x max(1, hh >> k) */
+    VQHIP_CACAO_PLANE_NORMALS = 1,   /* deinterleaved view-space normals, R8G8B8A8_SNORM: slice 0..3, hw x hh */
+    VQHIP_CACAO_PLANE_PING = 2,      /* (occlusion, packed edges), R8G8_UNORM, as CSGenerateQ2 wrote them: slice 0..3, hw x hh */
+    VQHIP_CACAO_PLANE_PONG = 3       /* the same after the edge-sensitive blur (not written when blurPassCount == 0) */
+} vqhip_cacao_plane;
+#define VQHIP_CACAO_MAX_DIM 16384
+#define VQHIP_CACAO_MAX_BLUR_PASSES 8
+/* The work buffer of a width x height frame, hw = (width + 1) / 2, hh = (height + 1) / 2: every plane above, dense rows, slice after slice.
+ * _plane_offset_bytes: where slice `slice` (mip `mip` of DEPTHS; 0 otherwise) starts, so that a caller or a test can address every intermediate.
+ * Both return 0 for arguments out of range (offset 0 is also the valid start of DEPTHS slice 0 mip 0). Host-only. */
+VQHIP_API size_t vqhip_cacao_work_bytes(int width, int height);
+VQHIP_API size_t vqhip_cacao_plane_offset_bytes(int width, int height, int plane, int slice, int mip);
+/*   depth     : R32F [height] rows of depthPitchBytes bytes (a multiple of 4, >= 4 * width)
+ *   normals   : normalFmt R10G10B10A2_UNORM (4 B per pixel) or RGBA32F (16 B), world space as (n + 1) / 2; rows of normalPitchBytes bytes (a multiple of the pixel size)
+ *   shared / perPass[4] : the constant blocks; their buffer sizes must be those of this frame and perPass[i].PassIndex == i
+ *   qualityLevel : VQHIP_CACAO_QUALITY_HIGH; blurPassCount 0..8 (0: the blur is skipped and CSApply reads the ping planes)
+ *   work      : vqhip_cacao_work_bytes(width, height) bytes, 256-byte aligned, not overlapping the other buffers
+ *   ao        : R8_UNORM [height] rows of aoPitchBytes bytes (>= width); bytes between width and the pitch are not written
+ * Returns VQHIP_ERR_INVALID_ARG for NULL pointers, non-positive sizes, pitches or workBytes too small, constants of another frame size;
+ * VQHIP_ERR_UNSUPPORTED for another quality level, normal format or a frame above VQHIP_CACAO_MAX_DIM — without launching anything. */
+VQHIP_API int vqhip_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_t depthPitchBytes, const void* normals, int normalFmt, size_t normalPitchBytes,
+        const VQ_CacaoConstants* shared, const VQ_CacaoConstants perPass[4], int qualityLevel, int blurPassCount,
+        void* work, size_t workBytes, uint8_t* ao, size_t aoPitchBytes, int width, int height);
 
 #ifdef __cplusplus
 }

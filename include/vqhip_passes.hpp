@@ -412,6 +412,49 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// Ambient occlusion == AmbientOcclusionPass::RecordCommands -> FFX_CACAO_D3D12Draw (AmbientOcclusion.cpp; VQRenderer::RenderAmbientOcclusion,
+// SceneRendering.cpp:1503-1555): vqhip_cacao at quality HIGH, native resolution. Owns FidelityFX CACAO's intermediates (the deinterleaved depths and
+// normals, the ping / pong occlusion planes) as ONE work buffer, sized for the window like FFX_CACAO_D3D12InitScreenSizeDependentResources does. The
+// engine keeps filling the constants with FidelityFX's own FFX_CACAO_UpdateBufferSizeInfo / _UpdateConstants / _UpdatePerPassConstants from
+// FDrawParameters::matProj / matNormalToView and hands the five blocks over; TexAmbientOcclusion is what the lit draw reads as texScreenSpaceAO.
+// ---------------------------------------------------------------------------------------------------------------
+class AmbientOcclusionPass : public RenderPassBase {
+public:
+    struct FResourceParameters : public IRenderPassResourceCollection {};
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        VQ_CacaoConstants Constants = {};                        // FFX_CACAO_UpdateConstants
+        VQ_CacaoConstants PerPassConstants[4] = {};              // + FFX_CACAO_UpdatePerPassConstants(.., i)
+        int BlurPassCount = 2;                                   // FFX_CACAO_Settings::blurPassCount
+        const float* TexSceneDepthResolve = nullptr;             // Tex_SceneDepthResolve, R32F, dense rows
+        const void* TexSceneNormals = nullptr;                   // Tex_SceneNormals, R10G10B10A2_UNORM, dense rows
+        uint8_t* TexAmbientOcclusion = nullptr;                  // Tex_AmbientOcclusion, R8_UNORM, dense rows
+    };
+    explicit AmbientOcclusionPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    ~AmbientOcclusionPass() override { OnDestroyWindowSizeDependentResources(); }
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { OnDestroyWindowSizeDependentResources(); }
+    void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override {
+        OnDestroyWindowSizeDependentResources();
+        mWidth = Width; mHeight = Height;
+        mWorkBytes = vqhip_cacao_work_bytes((int)Width, (int)Height);
+        mWork = mWorkBytes ? Alloc(mWorkBytes) : nullptr;
+    }
+    void OnDestroyWindowSizeDependentResources() override { Free(mWork); mWorkBytes = 0; mWidth = mHeight = 0; }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p || !mWork) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        mStatus = vqhip_cacao(mCtx, p->Stream, p->TexSceneDepthResolve, (size_t)mWidth * 4, p->TexSceneNormals, VQHIP_FMT_R10G10B10A2_UNORM, (size_t)mWidth * 4,
+                              &p->Constants, p->PerPassConstants, VQHIP_CACAO_QUALITY_HIGH, p->BlurPassCount, mWork, mWorkBytes, p->TexAmbientOcclusion,
+                              (size_t)mWidth, (int)mWidth, (int)mHeight);
+    }
+    const void* GetWorkBuffer() const { return mWork; }          // vqhip_cacao_plane_offset_bytes addresses the intermediates
+private:
+    void* mWork = nullptr; size_t mWorkBytes = 0;
+    unsigned mWidth = 0, mHeight = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // Reflection denoiser, pass 1 == the "FFX DNSR Reproject" dispatch of ScreenSpaceReflectionsPass::RecordCommands: vqhip_ssr_reproject. Buffer roles as
 // ScreenSpaceReflections.cpp:1177-1198 binds them for frame index i: reads the surfaces of this frame and their history copies, TexRadiance[i] (what the march
 // wrote), TexRadiance[1 - i] (last frame's resolved radiance), the motion vectors, TexVariance[1 - i] and TexSampleCount[1 - i]; writes TexReprojectedRadiance,

@@ -206,6 +206,24 @@ class SSSRConstants(C.Structure):  # VQ_SSSRConstants == FFX_SSSRConstants (Scre
         ("pad_", C.c_uint32)]
 
 
+class CacaoConstants(C.Structure):  # VQ_CacaoConstants == FFX_CACAO_Constants (AMDFidelityFX/CACAO/ffx_cacao.h:95-154)
+    _fields_ = [(k, C.c_float * 2) for k in ("DepthUnpackConsts", "CameraTanHalfFOV", "NDCToViewMul", "NDCToViewAdd", "DepthBufferUVToViewMul", "DepthBufferUVToViewAdd")] + [
+        (k, C.c_float) for k in ("EffectRadius", "EffectShadowStrength", "EffectShadowPow", "EffectShadowClamp", "EffectFadeOutMul", "EffectFadeOutAdd",
+                                 "EffectHorizonAngleThreshold", "EffectSamplingRadiusNearLimitRec", "DepthPrecisionOffsetMod", "NegRecEffectRadius", "LoadCounterAvgDiv",
+                                 "AdaptiveSampleCountLimit", "InvSharpness")] + [
+        ("PassIndex", C.c_int32), ("BilateralSigmaSquared", C.c_float), ("BilateralSimilarityDistanceSigma", C.c_float),
+        ("PatternRotScaleMatrices", (C.c_float * 4) * 5),
+        ("NormalsUnpackMul", C.c_float), ("NormalsUnpackAdd", C.c_float), ("DetailAOStrength", C.c_float), ("Dummy0", C.c_float),
+        ("SSAOBufferDimensions", C.c_float * 2), ("SSAOBufferInverseDimensions", C.c_float * 2),
+        ("DepthBufferDimensions", C.c_float * 2), ("DepthBufferInverseDimensions", C.c_float * 2),
+        ("DepthBufferOffset", C.c_int32 * 2), ("PerPassFullResUVOffset", C.c_float * 2),
+        ("InputOutputBufferDimensions", C.c_float * 2), ("InputOutputBufferInverseDimensions", C.c_float * 2),
+        ("ImportanceMapDimensions", C.c_float * 2), ("ImportanceMapInverseDimensions", C.c_float * 2),
+        ("DeinterleavedDepthBufferDimensions", C.c_float * 2), ("DeinterleavedDepthBufferInverseDimensions", C.c_float * 2),
+        ("DeinterleavedDepthBufferOffset", C.c_float * 2), ("DeinterleavedDepthBufferNormalisedOffset", C.c_float * 2),
+        ("NormalsWorldToViewspaceMatrix", matrix)]
+
+
 def _chk(t, size, **offs):
     assert C.sizeof(t) == size, (t.__name__, C.sizeof(t), size)
     for k, v in offs.items():
@@ -230,6 +248,8 @@ _chk(MSAASurfaces, 176, coverage=8, normals=40, roughness=72, background=104, no
 _chk(TonemapperParams, 16)
 _chk(BlurParams, 8)
 _chk(SSSRConstants, 512, bufferDimensions=448, roughnessThreshold=472, envMapSpecularIrradianceCubemapMipLevelCount=504)
+_chk(CacaoConstants, 384, EffectRadius=48, InvSharpness=96, PassIndex=100, PatternRotScaleMatrices=112, NormalsUnpackMul=192, SSAOBufferDimensions=208,
+     DepthBufferOffset=240, PerPassFullResUVOffset=248, DeinterleavedDepthBufferNormalisedOffset=312, NormalsWorldToViewspaceMatrix=320)
 
 
 def mip_level_count(w, h):
@@ -282,3 +302,16 @@ def unpack_ray_coords(packed):
     """UnpackRayCoords (Common.hlsl:73-79): (x, y, copy_horizontal, copy_vertical, copy_diagonal)"""
     packed = int(packed)
     return packed & 0x7FFF, (packed >> 15) & 0x3FFF, bool((packed >> 29) & 1), bool((packed >> 30) & 1), bool((packed >> 31) & 1)
+
+
+# ---- vqhip_cacao (docs/DESIGN_DETAILS.md §7.14) -------------------------------------------------------------------------------------------------
+CACAO_QUALITY_LOWEST, CACAO_QUALITY_LOW, CACAO_QUALITY_MEDIUM, CACAO_QUALITY_HIGH, CACAO_QUALITY_HIGHEST = 0, 1, 2, 3, 4   # FFX_CACAO_Quality
+CACAO_PLANE_DEPTHS, CACAO_PLANE_NORMALS, CACAO_PLANE_PING, CACAO_PLANE_PONG = 0, 1, 2, 3
+CACAO_DEPTH_MIPS = 4                    # SSAO_DEPTH_MIP_LEVELS
+CACAO_MAX_BLUR_PASSES = 8
+CACAO_MAX_DIM = 16384                   # above: VQHIP_ERR_UNSUPPORTED
+
+
+def cacao_half_dims(w, h):
+    """(hw, hh) of the deinterleaved buffers of a w x h frame (FFX_CACAO_UpdateBufferSizeInfo: (w + 1) / 2)"""
+    return (w + 1) // 2, (h + 1) // 2

@@ -104,6 +104,9 @@ def load_library():
         "vqhip_ssr_resolve_temporal": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, i32, vp, i32, C.POINTER(abi.SSSRConstants),
                                              vp, i32, i32, vp, i32]),
         "vqhip_ssr_reproject": (i32, [vp, vp, C.POINTER(abi.SSRReprojectSurfaces), C.POINTER(abi.SSSRConstants)]),
+        "vqhip_cacao_work_bytes": (sz, [i32, i32]),
+        "vqhip_cacao_plane_offset_bytes": (sz, [i32, i32, i32, i32, i32]),
+        "vqhip_cacao": (i32, [vp, vp, vp, sz, vp, i32, sz, C.POINTER(abi.CacaoConstants), C.POINTER(abi.CacaoConstants), i32, i32, vp, sz, vp, sz, i32, i32]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -136,7 +139,34 @@ EXPORTED_SYMBOLS = [
     "vqhip_composite_tiles", "vqhip_forward_lighting_msaa",
     "vqhip_msaa_resolve_surfaces", "vqhip_depth_hierarchy", "vqhip_depth_hierarchy_bytes", "vqhip_depth_hierarchy_level_offset_bytes",
     "vqhip_ssr_classify", "vqhip_ssr_intersect", "vqhip_ssr_prefilter", "vqhip_ssr_resolve_temporal", "vqhip_ssr_reproject",
+    "vqhip_cacao", "vqhip_cacao_work_bytes", "vqhip_cacao_plane_offset_bytes",
 ]
+
+
+def cacao_work_bytes(width, height):
+    """vqhip_cacao_work_bytes: the size of vqhip_cacao's work buffer for a width x height frame. Host-only."""
+    return load_library().vqhip_cacao_work_bytes(width, height)
+
+
+def cacao_plane_offset_bytes(width, height, plane, slice_index=0, mip=0):
+    """vqhip_cacao_plane_offset_bytes: where slice `slice_index` of abi.CACAO_PLANE_* (mip `mip` of the depths) starts inside the work buffer. Host-only."""
+    return load_library().vqhip_cacao_plane_offset_bytes(width, height, plane, slice_index, mip)
+
+
+def cacao_work_planes(work, width, height):
+    """Views of every intermediate of vqhip_cacao inside its work buffer (a uint8 tensor or numpy array of cacao_work_bytes bytes): dict with `depths` (four
+    float16 [4, rows, cols] mips), `normals` int8 [4, hh, hw, 4], `ping` / `pong` uint8 [4, hh, hw, 2]"""
+    hw, hh = abi.cacao_half_dims(width, height)
+    f16, i8 = (torch.float16, torch.int8) if hasattr(work, "is_cuda") else ("float16", "int8")
+
+    def view(plane, mip, rows, cols, ch, dtype, size):
+        off = cacao_plane_offset_bytes(width, height, plane, 0, mip)
+        v = work[off:off + 4 * rows * cols * ch * size]
+        v = v.view(dtype) if dtype is not None else v
+        return v.reshape((4, rows, cols) + ((ch,) if ch > 1 else ()))
+    depths = [view(abi.CACAO_PLANE_DEPTHS, k, abi.mip_dim(hh, k), abi.mip_dim(hw, k), 1, f16, 2) for k in range(abi.CACAO_DEPTH_MIPS)]
+    return {"depths": depths, "normals": view(abi.CACAO_PLANE_NORMALS, 0, hh, hw, 4, i8, 1), "ping": view(abi.CACAO_PLANE_PING, 0, hh, hw, 2, None, 1),
+            "pong": view(abi.CACAO_PLANE_PONG, 0, hh, hw, 2, None, 1)}
 
 
 def fsr_easu_con(in_w, in_h, out_w, out_h, container_w=None, container_h=None):
@@ -420,6 +450,33 @@ class Context:
         flat = self._hierarchy_buffer(w, h)
         self._ck(self.lib.vqhip_depth_hierarchy(self._h, self._stream(stream), _ptr(depth), depth.stride(0), w, h, _ptr(flat), int(flags)))
         return self._hierarchy_views(flat, w, h)
+
+    # ---- FidelityFX CACAO (RenderAmbientOcclusion, SceneRendering.cpp:1503-1555) -----------------------------------------------------------
+    def cacao(self, depth, normals, normal_fmt, shared, per_pass, quality=abi.CACAO_QUALITY_HIGH, blur_passes=2, work=None, out=None, stream=None):
+        """vqhip_cacao: depth float32 cuda [H,W] (rows may be strided); normals int32 [H,W] (R10G10B10A2_UNORM words) or float32 [H,W,4], rows may be strided;
+        shared / per_pass: abi.CacaoConstants and an array of four (vqengine_amd.cacao.constants). work: a cuda uint8 tensor of cacao_work_bytes bytes (allocated
+        when None); out: uint8 [H,W], rows may be strided. Returns (ao, work): the R8_UNORM plane that forward lighting takes as texScreenSpaceAO, and the work
+        buffer (cacao_work_planes views its intermediates)."""
+        if not (depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 2 and depth.stride(1) == 1):
+            raise ValueError(f"cacao: depth: expected cuda float32 [H,W] with unit column stride, got {tuple(depth.shape)} {depth.dtype} strides {depth.stride()}")
+        h, w = depth.shape
+        if normal_fmt == abi.FMT_RGBA32F:
+            ok = normals.dtype == torch.float32 and tuple(normals.shape) == (h, w, 4) and normals.stride(2) == 1 and normals.stride(1) == 4
+        else:
+            ok = normals.dtype == torch.int32 and tuple(normals.shape) == (h, w) and normals.stride(1) == 1
+        if not (ok and normals.is_cuda):
+            raise ValueError("cacao: normals: expected cuda int32 [H,W] (R10G10B10A2_UNORM words) or float32 [H,W,4] with dense pixels")
+        if work is None:
+            work = torch.empty((cacao_work_bytes(w, h),), dtype=torch.uint8, device=self.device)
+        if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
+            raise ValueError("cacao: work: expected a contiguous cuda uint8 tensor")
+        if out is None:
+            out = torch.empty((h, w), dtype=torch.uint8, device=self.device)
+        if not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (h, w) and out.stride(1) == 1):
+            raise ValueError(f"cacao: out: expected cuda uint8 {(h, w)} with unit column stride")
+        self._ck(self.lib.vqhip_cacao(self._h, self._stream(stream), _ptr(depth), depth.stride(0) * 4, _ptr(normals), normal_fmt, normals.stride(0) * normals.element_size(),
+                                      C.byref(shared), per_pass, int(quality), int(blur_passes), _ptr(work), work.numel(), _ptr(out), out.stride(0), w, h))
+        return out, work
 
     def msaa_resolve_surfaces(self, depth_ms, coverage=None, normals=None, normals_fmt=abi.FMT_R10G10B10A2_UNORM, roughness=None, background=None,
                               out_depth=False, out_normals_fmt=None, scene_color=None, scene_fmt=FMT_RGBA16F, hierarchy=False, flags=0, stream=None):

@@ -1613,4 +1613,96 @@ int vqhip_envmap_prefilter(vqhip_ctx* ctx, void* stream, const void* equirect_mi
     return vqhip_conv_specular(ctx, stream, equirect_mips, w0, h0, nMips, specRes0, order, out->specular, VQHIP_FMT_RGBA16F);             // :386-472
 }
 
+// ---- FidelityFX CACAO at quality HIGH (cacao.hip; docs/DESIGN_DETAILS.md §7.14) ------------------------------------------------------------------
+namespace {
+struct CacaoLayout { size_t depth[4], normals, ping, pong, total; int hw, hh, mw[4], mh[4]; };
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+bool cacaoLayout(int W, int H, CacaoLayout* L) {
+    if (W <= 0 || H <= 0 || W > VQHIP_CACAO_MAX_DIM || H > VQHIP_CACAO_MAX_DIM) return false;
+    L->hw = (W + 1) / 2; L->hh = (H + 1) / 2;
+    size_t off = 0;
+    for (int k = 0; k < 4; ++k) {
+        L->mw[k] = mipDim(L->hw, k); L->mh[k] = mipDim(L->hh, k);
+        L->depth[k] = off;
+        off = align256(off + (size_t)4 * L->mw[k] * L->mh[k] * 2);
+    }
+    const size_t texels = (size_t)4 * L->hw * L->hh;
+    L->normals = off; off = align256(off + texels * 4);
+    L->ping = off;    off = align256(off + texels * 2);
+    L->pong = off;    off = align256(off + texels * 2);
+    L->total = off;
+    return true;
+}
+} // namespace
+
+size_t vqhip_cacao_work_bytes(int width, int height) {
+    CacaoLayout L;
+    return cacaoLayout(width, height, &L) ? L.total : 0;
+}
+size_t vqhip_cacao_plane_offset_bytes(int width, int height, int plane, int slice, int mip) {
+    CacaoLayout L;
+    if (!cacaoLayout(width, height, &L) || slice < 0 || slice > 3 || mip < 0 || mip > 3 || (plane != VQHIP_CACAO_PLANE_DEPTHS && mip != 0)) return 0;
+    const size_t texels = (size_t)L.hw * L.hh;
+    switch (plane) {
+        case VQHIP_CACAO_PLANE_DEPTHS:  return L.depth[mip] + (size_t)slice * L.mw[mip] * L.mh[mip] * 2;
+        case VQHIP_CACAO_PLANE_NORMALS: return L.normals + (size_t)slice * texels * 4;
+        case VQHIP_CACAO_PLANE_PING:    return L.ping + (size_t)slice * texels * 2;
+        case VQHIP_CACAO_PLANE_PONG:    return L.pong + (size_t)slice * texels * 2;
+        default: return 0;
+    }
+}
+
+int vqhip_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_t depthPitchBytes, const void* normals, int normalFmt, size_t normalPitchBytes,
+        const VQ_CacaoConstants* shared, const VQ_CacaoConstants perPass[4], int qualityLevel, int blurPassCount,
+        void* work, size_t workBytes, uint8_t* ao, size_t aoPitchBytes, int width, int height) {
+    vqk::Range range_("Ambient Occlusion (FidelityFX CACAO)");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "cacao: ctx is NULL");
+    CTX_GUARD(ctx, "cacao");
+    if (!depth || !normals || !shared || !perPass || !work || !ao) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: NULL argument");
+    if (width <= 0 || height <= 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: bad dimensions");
+    if (width > VQHIP_CACAO_MAX_DIM || height > VQHIP_CACAO_MAX_DIM) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: frames above 16384 in either dimension are not supported");
+    if (qualityLevel < VQHIP_CACAO_QUALITY_LOWEST || qualityLevel > VQHIP_CACAO_QUALITY_HIGHEST) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: qualityLevel is not an FFX_CACAO_Quality");
+    if (qualityLevel == VQHIP_CACAO_QUALITY_HIGHEST)
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: quality HIGHEST (the adaptive base pass, the importance map and the importance-driven tap loop) is not implemented; use HIGH");
+    if (qualityLevel != VQHIP_CACAO_QUALITY_HIGH) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: quality levels LOWEST, LOW and MEDIUM are not implemented; use HIGH");
+    if (normalFmt != VQHIP_FMT_R10G10B10A2_UNORM && normalFmt != VQHIP_FMT_RGBA32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: normals must be R10G10B10A2_UNORM or RGBA32F");
+    if (blurPassCount < 0 || blurPassCount > VQHIP_CACAO_MAX_BLUR_PASSES) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: blurPassCount must be 0..8");
+    const size_t normalPx = normalFmt == VQHIP_FMT_RGBA32F ? 16 : 4;
+    if (depthPitchBytes < (size_t)width * 4 || depthPitchBytes % 4) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: depthPitchBytes below 4 * width or not a multiple of 4");
+    if (normalPitchBytes < (size_t)width * normalPx || normalPitchBytes % normalPx) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: normalPitchBytes below the row size or not a multiple of the pixel size");
+    if (aoPitchBytes < (size_t)width) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: aoPitchBytes below the width");
+    if (depthPitchBytes / 4 > 0x7fffffffu || normalPitchBytes / normalPx > 0x7fffffffu || aoPitchBytes > 0x7fffffffu) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: pitch too large");
+    CacaoLayout L;
+    cacaoLayout(width, height, &L);
+    if (workBytes < L.total) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: workBytes below vqhip_cacao_work_bytes(width, height)");
+    if ((uintptr_t)work % 256) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: work must be 256-byte aligned");
+    // the constants must describe THIS frame: the kernels address by the integer sizes and compute with the blocks' floats
+    auto sizesMatch = [&](const VQ_CacaoConstants& c) {
+        return c.SSAOBufferDimensions[0] == (float)L.hw && c.SSAOBufferDimensions[1] == (float)L.hh && c.DepthBufferDimensions[0] == (float)width &&
+               c.DepthBufferDimensions[1] == (float)height && c.InputOutputBufferDimensions[0] == (float)width && c.InputOutputBufferDimensions[1] == (float)height &&
+               c.DeinterleavedDepthBufferDimensions[0] == (float)L.hw && c.DeinterleavedDepthBufferDimensions[1] == (float)L.hh;
+    };
+    if (!sizesMatch(*shared)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: the shared constants are not those of this frame size at native resolution (FFX_CACAO_UpdateBufferSizeInfo(width, height, false))");
+    for (int i = 0; i < 4; ++i) {
+        if (!sizesMatch(perPass[i])) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: a per-pass constants block is not of this frame size at native resolution");
+        if (perPass[i].PassIndex != i) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: perPass[i].PassIndex must be i");
+    }
+    const size_t depthBytes = (size_t)(height - 1) * depthPitchBytes + (size_t)width * 4, normalBytes = (size_t)(height - 1) * normalPitchBytes + (size_t)width * normalPx;
+    const size_t aoBytes = (size_t)(height - 1) * aoPitchBytes + (size_t)width;
+    if (rangesOverlap(work, L.total, depth, depthBytes) || rangesOverlap(work, L.total, normals, normalBytes) || rangesOverlap(work, L.total, ao, aoBytes) ||
+        rangesOverlap(ao, aoBytes, depth, depthBytes) || rangesOverlap(ao, aoBytes, normals, normalBytes))
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: work and ao must not overlap each other or the inputs");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    CacaoArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.depth = depth; a.normals = normals; a.work = (uint8_t*)work; a.ao = ao;
+    for (int k = 0; k < 4; ++k) { a.offDepth[k] = L.depth[k]; a.mw[k] = L.mw[k]; a.mh[k] = L.mh[k]; }
+    a.offNormals = L.normals; a.offPing = L.ping; a.offPong = L.pong;
+    a.width = width; a.height = height; a.hw = L.hw; a.hh = L.hh;
+    a.depthPitch = (int)(depthPitchBytes / 4); a.normalPitch = (int)(normalPitchBytes / normalPx); a.aoPitch = (int)aoPitchBytes;
+    a.normF32 = normalFmt == VQHIP_FMT_RGBA32F; a.blurPasses = blurPassCount;
+    hipError_t e = launch_cacao((hipStream_t)stream, a, *shared, perPass);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "cacao launch");
+}
+
 } // extern "C"

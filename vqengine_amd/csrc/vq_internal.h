@@ -236,6 +236,16 @@ struct HierArgs {
 hipError_t launch_resolve_surfaces(hipStream_t s, const SurfArgs& a);
 hipError_t launch_depth_hierarchy(hipStream_t s, const HierArgs& a, bool ms);
 
+// FidelityFX CACAO at quality HIGH (vqhip_cacao, cacao.hip; docs/DESIGN_DETAILS.md §7.14). depthPitch in floats, normalPitch in pixels, aoPitch in bytes;
+// off*: byte offsets of the planes inside the work buffer (vqhip_cacao_plane_offset_bytes), mw / mh: the sizes of the four depth mips.
+struct CacaoArgs {
+    const float* depth; const void* normals; uint8_t* work; uint8_t* ao;
+    size_t offDepth[4], offNormals, offPing, offPong;
+    int mw[4], mh[4];
+    int width, height, hw, hh, depthPitch, normalPitch, aoPitch, normF32, blurPasses;
+};
+hipError_t launch_cacao(hipStream_t s, const CacaoArgs& a, const VQ_CacaoConstants& shared, const VQ_CacaoConstants perPass[4]);
+
 // launchers (each returns the hipError_t of the launch)
 hipError_t launch_forward_lighting(hipStream_t s, const ShadeArgs& a, bool hasEnv, bool hasCasters, int outFmt, const Options& opt);
 hipError_t launch_blur_x(hipStream_t s, const void* in, void* out, int W, int H, int fmt, const Options& opt);

@@ -799,3 +799,36 @@ def ssr_motion_vectors(depth, cb):
     world /= world[..., 3:]
     prev = world @ _matrix_of(cb.prevViewProjection)
     return (ndc[..., :2] - prev[..., :2] / prev[..., 3:]).astype(np.float32)
+
+
+# ---- FidelityFX CACAO (docs/DESIGN_DETAILS.md §7.14): the inputs of vqhip_cacao -----------------------------------------------------------------
+CACAO_ROOM_CAMERA = {"camera": (-44.5, 0.6, -89.0), "look_at": (44.0, 6.0, 10.0)}   # in a corner of the room, low above the floor: view depths from ~1 to ~150
+
+
+def cacao_room(width, height, **constants):
+    """ssr_room seen by a camera close to the floor (CACAO_ROOM_CAMERA unless `constants` names another), as vqhip_cacao's inputs. Near pixels get sampling discs of
+    more than a hundred half-resolution texels (depth mips 2 and 3), far ones a few texels (mip 0); box and wall silhouettes and the floor and the side wall at grazing
+    angles give depth edges, creases normal edges (tests/test_cacao_cpu.py pins the shares at 1280 x 720).
+    Returns a dict: depth float32 [H,W] (NDC z, the resolved scene depth), packed uint32 [H,W] / n01 float32 [H,W,4] (world-space normals as Tex_SceneNormals holds them,
+    R10G10B10A2_UNORM and its decoded values), proj / normals_to_view float32 [4,4] as VQRenderer::RenderAmbientOcclusion stores them (SceneRendering.cpp:1525-1526:
+    SceneView.proj and SceneView.view, row-major, row-vector convention)."""
+    args = dict(CACAO_ROOM_CAMERA)
+    args.update(constants)
+    room = ssr_room(width, height, **args)
+    return {"depth": room["depth"], "packed": room["packed"], "n01": room["n01"], "proj": _matrix_of(room["cb"].projection).astype(np.float32),
+            "normals_to_view": _matrix_of(room["cb"].view).astype(np.float32)}
+
+
+def cacao_noise(width, height, seed=0xCAC0):
+    """White-noise inputs of vqhip_cacao with the camera of cacao_room: NDC depths whose view-space values are log-uniform in [0.15, 100] (neighbouring texels differ by
+    factors: every depth edge closes, taps land on unrelated depths, and with a radius scaled to the frame size every mip is selected), unit normals on the whole sphere. Same dict as cacao_room."""
+    cb = ssr_constants(width, height, 1, **CACAO_ROOM_CAMERA)
+    room = {"proj": _matrix_of(cb.projection).astype(np.float32), "normals_to_view": _matrix_of(cb.view).astype(np.float32)}
+    r = _chunk_rng(seed, 0)
+    z = 0.15 * np.exp(r.random((height, width)) * np.log(100.0 / 0.15))
+    p = room["proj"].astype(np.float64)
+    depth = (p[2, 2] + p[3, 2] / z).astype(np.float32)                               # NDC z of view depth z
+    n = r.normal(size=(height, width, 3))
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    packed, n01 = _pack_normals(n)
+    return {"depth": depth, "packed": packed, "n01": n01, "proj": room["proj"], "normals_to_view": room["normals_to_view"]}
