@@ -346,7 +346,7 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * vqhip_composite_reflections; vqhip_visualize reads R10G10B10A2 / RG16F / RG32F inputs.
                                * Later additions to 3: vqhip_gbuffer_msaa, vqhip_forward_lighting_msaa; vqhip_msaa_surfaces, vqhip_msaa_resolve_surfaces, vqhip_depth_hierarchy (+ _bytes, _level_offset_bytes);
                                * vqhip_ssr_classify, vqhip_ssr_intersect; vqhip_ssr_prefilter, vqhip_ssr_resolve_temporal, VQHIP_FMT_R11G11B10_FLOAT; vqhip_ssr_reproject, vqhip_ssr_reproject_surfaces;
-                               * VQ_CacaoConstants, vqhip_cacao (+ _work_bytes, _plane_offset_bytes) */
+                               * VQ_CacaoConstants, vqhip_cacao (+ _work_bytes, _plane_offset_bytes); vqhip_adaptive_cacao (+ _work_bytes, _plane_offset_bytes) and three plane ids */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -1004,8 +1004,8 @@ VQHIP_API int  vqhip_composite_tiles(vqhip_comm* comm, void* stream, const void*
  * Writes Tex_AmbientOcclusion (R8_UNORM), the texScreenSpaceAO of the lit draw, from Tex_SceneDepthResolve (R32F) and Tex_SceneNormals at native resolution:
  *   CSPrepareNativeDepthsAndMips -> CSPrepareNativeNormalsFromInputNormals -> CSGenerateQ2 x 4 passes -> CSEdgeSensitiveBlur<blurPassCount> x 4 -> CSApply,
  * five kernels on `stream` (the four passes of a stage are ONE launch), no host synchronisation, no allocation: every intermediate lives in `work`.
- * Implemented: quality HIGH (FFX_CACAO_QUALITY_HIGH), useDownsampledSsao off, generateNormals off. HIGHEST (the adaptive stage on top of this pipeline), the lower
- * levels, the downsampled path and normal generation return VQHIP_ERR_UNSUPPORTED.
+ * Implemented: quality HIGH (FFX_CACAO_QUALITY_HIGH) here and HIGHEST, the adaptive stage on top of this pipeline, as vqhip_adaptive_cacao below; useDownsampledSsao
+ * off, generateNormals off. The lower levels, the downsampled path and normal generation return VQHIP_ERR_UNSUPPORTED, and so does HIGHEST passed to vqhip_cacao.
  * VQ_CacaoConstants == FFX_CACAO_Constants (ffx_cacao.h:95-154): the engine keeps calling FFX_CACAO_UpdateBufferSizeInfo / _UpdateConstants /
  * _UpdatePerPassConstants (ffx_cacao.cpp:48-262) and hands the shared block and the four per-pass blocks over as FFX_CACAO_D3D12Draw uploads them. */
 typedef struct VQ_CacaoConstants {
@@ -1034,7 +1034,11 @@ typedef enum vqhip_cacao_plane {
     VQHIP_CACAO_PLANE_DEPTHS = 0,    /* deinterleaved view-space depths, R16F: slice 0..3, mip 0..3; mip k is max(1, hw >> k) x max(1, hh >> k) */
     VQHIP_CACAO_PLANE_NORMALS = 1,   /* deinterleaved view-space normals, R8G8B8A8_SNORM: slice 0..3, hw x hh */
     VQHIP_CACAO_PLANE_PING = 2,      /* (occlusion, packed edges), R8G8_UNORM, as CSGenerateQ2 wrote them: slice 0..3, hw x hh */
-    VQHIP_CACAO_PLANE_PONG = 3       /* the same after the edge-sensitive blur (not written when blurPassCount == 0) */
+    VQHIP_CACAO_PLANE_PONG = 3,      /* the same after the edge-sensitive blur (not written when blurPassCount == 0) */
+    /* vqhip_adaptive_cacao only (below): iw = (hw + 1) / 2, ih = (hh + 1) / 2; slice 0, mip 0 */
+    VQHIP_CACAO_PLANE_IMPORTANCE = 4,        /* the importance map after CSPostprocessImportanceMapB, R8_UNORM, iw x ih, dense rows */
+    VQHIP_CACAO_PLANE_IMPORTANCE_PONG = 5,   /* the map after CSPostprocessImportanceMapA, the same shape */
+    VQHIP_CACAO_PLANE_LOAD_COUNTER = 6       /* one uint32: the sum CSPostprocessImportanceMapB's InterlockedAdd left */
 } vqhip_cacao_plane;
 #define VQHIP_CACAO_MAX_DIM 16384
 #define VQHIP_CACAO_MAX_BLUR_PASSES 8
@@ -1053,6 +1057,26 @@ VQHIP_API size_t vqhip_cacao_plane_offset_bytes(int width, int height, int plane
  * VQHIP_ERR_UNSUPPORTED for another quality level, normal format or a frame above VQHIP_CACAO_MAX_DIM — without launching anything. */
 VQHIP_API int vqhip_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_t depthPitchBytes, const void* normals, int normalFmt, size_t normalPitchBytes,
         const VQ_CacaoConstants* shared, const VQ_CacaoConstants perPass[4], int qualityLevel, int blurPassCount,
+        void* work, size_t workBytes, uint8_t* ao, size_t aoPitchBytes, int width, int height);
+
+/* ---- Quality HIGHEST, FFX_CACAO_DEFAULT_SETTINGS' own level (ffx_cacao.h:72-90; AmbientOcclusion.cpp:38 constructs the pass from them): the pipeline above with
+ * an adaptive stage in place of CSGenerateQ2 (FFX_CACAO_D3D12Draw, ffx_cacao_impl.cpp:1950-2150). docs/DESIGN_DETAILS.md §7.15; tests/cacao_adaptive_ref.py states
+ * it in numpy.
+ *   prepare depths, prepare normals (as above) -> CSGenerateQ3Base x 4 (5 taps; (obscurance, weight / 20) into the PONG slices) -> CSGenerateImportanceMap ->
+ *   CSPostprocessImportanceMapA -> CSPostprocessImportanceMapB (+ the load counter) -> CSGenerateQ3 x 4 (1 .. 27 more taps per texel, by importance; into PING) ->
+ *   CSEdgeSensitiveBlur<blurPassCount> x 4 -> CSApply,
+ * ten kernels on `stream` (nine when blurPassCount == 0), no host synchronisation, no allocation, no memset: a lane of the first importance kernel clears the counter.
+ * It is an entry point of its own because its work buffer is larger: HIGH's layout is the prefix (the same offsets for DEPTHS, NORMALS, PING and PONG), and three
+ * planes follow, each on a 256-byte boundary: VQHIP_CACAO_PLANE_IMPORTANCE, _IMPORTANCE_PONG and _LOAD_COUNTER; iw x ih are the constants' ImportanceMapDimensions. */
+/* After a call with blurPassCount == 0 the PONG slices hold the base pass's output (R8G8_UNORM: obscurance, weight / 20); with a blur they hold the blurred planes,
+ * as at HIGH (the blur overwrites the base values, as it does in the source). PING holds CSGenerateQ3's output either way.
+ * _plane_offset_bytes takes the seven plane ids; slice and mip must be 0 for the three new ones. Both size functions return 0 for arguments out of range. Host-only. */
+VQHIP_API size_t vqhip_adaptive_cacao_work_bytes(int width, int height);
+VQHIP_API size_t vqhip_adaptive_cacao_plane_offset_bytes(int width, int height, int plane, int slice, int mip);
+/* Arguments and refusals as vqhip_cacao's, without qualityLevel; work is vqhip_adaptive_cacao_work_bytes(width, height) bytes, and the constants'
+ * ImportanceMapDimensions must be (iw, ih) too. The blocks' LoadCounterAvgDiv and AdaptiveSampleCountLimit (settings.adaptiveQualityLimit) are used as handed over. */
+VQHIP_API int vqhip_adaptive_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_t depthPitchBytes, const void* normals, int normalFmt, size_t normalPitchBytes,
+        const VQ_CacaoConstants* shared, const VQ_CacaoConstants perPass[4], int blurPassCount,
         void* work, size_t workBytes, uint8_t* ao, size_t aoPitchBytes, int width, int height);
 
 #ifdef __cplusplus

@@ -455,6 +455,40 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// Ambient occlusion at FFX_CACAO_DEFAULT_SETTINGS' own quality, HIGHEST — what AmbientOcclusionPass's constructor sets (AmbientOcclusion.cpp:38):
+// vqhip_adaptive_cacao. The same parameters and the same roles as AmbientOcclusionPass above; the work buffer is the larger one of
+// vqhip_adaptive_cacao_work_bytes (HIGH's layout, then the importance map, its pong and the load counter). The constants come from FidelityFX's own functions with
+// settings.qualityLevel = FFX_CACAO_QUALITY_HIGHEST: LoadCounterAvgDiv, AdaptiveSampleCountLimit and ImportanceMapDimensions are read here.
+// ---------------------------------------------------------------------------------------------------------------
+class AdaptiveAmbientOcclusionPass : public RenderPassBase {
+public:
+    using FResourceParameters = AmbientOcclusionPass::FResourceParameters;
+    using FDrawParameters = AmbientOcclusionPass::FDrawParameters;
+    explicit AdaptiveAmbientOcclusionPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    ~AdaptiveAmbientOcclusionPass() override { OnDestroyWindowSizeDependentResources(); }
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { OnDestroyWindowSizeDependentResources(); }
+    void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override {
+        OnDestroyWindowSizeDependentResources();
+        mWidth = Width; mHeight = Height;
+        mWorkBytes = vqhip_adaptive_cacao_work_bytes((int)Width, (int)Height);
+        mWork = mWorkBytes ? Alloc(mWorkBytes) : nullptr;
+    }
+    void OnDestroyWindowSizeDependentResources() override { Free(mWork); mWorkBytes = 0; mWidth = mHeight = 0; }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p || !mWork) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        mStatus = vqhip_adaptive_cacao(mCtx, p->Stream, p->TexSceneDepthResolve, (size_t)mWidth * 4, p->TexSceneNormals, VQHIP_FMT_R10G10B10A2_UNORM, (size_t)mWidth * 4,
+                                       &p->Constants, p->PerPassConstants, p->BlurPassCount, mWork, mWorkBytes, p->TexAmbientOcclusion,
+                                       (size_t)mWidth, (int)mWidth, (int)mHeight);
+    }
+    const void* GetWorkBuffer() const { return mWork; }          // vqhip_adaptive_cacao_plane_offset_bytes addresses the intermediates
+private:
+    void* mWork = nullptr; size_t mWorkBytes = 0;
+    unsigned mWidth = 0, mHeight = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // Reflection denoiser, pass 1 == the "FFX DNSR Reproject" dispatch of ScreenSpaceReflectionsPass::RecordCommands: vqhip_ssr_reproject. Buffer roles as
 // ScreenSpaceReflections.cpp:1177-1198 binds them for frame index i: reads the surfaces of this frame and their history copies, TexRadiance[i] (what the march
 // wrote), TexRadiance[1 - i] (last frame's resolved radiance), the motion vectors, TexVariance[1 - i] and TexSampleCount[1 - i]; writes TexReprojectedRadiance,

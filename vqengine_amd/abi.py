@@ -307,6 +307,7 @@ def unpack_ray_coords(packed):
 # ---- vqhip_cacao (docs/DESIGN_DETAILS.md §7.14) -------------------------------------------------------------------------------------------------
 CACAO_QUALITY_LOWEST, CACAO_QUALITY_LOW, CACAO_QUALITY_MEDIUM, CACAO_QUALITY_HIGH, CACAO_QUALITY_HIGHEST = 0, 1, 2, 3, 4   # FFX_CACAO_Quality
 CACAO_PLANE_DEPTHS, CACAO_PLANE_NORMALS, CACAO_PLANE_PING, CACAO_PLANE_PONG = 0, 1, 2, 3
+CACAO_PLANE_IMPORTANCE, CACAO_PLANE_IMPORTANCE_PONG, CACAO_PLANE_LOAD_COUNTER = 4, 5, 6   # vqhip_adaptive_cacao only (§7.15)
 CACAO_DEPTH_MIPS = 4                    # SSAO_DEPTH_MIP_LEVELS
 CACAO_MAX_BLUR_PASSES = 8
 CACAO_MAX_DIM = 16384                   # above: VQHIP_ERR_UNSUPPORTED

@@ -1,6 +1,6 @@
 """Host mirror of FidelityFX CACAO's constant setup (AMDFidelityFX/CACAO/ffx_cacao.h:72-90, ffx_cacao.cpp:48-262): FFX_CACAO_DEFAULT_SETTINGS,
 FFX_CACAO_UpdateBufferSizeInfo, FFX_CACAO_UpdateConstants and FFX_CACAO_UpdatePerPassConstants, operation by operation in binary32. The engine keeps calling
-FidelityFX's own functions and hands the five blocks to vqhip_cacao; this mirror exists for callers that have no FidelityFX at hand (the tests, the benchmark
+FidelityFX's own functions and hands the five blocks to vqhip_cacao or vqhip_adaptive_cacao; this mirror exists for callers that have no FidelityFX at hand (the tests, the benchmark
 script). tests/test_cacao_cpu.py pins it to the output of the reference's own C++ (tests/golden/cacao_constants.json). Pure numpy; importable without a GPU."""
 import numpy as np
 
@@ -8,7 +8,7 @@ from . import abi
 
 F = np.float32
 
-# FFX_CACAO_DEFAULT_SETTINGS (ffx_cacao.h:72-90). qualityLevel there is HIGHEST; vqhip_cacao implements HIGH (docs/DESIGN_DETAILS.md §7.14).
+# FFX_CACAO_DEFAULT_SETTINGS (ffx_cacao.h:72-90). qualityLevel there is HIGHEST: vqhip_adaptive_cacao (docs/DESIGN_DETAILS.md §7.15); vqhip_cacao runs HIGH (§7.14).
 DEFAULT_SETTINGS = {
     "radius": 1.2, "shadowMultiplier": 1.0, "shadowPower": 1.50, "shadowClamp": 0.98, "horizonAngleThreshold": 0.06, "fadeOutFrom": 50.0, "fadeOutTo": 300.0,
     "qualityLevel": abi.CACAO_QUALITY_HIGHEST, "adaptiveQualityLimit": 0.45, "blurPassCount": 2, "sharpness": 0.98, "temporalSupersamplingAngleOffset": 0.0,
@@ -133,7 +133,8 @@ def update_per_pass_constants(consts, s, bsi, pass_index):
 
 def constants(width, height, proj, normals_to_view, s=None):
     """(shared, [4 per-pass blocks]) as FFX_CACAO_D3D12Draw uploads them (ffx_cacao_impl.cpp:1967-1978): every per-pass block is UpdateConstants +
-    UpdatePerPassConstants. s: a settings() dict (default: the defaults at quality HIGH)"""
+    UpdatePerPassConstants. s: a settings() dict; None: the defaults at quality HIGH, for vqhip_cacao. settings() itself, HIGHEST with adaptiveQualityLimit 0.45, is
+    what vqhip_adaptive_cacao takes: LoadCounterAvgDiv, AdaptiveSampleCountLimit and ImportanceMapDimensions are filled either way."""
     s = settings(qualityLevel=abi.CACAO_QUALITY_HIGH) if s is None else s
     bsi = buffer_size_info(width, height)
     shared = update_constants(abi.CacaoConstants(), s, bsi, proj, normals_to_view)

@@ -107,6 +107,9 @@ def load_library():
         "vqhip_cacao_work_bytes": (sz, [i32, i32]),
         "vqhip_cacao_plane_offset_bytes": (sz, [i32, i32, i32, i32, i32]),
         "vqhip_cacao": (i32, [vp, vp, vp, sz, vp, i32, sz, C.POINTER(abi.CacaoConstants), C.POINTER(abi.CacaoConstants), i32, i32, vp, sz, vp, sz, i32, i32]),
+        "vqhip_adaptive_cacao_work_bytes": (sz, [i32, i32]),
+        "vqhip_adaptive_cacao_plane_offset_bytes": (sz, [i32, i32, i32, i32, i32]),
+        "vqhip_adaptive_cacao": (i32, [vp, vp, vp, sz, vp, i32, sz, C.POINTER(abi.CacaoConstants), C.POINTER(abi.CacaoConstants), i32, vp, sz, vp, sz, i32, i32]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -140,6 +143,7 @@ EXPORTED_SYMBOLS = [
     "vqhip_msaa_resolve_surfaces", "vqhip_depth_hierarchy", "vqhip_depth_hierarchy_bytes", "vqhip_depth_hierarchy_level_offset_bytes",
     "vqhip_ssr_classify", "vqhip_ssr_intersect", "vqhip_ssr_prefilter", "vqhip_ssr_resolve_temporal", "vqhip_ssr_reproject",
     "vqhip_cacao", "vqhip_cacao_work_bytes", "vqhip_cacao_plane_offset_bytes",
+    "vqhip_adaptive_cacao", "vqhip_adaptive_cacao_work_bytes", "vqhip_adaptive_cacao_plane_offset_bytes",
 ]
 
 
@@ -167,6 +171,31 @@ def cacao_work_planes(work, width, height):
     depths = [view(abi.CACAO_PLANE_DEPTHS, k, abi.mip_dim(hh, k), abi.mip_dim(hw, k), 1, f16, 2) for k in range(abi.CACAO_DEPTH_MIPS)]
     return {"depths": depths, "normals": view(abi.CACAO_PLANE_NORMALS, 0, hh, hw, 4, i8, 1), "ping": view(abi.CACAO_PLANE_PING, 0, hh, hw, 2, None, 1),
             "pong": view(abi.CACAO_PLANE_PONG, 0, hh, hw, 2, None, 1)}
+
+
+def adaptive_cacao_work_bytes(width, height):
+    """vqhip_adaptive_cacao_work_bytes: the size of vqhip_adaptive_cacao's work buffer (quality HIGHEST) for a width x height frame. Host-only."""
+    return load_library().vqhip_adaptive_cacao_work_bytes(width, height)
+
+
+def adaptive_cacao_plane_offset_bytes(width, height, plane, slice_index=0, mip=0):
+    """vqhip_adaptive_cacao_plane_offset_bytes: as cacao_plane_offset_bytes for the four planes of HIGH's layout (the prefix), and where abi.CACAO_PLANE_IMPORTANCE,
+    _IMPORTANCE_PONG and _LOAD_COUNTER start (slice 0, mip 0). Host-only."""
+    return load_library().vqhip_adaptive_cacao_plane_offset_bytes(width, height, plane, slice_index, mip)
+
+
+def adaptive_cacao_work_planes(work, width, height):
+    """cacao_work_planes of vqhip_adaptive_cacao's work buffer plus `importance` / `importance_pong` uint8 [ih, iw] and `counter`, a view of one int32 (torch has no
+    uint32 arithmetic; a numpy buffer gives uint32). After a call with no blur `pong` is the base pass's (obscurance, weight / 20)."""
+    hw, hh = abi.cacao_half_dims(width, height)
+    iw, ih = abi.cacao_half_dims(hw, hh)
+    out = cacao_work_planes(work, width, height)
+    for key, plane in (("importance", abi.CACAO_PLANE_IMPORTANCE), ("importance_pong", abi.CACAO_PLANE_IMPORTANCE_PONG)):
+        off = adaptive_cacao_plane_offset_bytes(width, height, plane)
+        out[key] = work[off:off + iw * ih].reshape((ih, iw))
+    off = adaptive_cacao_plane_offset_bytes(width, height, abi.CACAO_PLANE_LOAD_COUNTER)
+    out["counter"] = work[off:off + 4].view(torch.int32 if hasattr(work, "is_cuda") else "uint32")
+    return out
 
 
 def fsr_easu_con(in_w, in_h, out_w, out_h, container_w=None, container_h=None):
@@ -476,6 +505,32 @@ class Context:
             raise ValueError(f"cacao: out: expected cuda uint8 {(h, w)} with unit column stride")
         self._ck(self.lib.vqhip_cacao(self._h, self._stream(stream), _ptr(depth), depth.stride(0) * 4, _ptr(normals), normal_fmt, normals.stride(0) * normals.element_size(),
                                       C.byref(shared), per_pass, int(quality), int(blur_passes), _ptr(work), work.numel(), _ptr(out), out.stride(0), w, h))
+        return out, work
+
+    def adaptive_cacao(self, depth, normals, normal_fmt, shared, per_pass, blur_passes=2, work=None, out=None, stream=None):
+        """vqhip_adaptive_cacao, quality HIGHEST: the arguments of cacao() without `quality`; shared / per_pass from vqengine_amd.cacao.constants with settings at
+        HIGHEST (its defaults). work: a cuda uint8 tensor of adaptive_cacao_work_bytes bytes (allocated when None). Returns (ao, work); adaptive_cacao_work_planes
+        views the intermediates, the importance map and the load counter included."""
+        if not (depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 2 and depth.stride(1) == 1):
+            raise ValueError(f"adaptive_cacao: depth: expected cuda float32 [H,W] with unit column stride, got {tuple(depth.shape)} {depth.dtype} strides {depth.stride()}")
+        h, w = depth.shape
+        if normal_fmt == abi.FMT_RGBA32F:
+            ok = normals.dtype == torch.float32 and tuple(normals.shape) == (h, w, 4) and normals.stride(2) == 1 and normals.stride(1) == 4
+        else:
+            ok = normals.dtype == torch.int32 and tuple(normals.shape) == (h, w) and normals.stride(1) == 1
+        if not (ok and normals.is_cuda):
+            raise ValueError("adaptive_cacao: normals: expected cuda int32 [H,W] (R10G10B10A2_UNORM words) or float32 [H,W,4] with dense pixels")
+        if work is None:
+            work = torch.empty((adaptive_cacao_work_bytes(w, h),), dtype=torch.uint8, device=self.device)
+        if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
+            raise ValueError("adaptive_cacao: work: expected a contiguous cuda uint8 tensor")
+        if out is None:
+            out = torch.empty((h, w), dtype=torch.uint8, device=self.device)
+        if not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (h, w) and out.stride(1) == 1):
+            raise ValueError(f"adaptive_cacao: out: expected cuda uint8 {(h, w)} with unit column stride")
+        self._ck(self.lib.vqhip_adaptive_cacao(self._h, self._stream(stream), _ptr(depth), depth.stride(0) * 4, _ptr(normals), normal_fmt,
+                                               normals.stride(0) * normals.element_size(), C.byref(shared), per_pass, int(blur_passes), _ptr(work), work.numel(),
+                                               _ptr(out), out.stride(0), w, h))
         return out, work
 
     def msaa_resolve_surfaces(self, depth_ms, coverage=None, normals=None, normals_fmt=abi.FMT_R10G10B10A2_UNORM, roughness=None, background=None,

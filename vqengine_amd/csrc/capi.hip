@@ -1663,7 +1663,7 @@ int vqhip_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_t depthPi
     if (width > VQHIP_CACAO_MAX_DIM || height > VQHIP_CACAO_MAX_DIM) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: frames above 16384 in either dimension are not supported");
     if (qualityLevel < VQHIP_CACAO_QUALITY_LOWEST || qualityLevel > VQHIP_CACAO_QUALITY_HIGHEST) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: qualityLevel is not an FFX_CACAO_Quality");
     if (qualityLevel == VQHIP_CACAO_QUALITY_HIGHEST)
-        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: quality HIGHEST (the adaptive base pass, the importance map and the importance-driven tap loop) is not implemented; use HIGH");
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: quality HIGHEST (the adaptive base pass, the importance map and the importance-driven tap loop) is vqhip_adaptive_cacao, with its larger work buffer; this entry point runs HIGH");
     if (qualityLevel != VQHIP_CACAO_QUALITY_HIGH) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: quality levels LOWEST, LOW and MEDIUM are not implemented; use HIGH");
     if (normalFmt != VQHIP_FMT_R10G10B10A2_UNORM && normalFmt != VQHIP_FMT_RGBA32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: normals must be R10G10B10A2_UNORM or RGBA32F");
     if (blurPassCount < 0 || blurPassCount > VQHIP_CACAO_MAX_BLUR_PASSES) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: blurPassCount must be 0..8");
@@ -1703,6 +1703,89 @@ int vqhip_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_t depthPi
     a.normF32 = normalFmt == VQHIP_FMT_RGBA32F; a.blurPasses = blurPassCount;
     hipError_t e = launch_cacao((hipStream_t)stream, a, *shared, perPass);
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "cacao launch");
+}
+
+// ---- FidelityFX CACAO at quality HIGHEST (cacao.hip; docs/DESIGN_DETAILS.md §7.15): HIGH's work layout as the prefix, three planes appended ------------------
+namespace {
+struct AdaptiveCacaoLayout { CacaoLayout high; size_t importance, importancePong, counter, total; int iw, ih; };
+bool adaptiveCacaoLayout(int W, int H, AdaptiveCacaoLayout* L) {
+    if (!cacaoLayout(W, H, &L->high)) return false;
+    L->iw = (L->high.hw + 1) / 2; L->ih = (L->high.hh + 1) / 2;
+    size_t off = L->high.total;
+    L->importance = off;     off = align256(off + (size_t)L->iw * L->ih);
+    L->importancePong = off; off = align256(off + (size_t)L->iw * L->ih);
+    L->counter = off;        off = align256(off + 4);
+    L->total = off;
+    return true;
+}
+} // namespace
+
+size_t vqhip_adaptive_cacao_work_bytes(int width, int height) {
+    AdaptiveCacaoLayout L;
+    return adaptiveCacaoLayout(width, height, &L) ? L.total : 0;
+}
+size_t vqhip_adaptive_cacao_plane_offset_bytes(int width, int height, int plane, int slice, int mip) {
+    if (plane >= VQHIP_CACAO_PLANE_DEPTHS && plane <= VQHIP_CACAO_PLANE_PONG) return vqhip_cacao_plane_offset_bytes(width, height, plane, slice, mip);
+    AdaptiveCacaoLayout L;
+    if (!adaptiveCacaoLayout(width, height, &L) || slice != 0 || mip != 0) return 0;
+    switch (plane) {
+        case VQHIP_CACAO_PLANE_IMPORTANCE:      return L.importance;
+        case VQHIP_CACAO_PLANE_IMPORTANCE_PONG: return L.importancePong;
+        case VQHIP_CACAO_PLANE_LOAD_COUNTER:    return L.counter;
+        default: return 0;
+    }
+}
+
+int vqhip_adaptive_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_t depthPitchBytes, const void* normals, int normalFmt, size_t normalPitchBytes,
+        const VQ_CacaoConstants* shared, const VQ_CacaoConstants perPass[4], int blurPassCount,
+        void* work, size_t workBytes, uint8_t* ao, size_t aoPitchBytes, int width, int height) {
+    vqk::Range range_("Ambient Occlusion (FidelityFX CACAO)");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: ctx is NULL");
+    CTX_GUARD(ctx, "adaptive_cacao");
+    if (!depth || !normals || !shared || !perPass || !work || !ao) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: NULL argument");
+    if (width <= 0 || height <= 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: bad dimensions");
+    if (width > VQHIP_CACAO_MAX_DIM || height > VQHIP_CACAO_MAX_DIM) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "adaptive_cacao: frames above 16384 in either dimension are not supported");
+    if (normalFmt != VQHIP_FMT_R10G10B10A2_UNORM && normalFmt != VQHIP_FMT_RGBA32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "adaptive_cacao: normals must be R10G10B10A2_UNORM or RGBA32F");
+    if (blurPassCount < 0 || blurPassCount > VQHIP_CACAO_MAX_BLUR_PASSES) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: blurPassCount must be 0..8");
+    const size_t normalPx = normalFmt == VQHIP_FMT_RGBA32F ? 16 : 4;
+    if (depthPitchBytes < (size_t)width * 4 || depthPitchBytes % 4) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: depthPitchBytes below 4 * width or not a multiple of 4");
+    if (normalPitchBytes < (size_t)width * normalPx || normalPitchBytes % normalPx) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: normalPitchBytes below the row size or not a multiple of the pixel size");
+    if (aoPitchBytes < (size_t)width) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: aoPitchBytes below the width");
+    if (depthPitchBytes / 4 > 0x7fffffffu || normalPitchBytes / normalPx > 0x7fffffffu || aoPitchBytes > 0x7fffffffu) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: pitch too large");
+    AdaptiveCacaoLayout A;
+    adaptiveCacaoLayout(width, height, &A);
+    const CacaoLayout& L = A.high;
+    if (workBytes < A.total) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: workBytes below vqhip_adaptive_cacao_work_bytes(width, height)");
+    if ((uintptr_t)work % 256) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: work must be 256-byte aligned");
+    // the constants must describe THIS frame, the importance map included: the kernels address by the integer sizes and compute with the blocks' floats
+    auto sizesMatch = [&](const VQ_CacaoConstants& c) {
+        return c.SSAOBufferDimensions[0] == (float)L.hw && c.SSAOBufferDimensions[1] == (float)L.hh && c.DepthBufferDimensions[0] == (float)width &&
+               c.DepthBufferDimensions[1] == (float)height && c.InputOutputBufferDimensions[0] == (float)width && c.InputOutputBufferDimensions[1] == (float)height &&
+               c.DeinterleavedDepthBufferDimensions[0] == (float)L.hw && c.DeinterleavedDepthBufferDimensions[1] == (float)L.hh &&
+               c.ImportanceMapDimensions[0] == (float)A.iw && c.ImportanceMapDimensions[1] == (float)A.ih;
+    };
+    if (!sizesMatch(*shared)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: the shared constants are not those of this frame size at native resolution (FFX_CACAO_UpdateBufferSizeInfo(width, height, false))");
+    for (int i = 0; i < 4; ++i) {
+        if (!sizesMatch(perPass[i])) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: a per-pass constants block is not of this frame size at native resolution");
+        if (perPass[i].PassIndex != i) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: perPass[i].PassIndex must be i");
+    }
+    const size_t depthBytes = (size_t)(height - 1) * depthPitchBytes + (size_t)width * 4, normalBytes = (size_t)(height - 1) * normalPitchBytes + (size_t)width * normalPx;
+    const size_t aoBytes = (size_t)(height - 1) * aoPitchBytes + (size_t)width;
+    if (rangesOverlap(work, A.total, depth, depthBytes) || rangesOverlap(work, A.total, normals, normalBytes) || rangesOverlap(work, A.total, ao, aoBytes) ||
+        rangesOverlap(ao, aoBytes, depth, depthBytes) || rangesOverlap(ao, aoBytes, normals, normalBytes))
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: work and ao must not overlap each other or the inputs");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    CacaoArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.depth = depth; a.normals = normals; a.work = (uint8_t*)work; a.ao = ao;
+    for (int k = 0; k < 4; ++k) { a.offDepth[k] = L.depth[k]; a.mw[k] = L.mw[k]; a.mh[k] = L.mh[k]; }
+    a.offNormals = L.normals; a.offPing = L.ping; a.offPong = L.pong;
+    a.width = width; a.height = height; a.hw = L.hw; a.hh = L.hh;
+    a.depthPitch = (int)(depthPitchBytes / 4); a.normalPitch = (int)(normalPitchBytes / normalPx); a.aoPitch = (int)aoPitchBytes;
+    a.normF32 = normalFmt == VQHIP_FMT_RGBA32F; a.blurPasses = blurPassCount;
+    const CacaoAdaptiveArgs ad = { A.importance, A.importancePong, A.counter, A.iw, A.ih };
+    hipError_t e = launch_cacao_adaptive((hipStream_t)stream, a, ad, *shared, perPass);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "adaptive_cacao launch");
 }
 
 } // extern "C"

@@ -245,6 +245,9 @@ struct CacaoArgs {
     int width, height, hw, hh, depthPitch, normalPitch, aoPitch, normF32, blurPasses;
 };
 hipError_t launch_cacao(hipStream_t s, const CacaoArgs& a, const VQ_CacaoConstants& shared, const VQ_CacaoConstants perPass[4]);
+// Quality HIGHEST (vqhip_adaptive_cacao; §7.15): the three planes appended to the work buffer — the importance map and its pong, R8_UNORM iw x ih, and the load counter
+struct CacaoAdaptiveArgs { size_t offImportance, offImportancePong, offCounter; int iw, ih; };
+hipError_t launch_cacao_adaptive(hipStream_t s, const CacaoArgs& a, const CacaoAdaptiveArgs& ad, const VQ_CacaoConstants& shared, const VQ_CacaoConstants perPass[4]);
 
 // launchers (each returns the hipError_t of the launch)
 hipError_t launch_forward_lighting(hipStream_t s, const ShadeArgs& a, bool hasEnv, bool hasCasters, int outFmt, const Options& opt);
