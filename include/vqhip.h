@@ -332,7 +332,7 @@ VQHIP_API int  vqhip_set_fresnel_pow(vqhip_ctx* ctx, vqhip_fresnel_pow mode);
  * undefined behaviour, and VQEngine records on many threads, SceneRendering.cpp:563-706). value NULL, "" or "default" restores the default. Every
  * form selected here gives the bits of the default form (tests/test_gpu_conv_forms.py, tests/test_gpu_round3.py); unknown keys / values: VQHIP_ERR_INVALID_ARG.
  *   shade_wg 64|128|256 · psmain_waves 4|5|6 · blur_y_wgs n · post_form two|chain · post_strips n · lut_form general ·
- *   specular_form general · diffuse_form records|texels|general · diffuse_seq_form ordered|lane
+ *   specular_form general · diffuse_form records|texels|general · diffuse_seq_form ordered|lane · raster_tile 32|64
  * (the non-default values are the general / fallback forms of the same kernels; the measured-and-rejected kernel forms of rounds 2-5 — the compact tonemap
  * tables, the per-sample LUT and per-mip specular kernels, the persistent X pass, the rolling-ring Y pass — are not in the library: docs/HISTORY.md).
  * psmain_waves applies to the literal reading only (the DXC-reading instantiation of the fused PSMain kernel has one register cap). post_form: "two" = vqhip_post_process[_tile] always runs blur X, then blur Y + tonemap (two kernels); "chain" = the one-kernel chain whatever the frame size
@@ -346,7 +346,8 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * vqhip_composite_reflections; vqhip_visualize reads R10G10B10A2 / RG16F / RG32F inputs.
                                * Later additions to 3: vqhip_gbuffer_msaa, vqhip_forward_lighting_msaa; vqhip_msaa_surfaces, vqhip_msaa_resolve_surfaces, vqhip_depth_hierarchy (+ _bytes, _level_offset_bytes);
                                * vqhip_ssr_classify, vqhip_ssr_intersect; vqhip_ssr_prefilter, vqhip_ssr_resolve_temporal, VQHIP_FMT_R11G11B10_FLOAT; vqhip_ssr_reproject, vqhip_ssr_reproject_surfaces;
-                               * VQ_CacaoConstants, vqhip_cacao (+ _work_bytes, _plane_offset_bytes); vqhip_adaptive_cacao (+ _work_bytes, _plane_offset_bytes) and three plane ids */
+                               * VQ_CacaoConstants, vqhip_cacao (+ _work_bytes, _plane_offset_bytes); vqhip_adaptive_cacao (+ _work_bytes, _plane_offset_bytes) and three plane ids;
+                               * vqhip_shadow_depth (+ _work_bytes), vqhip_shadow_mesh / _draw / _view, VQHIP_CULL_*, option raster_tile */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -1078,6 +1079,49 @@ VQHIP_API size_t vqhip_adaptive_cacao_plane_offset_bytes(int width, int height, 
 VQHIP_API int vqhip_adaptive_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_t depthPitchBytes, const void* normals, int normalFmt, size_t normalPitchBytes,
         const VQ_CacaoConstants* shared, const VQ_CacaoConstants perPass[4], int blurPassCount,
         void* work, size_t workBytes, uint8_t* ao, size_t aoPitchBytes, int width, int height);
+
+/* ---- Shadow-map rasteriser: VQRenderer::RenderDirectionalShadowMaps / RenderSpotShadowMaps / RenderPointShadowMaps (SceneRendering.cpp:996-1263) ==
+ * ShadowDepthPass.hlsl drawn through the shadow PSOs (PipelineStateObjects.cpp:1697-1741): indexed, instanced triangle lists in, the R32F slices of
+ * vqhip_shadowmaps out. ALL views of a frame in one call (the engine: 37 clear-and-draw sequences). docs/DESIGN_DETAILS.md §7.16 is the normative statement
+ * (R1 vertex stage, R2 clipping against w >= 2^-24 and the four side planes — no z planes: DepthClipEnable is FALSE —, R3 viewport and 16.8 snap, R4 top-left
+ * coverage in int64, R5 z/w and R6 LINEAR_DEPTH interpolation); tests/shadow_raster_ref.py states it in numpy. R2, R5 and R6 are UNPINNED against a D3D12
+ * device (docs/WARP_CALIBRATION.md §5).
+ * Out of scope: the ENABLE_ALPHA_MASK variant, the tessellation and heightmap variants (the null heightmap's + 0.0f is kept), wireframe.
+ * Three kernels on `stream` (plus one setup launch per further ~700 draws): counters, triangle setup, tile fill. No allocation, no memset node; the call clears
+ * each map itself (uncovered texels read 1.0; a view with numDraws == 0 yields all 1.0). View and draw descriptors are host memory, consumed before the call
+ * returns; meshes and matrices are device memory, read when the kernels run. The maps of one call must not overlap each other, the work buffer or the inputs. */
+typedef enum vqhip_cull_mode { VQHIP_CULL_NONE = 0, VQHIP_CULL_FRONT = 1, VQHIP_CULL_BACK = 2 } vqhip_cull_mode;   /* iFaceCull, DrawData.h:161 */
+typedef struct vqhip_shadow_mesh {      /* device pointers */
+    const void* positions;  uint32_t strideBytes;   /* float3 at offset 0 of each vertex; 12 (tight) or the engine's 44-byte vertex, any multiple of 4 >= 12 */
+    uint32_t    numVertices;                        /* a triangle with an index >= numVertices is dropped */
+    const void* indices;    int32_t indexBits;      /* 16 | 32 */
+    uint32_t    numIndices;                         /* multiple of 3: triangle list */
+} vqhip_shadow_mesh;
+typedef struct vqhip_shadow_draw {      /* one DrawIndexedInstanced of DrawShadowViewMeshList */
+    vqhip_shadow_mesh mesh;
+    const VQ_matrix* matWorldViewProj;  /* device, [numInstances]: PerObjectShadowData.matWorldViewProj */
+    const VQ_matrix* matWorld;          /* device, [numInstances]: PerObjectShadowData.matWorld; may be NULL when the view is not linear-depth */
+    uint32_t numInstances;              /* 1 .. 128 (MAX_INSTANCE_COUNT__SHADOW_MESHES) */
+    int32_t  cullMode;                  /* VQHIP_CULL_NONE | _FRONT | _BACK  (iFaceCull) */
+} vqhip_shadow_draw;
+typedef struct vqhip_shadow_view {
+    float*  depth;  size_t pitchBytes;  int32_t dim;   /* one dim x dim R32F slice of vqhip_shadowmaps; pitch 0 = dense */
+    int32_t linearDepth;                               /* 0: z/w (directional, spot); 1: LINEAR_DEPTH (point faces) */
+    VQ_float3 cameraPosition;  float farPlane;         /* PerShadowViewData; read only when linearDepth */
+    const vqhip_shadow_draw* draws;  int32_t numDraws; /* host array */
+} vqhip_shadow_view;
+#define VQHIP_SHADOW_MAX_DIM 8192
+#define VQHIP_SHADOW_MAX_VIEWS 64
+#define VQHIP_SHADOW_MAX_INSTANCES 128
+/* Bytes of work for a call whose views draw `instancedTriangles` triangles in all (sum over views and draws of numIndices / 3 * numInstances): six records per
+ * triangle (a triangle clipped by five planes is a fan of at most six). 0 for numViews outside 1 .. 64 or a size that does not fit size_t. Host-only. */
+VQHIP_API size_t vqhip_shadow_depth_work_bytes(uint64_t instancedTriangles, int numViews);
+/* Returns VQHIP_ERR_INVALID_ARG — launching nothing, leaving the maps untouched — for NULL pointers (ctx, views, a view's depth, draws with numDraws > 0, a
+ * mesh's positions or indices, matWorldViewProj, matWorld of a linear-depth view, work), numViews outside 1 .. 64, dim outside 1 .. 8192, a pitch below 4 * dim or not
+ * a multiple of 4, numDraws < 0, an indexBits other than 16 / 32, numIndices % 3 != 0, a stride below 12 or not a multiple of 4, numInstances outside 1 .. 128, an
+ * unknown cullMode, positions or matrices not 4-byte aligned, indices not aligned to their size, work not 256-byte aligned or workBytes below vqhip_shadow_depth_work_bytes of the
+ * call's own triangle count; VQHIP_ERR_UNSUPPORTED for more than 20 000 draws or 2^31 triangle lanes in one call. */
+VQHIP_API int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_view* views, int numViews, void* work, size_t workBytes);
 
 #ifdef __cplusplus
 }

@@ -489,6 +489,80 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// Shadow maps == VQRenderer::RenderDirectionalShadowMaps + RenderSpotShadowMaps + RenderPointShadowMaps (SceneRendering.cpp:1114-1263) with
+// DrawShadowViewMeshList (:996-1040): vqhip_shadow_depth, every view of the frame in ONE call. FDrawParameters carries what the three functions hold per view:
+// the draw lists (FSceneDrawData::directionalShadowDrawParams / spotShadowDrawParams[i] / pointShadowDrawParams[i * 6 + face], each FInstancedDrawParameters as a
+// vqhip_shadow_draw whose matrices are the uploaded PerObjectShadowData), the casters' position and range (SetPerViewShadowCB) and the three depth arrays the lit
+// draw reads through vqhip_shadowmaps (DSV_ShadowMaps_Directional / _Spot / _Point as R32F). As in the engine, a view whose draw list is empty is skipped: its
+// map is neither cleared nor drawn. Point faces are LINEAR_DEPTH (iDepthMode 1), the others z/w. The pass owns the work buffer: Reserve sizes it for a triangle
+// count ahead of time; RecordCommands grows it when a frame needs more (hipFree of the old buffer waits for the device; the library itself never allocates).
+// ---------------------------------------------------------------------------------------------------------------
+class ShadowDepthPass : public RenderPassBase {
+public:
+    struct FResourceParameters : public IRenderPassResourceCollection {};
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        float* ShadowMapsDirectional = nullptr; int DirectionalDim = 2048;      // [dim][dim]                     SceneRendering.cpp:1128
+        float* ShadowMapsSpot = nullptr;        int SpotDim = 1024;             // [NumSpotShadowViews][dim][dim] :1166
+        float* ShadowMapsPoint = nullptr;       int PointDim = 1024;            // [NumPointShadowViews][6][dim][dim] :1219
+        const std::vector<vqhip_shadow_draw>* DirectionalDraws = nullptr;       // nullptr or empty: the directional map is skipped (:1122)
+        unsigned NumSpotShadowViews = 0;
+        const std::vector<vqhip_shadow_draw>* SpotDraws[VQ_NUM_SHADOWING_LIGHTS__SPOT] = {};
+        unsigned NumPointShadowViews = 0;                                       // point LIGHTS; six views each
+        const std::vector<vqhip_shadow_draw>* PointDraws[VQ_NUM_SHADOWING_LIGHTS__POINT * 6] = {};
+        VQ_float3 PointPosition[VQ_NUM_SHADOWING_LIGHTS__POINT] = {};           // GPULightingData.point_casters[i].position (:1234)
+        float PointRange[VQ_NUM_SHADOWING_LIGHTS__POINT] = {};                  // ... .range, the far plane (:1235)
+    };
+    explicit ShadowDepthPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    ~ShadowDepthPass() override { Free(mWork); }
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { Free(mWork); mWorkBytes = 0; }
+    void OnCreateWindowSizeDependentResources(unsigned, unsigned, const IRenderPassResourceCollection* = nullptr) override {}   // shadow maps do not follow the window
+    void OnDestroyWindowSizeDependentResources() override {}
+    bool Reserve(uint64_t InstancedTriangles) {
+        const size_t need = vqhip_shadow_depth_work_bytes(InstancedTriangles, VQHIP_SHADOW_MAX_VIEWS);
+        if (!need) return false;
+        if (need <= mWorkBytes) return true;
+        Free(mWork); mWorkBytes = 0;
+        mWork = Alloc(need);
+        if (mWork) mWorkBytes = need;
+        return mWork != nullptr;
+    }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p || p->NumSpotShadowViews > VQ_NUM_SHADOWING_LIGHTS__SPOT || p->NumPointShadowViews > VQ_NUM_SHADOWING_LIGHTS__POINT) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        vqhip_shadow_view views[1 + VQ_NUM_SHADOWING_LIGHTS__SPOT + 6 * VQ_NUM_SHADOWING_LIGHTS__POINT];
+        int n = 0;
+        uint64_t triangles = 0;
+        auto add = [&](const std::vector<vqhip_shadow_draw>* draws, float* map, int dim, int linear, VQ_float3 pos, float farPlane) {
+            if (!draws || draws->empty()) return;
+            vqhip_shadow_view& v = views[n++];
+            v.depth = map; v.pitchBytes = 0; v.dim = dim; v.linearDepth = linear; v.cameraPosition = pos; v.farPlane = farPlane;
+            v.draws = draws->data(); v.numDraws = (int32_t)draws->size();
+            for (const vqhip_shadow_draw& d : *draws) triangles += (uint64_t)(d.mesh.numIndices / 3) * d.numInstances;
+        };
+        const VQ_float3 zero = { 0.0f, 0.0f, 0.0f };
+        add(p->DirectionalDraws, p->ShadowMapsDirectional, p->DirectionalDim, 0, zero, 1.0f);                       // :1146-1147
+        for (unsigned i = 0; i < p->NumSpotShadowViews; ++i)
+            add(p->SpotDraws[i], p->ShadowMapsSpot ? p->ShadowMapsSpot + (size_t)i * p->SpotDim * p->SpotDim : nullptr, p->SpotDim, 0, zero, 1.0f);
+        for (unsigned i = 0; i < p->NumPointShadowViews; ++i)
+            for (unsigned face = 0; face < 6; ++face)
+                add(p->PointDraws[i * 6 + face], p->ShadowMapsPoint ? p->ShadowMapsPoint + (size_t)(i * 6 + face) * p->PointDim * p->PointDim : nullptr, p->PointDim, 1,
+                    p->PointPosition[i], p->PointRange[i]);
+        mNumViews = n;
+        if (n == 0) { mStatus = VQHIP_OK; return; }                              // nothing casts a shadow this frame
+        if (!Reserve(triangles)) { mStatus = VQHIP_ERR_HIP; return; }
+        mStatus = vqhip_shadow_depth(mCtx, p->Stream, views, n, mWork, mWorkBytes);
+    }
+    const void* GetWorkBuffer() const { return mWork; }
+    size_t GetWorkBytes() const { return mWorkBytes; }
+    int LastViewCount() const { return mNumViews; }
+private:
+    void* mWork = nullptr; size_t mWorkBytes = 0;
+    int mNumViews = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // Reflection denoiser, pass 1 == the "FFX DNSR Reproject" dispatch of ScreenSpaceReflectionsPass::RecordCommands: vqhip_ssr_reproject. Buffer roles as
 // ScreenSpaceReflections.cpp:1177-1198 binds them for frame index i: reads the surfaces of this frame and their history copies, TexRadiance[i] (what the march
 // wrote), TexRadiance[1 - i] (last frame's resolved radiance), the motion vectors, TexVariance[1 - i] and TexSampleCount[1 - i]; writes TexReprojectedRadiance,

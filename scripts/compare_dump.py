@@ -14,6 +14,9 @@ Inputs (raw little-endian files written by the patched engine, all of one frame)
   --size W H
   --backend hip|oracle                        hip: libvqhip.so on cuda:0 (the product); oracle: the CPU restatement (no GPU needed)
 Output: one JSON object: channels compared, max ulps, histogram, the worst pixels. Exit code 1 when any channel is more than --max-ulps (1) away.
+  --shadow-slice ENGINE.f32 OURS.f32 --size D D    instead of all of the above: two raw float32 planes of one D x D shadow-map slice — the engine's D32_FLOAT slice
+                                              read back, and tests/shadow_raster_ref.rasterize on the dumped meshes and matrices (docs/WARP_CALIBRATION.md §5) —
+                                              compared as the SET of covered texels (value != 1.0; must be equal) and in binary32 ulps on the texels both cover
 `--selftest` fabricates a dump from the oracle (plus a known 1-ulp perturbation) and runs the comparison on it."""
 import argparse
 import json
@@ -73,6 +76,22 @@ def compare(ours, theirs, max_ulps):
     return rep
 
 
+def compare_shadow_slice(engine_path, ours_path, dim):
+    a, b = (np.fromfile(p, np.float32) for p in (engine_path, ours_path))
+    if a.size != dim * dim or b.size != dim * dim:
+        raise SystemExit(f"--shadow-slice: expected {dim * dim * 4} bytes per plane, got {a.size * 4} and {b.size * 4}")
+    a, b = a.reshape(dim, dim), b.reshape(dim, dim)
+    ca, cb = a != 1.0, b != 1.0
+    both = ca & cb
+    key = lambda x: x.view(np.int32).astype(np.int64)      # noqa: E731  (depths are >= +0: the bit pattern orders them)
+    d = np.abs(key(a) - key(b))[both]
+    only = np.argwhere(ca ^ cb)
+    border = int(sum(1 for (y, x) in only if y in (0, dim - 1) or x in (0, dim - 1)))
+    return {"dim": dim, "covered_engine": int(ca.sum()), "covered_ours": int(cb.sum()), "covered_by_one_only": int(only.shape[0]), "of_those_on_the_border": border,
+            "first_differences": only[:8].tolist(), "max_ulps": int(d.max()) if d.size else 0, "texels_differing": int((d > 0).sum()),
+            "histogram_ulps": {str(k): int((d == k).sum()) for k in range(0, 5)} | {">4": int((d > 4).sum())}, "pass": bool(only.shape[0] == 0)}
+
+
 def selftest(tmp):
     from tests import oracle_lib as O
     from vqengine_amd import synth
@@ -98,7 +117,14 @@ def main():
     ap.add_argument("--backend", choices=["hip", "oracle"], default="hip")
     ap.add_argument("--max-ulps", type=int, default=1)
     ap.add_argument("--selftest", action="store_true")
+    ap.add_argument("--shadow-slice", nargs=2, metavar=("ENGINE.f32", "OURS.f32"))
     a = ap.parse_args()
+    if a.shadow_slice:
+        if not a.size or a.size[0] != a.size[1]:
+            ap.error("--shadow-slice needs --size D D")
+        rep = compare_shadow_slice(a.shadow_slice[0], a.shadow_slice[1], a.size[0])
+        print(json.dumps(rep, indent=1))
+        sys.exit(0 if rep["pass"] else 1)
     if a.selftest:
         import tempfile
         tmp = tempfile.mkdtemp()

@@ -224,6 +224,26 @@ class CacaoConstants(C.Structure):  # VQ_CacaoConstants == FFX_CACAO_Constants (
         ("NormalsWorldToViewspaceMatrix", matrix)]
 
 
+CULL_NONE, CULL_FRONT, CULL_BACK = 0, 1, 2   # VQHIP_CULL_*: iFaceCull
+SHADOW_MAX_DIM = 8192                        # VQHIP_SHADOW_MAX_DIM
+SHADOW_MAX_VIEWS = 64                        # VQHIP_SHADOW_MAX_VIEWS
+SHADOW_MAX_INSTANCES = 128                   # VQHIP_SHADOW_MAX_INSTANCES == MAX_INSTANCE_COUNT__SHADOW_MESHES
+
+
+class ShadowMesh(C.Structure):  # vqhip_shadow_mesh
+    _fields_ = [("positions", C.c_void_p), ("strideBytes", C.c_uint32), ("numVertices", C.c_uint32), ("indices", C.c_void_p), ("indexBits", C.c_int32),
+                ("numIndices", C.c_uint32)]
+
+
+class ShadowDraw(C.Structure):  # vqhip_shadow_draw
+    _fields_ = [("mesh", ShadowMesh), ("matWorldViewProj", C.c_void_p), ("matWorld", C.c_void_p), ("numInstances", C.c_uint32), ("cullMode", C.c_int32)]
+
+
+class ShadowView(C.Structure):  # vqhip_shadow_view
+    _fields_ = [("depth", C.c_void_p), ("pitchBytes", C.c_size_t), ("dim", C.c_int32), ("linearDepth", C.c_int32), ("cameraPosition", float3), ("farPlane", C.c_float),
+                ("draws", C.POINTER(ShadowDraw)), ("numDraws", C.c_int32)]
+
+
 def _chk(t, size, **offs):
     assert C.sizeof(t) == size, (t.__name__, C.sizeof(t), size)
     for k, v in offs.items():
@@ -248,6 +268,9 @@ _chk(MSAASurfaces, 176, coverage=8, normals=40, roughness=72, background=104, no
 _chk(TonemapperParams, 16)
 _chk(BlurParams, 8)
 _chk(SSSRConstants, 512, bufferDimensions=448, roughnessThreshold=472, envMapSpecularIrradianceCubemapMipLevelCount=504)
+_chk(ShadowMesh, 32, strideBytes=8, numVertices=12, indices=16, indexBits=24, numIndices=28)
+_chk(ShadowDraw, 56, matWorldViewProj=32, matWorld=40, numInstances=48, cullMode=52)
+_chk(ShadowView, 56, pitchBytes=8, dim=16, linearDepth=20, cameraPosition=24, farPlane=36, draws=40, numDraws=48)
 _chk(CacaoConstants, 384, EffectRadius=48, InvSharpness=96, PassIndex=100, PatternRotScaleMatrices=112, NormalsUnpackMul=192, SSAOBufferDimensions=208,
      DepthBufferOffset=240, PerPassFullResUVOffset=248, DeinterleavedDepthBufferNormalisedOffset=312, NormalsWorldToViewspaceMatrix=320)
 

@@ -110,6 +110,8 @@ def load_library():
         "vqhip_adaptive_cacao_work_bytes": (sz, [i32, i32]),
         "vqhip_adaptive_cacao_plane_offset_bytes": (sz, [i32, i32, i32, i32, i32]),
         "vqhip_adaptive_cacao": (i32, [vp, vp, vp, sz, vp, i32, sz, C.POINTER(abi.CacaoConstants), C.POINTER(abi.CacaoConstants), i32, vp, sz, vp, sz, i32, i32]),
+        "vqhip_shadow_depth_work_bytes": (sz, [C.c_uint64, i32]),
+        "vqhip_shadow_depth": (i32, [vp, vp, C.POINTER(abi.ShadowView), i32, vp, sz]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -144,7 +146,33 @@ EXPORTED_SYMBOLS = [
     "vqhip_ssr_classify", "vqhip_ssr_intersect", "vqhip_ssr_prefilter", "vqhip_ssr_resolve_temporal", "vqhip_ssr_reproject",
     "vqhip_cacao", "vqhip_cacao_work_bytes", "vqhip_cacao_plane_offset_bytes",
     "vqhip_adaptive_cacao", "vqhip_adaptive_cacao_work_bytes", "vqhip_adaptive_cacao_plane_offset_bytes",
+    "vqhip_shadow_depth", "vqhip_shadow_depth_work_bytes",
 ]
+
+
+def shadow_depth_work_bytes(instanced_triangles, num_views):
+    """vqhip_shadow_depth_work_bytes: the work buffer of a vqhip_shadow_depth call whose views draw `instanced_triangles` triangles in all. Host-only."""
+    return load_library().vqhip_shadow_depth_work_bytes(int(instanced_triangles), int(num_views))
+
+
+class ShadowDraw:
+    """One vqhip_shadow_draw. positions: cuda float32 [V, k] with k >= 3 and unit column stride (the row stride is the vertex stride: k = 3 tight, k = 11 the
+    engine's 44-byte vertex); indices: cuda 1-D int16 / uint16 (read as 16-bit unsigned) or int32, a triangle list; wvp / world: cuda float32 [n, 4, 4]
+    contiguous, VQ_matrix memory order (world may be None outside linear-depth views); cull: abi.CULL_*."""
+
+    def __init__(self, positions, indices, wvp, world=None, cull=abi.CULL_NONE):
+        self.positions, self.indices, self.wvp, self.world, self.cull = positions, indices, wvp, world, cull
+
+
+class ShadowView:
+    """One vqhip_shadow_view. depth: cuda float32 [dim, dim] with unit column stride (a slice of the arrays vqhip_shadowmaps points at); linear: LINEAR_DEPTH
+    (point-light faces) with camera = the light's position and far = its range; draws: a list of ShadowDraw."""
+
+    def __init__(self, depth, draws=(), linear=False, camera=(0.0, 0.0, 0.0), far=1.0):
+        self.depth, self.draws, self.linear, self.camera, self.far = depth, list(draws), bool(linear), tuple(camera), float(far)
+
+    def instanced_triangles(self):
+        return sum((d.indices.numel() // 3) * d.wvp.shape[0] for d in self.draws)
 
 
 def cacao_work_bytes(width, height):
@@ -532,6 +560,68 @@ class Context:
                                                normals.stride(0) * normals.element_size(), C.byref(shared), per_pass, int(blur_passes), _ptr(work), work.numel(),
                                                _ptr(out), out.stride(0), w, h))
         return out, work
+
+    def shadow_depth(self, views, work=None, stream=None):
+        """vqhip_shadow_depth: rasterise every ShadowView of `views` (at most 64) into its depth tensor, in one call. work: a cuda uint8 tensor of
+        shadow_depth_work_bytes(total instanced triangles, len(views)) bytes (allocated when None). Returns work."""
+        call, work = self.shadow_depth_prepared(views, work)
+        call(stream)
+        return work
+
+    def shadow_depth_prepared(self, views, work=None):
+        """The descriptors of a shadow_depth call built once: returns (call, work) with call(stream=None) issuing vqhip_shadow_depth on the same views again
+        (a frame loop, a benchmark). The tensors of `views` must stay alive and in place."""
+        views = list(views)
+        if not 1 <= len(views) <= abi.SHADOW_MAX_VIEWS:
+            raise ValueError(f"shadow_depth: expected 1..{abi.SHADOW_MAX_VIEWS} views, got {len(views)}")
+        cviews = (abi.ShadowView * len(views))()
+        keep = []
+        for i, v in enumerate(views):
+            d = v.depth
+            if not (d.is_cuda and d.dtype == torch.float32 and d.dim() == 2 and d.shape[0] == d.shape[1] and d.stride(1) == 1 and d.stride(0) >= d.shape[1]):
+                raise ValueError(f"shadow_depth: view {i}: depth: expected cuda float32 [dim, dim] with unit column stride, got {tuple(d.shape)} {d.dtype} strides {d.stride()}")
+            if not 1 <= d.shape[0] <= abi.SHADOW_MAX_DIM:
+                raise ValueError(f"shadow_depth: view {i}: dim must be 1..{abi.SHADOW_MAX_DIM}")
+            cdraws = (abi.ShadowDraw * max(1, len(v.draws)))()
+            keep.append(cdraws)
+            for j, dr in enumerate(v.draws):
+                who = f"shadow_depth: view {i} draw {j}"
+                p, ix = dr.positions, dr.indices
+                if not (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and p.shape[1] >= 3 and p.stride(1) == 1 and p.stride(0) >= p.shape[1]):
+                    raise ValueError(f"{who}: positions: expected cuda float32 [V, k >= 3] with unit column stride")
+                bits = {2: 16, 4: 32}.get(ix.element_size()) if not ix.dtype.is_floating_point else None
+                if not (ix.is_cuda and ix.dim() == 1 and ix.is_contiguous() and bits and ix.numel() % 3 == 0):
+                    raise ValueError(f"{who}: indices: expected a contiguous cuda 1-D 16-bit or 32-bit integer tensor whose length is a multiple of 3")
+                n = dr.wvp.shape[0] if dr.wvp.dim() == 3 else 0
+                for name, m in (("wvp", dr.wvp), ("world", dr.world)):
+                    if m is None and name == "world" and not v.linear:
+                        continue
+                    if m is None or not (m.is_cuda and m.dtype == torch.float32 and tuple(m.shape) == (n, 4, 4) and m.is_contiguous()):
+                        raise ValueError(f"{who}: {name}: expected cuda float32 [n, 4, 4] contiguous, n the same for wvp and world")
+                if not 1 <= n <= abi.SHADOW_MAX_INSTANCES:
+                    raise ValueError(f"{who}: 1..{abi.SHADOW_MAX_INSTANCES} instances, got {n}")
+                if dr.cull not in (abi.CULL_NONE, abi.CULL_FRONT, abi.CULL_BACK):
+                    raise ValueError(f"{who}: cull: expected abi.CULL_NONE, CULL_FRONT or CULL_BACK")
+                c = cdraws[j]
+                c.mesh.positions, c.mesh.strideBytes, c.mesh.numVertices = p.data_ptr(), p.stride(0) * 4, p.shape[0]
+                c.mesh.indices, c.mesh.indexBits, c.mesh.numIndices = ix.data_ptr(), bits, ix.numel()
+                c.matWorldViewProj, c.matWorld = dr.wvp.data_ptr(), (dr.world.data_ptr() if dr.world is not None else None)
+                c.numInstances, c.cullMode = n, dr.cull
+            cv = cviews[i]
+            cv.depth, cv.pitchBytes, cv.dim, cv.linearDepth = d.data_ptr(), d.stride(0) * 4, d.shape[0], int(v.linear)
+            cv.cameraPosition = abi.float3(*[float(x) for x in v.camera])
+            cv.farPlane, cv.numDraws = v.far, len(v.draws)
+            cv.draws = C.cast(cdraws, C.POINTER(abi.ShadowDraw))
+        need = shadow_depth_work_bytes(sum(v.instanced_triangles() for v in views), len(views))
+        if work is None:
+            work = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.numel() >= need):
+            raise ValueError(f"shadow_depth: work: expected a contiguous cuda uint8 tensor of at least {need} bytes")
+        keep.append(views)
+
+        def call(stream=None, _keep=keep):
+            self._ck(self.lib.vqhip_shadow_depth(self._h, self._stream(stream), cviews, len(views), _ptr(work), work.numel()))
+        return call, work
 
     def msaa_resolve_surfaces(self, depth_ms, coverage=None, normals=None, normals_fmt=abi.FMT_R10G10B10A2_UNORM, roughness=None, background=None,
                               out_depth=False, out_normals_fmt=None, scene_color=None, scene_fmt=FMT_RGBA16F, hierarchy=False, flags=0, stream=None):

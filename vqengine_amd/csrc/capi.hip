@@ -697,6 +697,7 @@ int vqhip_set_option(vqhip_ctx* ctx, const char* key, const char* value) {
     if (k == "specular_form") return pick(&o.specularForm, { "general" });
     if (k == "diffuse_form") { if (v == "records") { o.diffuseForm = 0; return VQHIP_OK; } return pick(&o.diffuseForm, { "texels", "general" }); }
     if (k == "diffuse_seq_form") { if (v == "ordered") { o.diffuseSeqForm = 0; return VQHIP_OK; } return pick(&o.diffuseSeqForm, { "lane" }); }
+    if (k == "raster_tile") return num(&o.rasterTile, { 0, 32, 64 });
     return fail(ctx, VQHIP_ERR_INVALID_ARG, "set_option: unknown key '" + k + "'");
 }
 int vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode) {
@@ -1786,6 +1787,129 @@ int vqhip_adaptive_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_
     const CacaoAdaptiveArgs ad = { A.importance, A.importancePong, A.counter, A.iw, A.ih };
     hipError_t e = launch_cacao_adaptive((hipStream_t)stream, a, ad, *shared, perPass);
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "adaptive_cacao launch");
+}
+
+// ---- Shadow-map rasteriser (raster.hip; docs/DESIGN_DETAILS.md §7.16) --------------------------------------------------------------------------------------
+namespace {
+constexpr size_t kRasterJobsPerSlot = kConstSlotBytes / sizeof(RasterJob);
+constexpr size_t kRasterMaxDraws = 20000;                      // at most 29 job slots of the 32-slot ring beside the view table's
+static_assert(sizeof(RasterView) * VQHIP_SHADOW_MAX_VIEWS <= kConstSlotBytes, "the view table fits one ring slot");
+static_assert((kRasterMaxDraws + kRasterJobsPerSlot - 1) / kRasterJobsPerSlot + 1 < vqhip_ctx::kSlots, "one call never meets its own view-table slot again");
+// counters | boxes[6 n] | records[6 n]; false when the sizes do not fit
+bool rasterLayout(uint64_t instancedTriangles, size_t* boxes, size_t* records, size_t* total) {
+    if (instancedTriangles > ((uint64_t)1 << 40)) return false;
+    const uint64_t cap = instancedTriangles * 6;
+    const uint64_t b = kRasterCounterBytes, r = align256(b + cap * kRasterBoxBytes), t = align256(r + cap * kRasterRecordBytes);
+    if (t > (uint64_t)SIZE_MAX) return false;
+    *boxes = (size_t)b; *records = (size_t)r; *total = (size_t)t;
+    return true;
+}
+} // namespace
+
+size_t vqhip_shadow_depth_work_bytes(uint64_t instancedTriangles, int numViews) {
+    size_t b, r, t;
+    if (numViews < 1 || numViews > VQHIP_SHADOW_MAX_VIEWS || !rasterLayout(instancedTriangles, &b, &r, &t)) return 0;
+    return t;
+}
+
+int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_view* views, int numViews, void* work, size_t workBytes) {
+    vqk::Range range_("RenderShadowMaps");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "shadow_depth: ctx is NULL");
+    CTX_GUARD(ctx, "shadow_depth");
+    if (!views || !work) return fail(ctx, VQHIP_ERR_INVALID_ARG, "shadow_depth: NULL argument");
+    if (numViews < 1 || numViews > VQHIP_SHADOW_MAX_VIEWS) return fail(ctx, VQHIP_ERR_INVALID_ARG, "shadow_depth: numViews must be 1..64");
+    if ((uintptr_t)work % 256) return fail(ctx, VQHIP_ERR_INVALID_ARG, "shadow_depth: work must be 256-byte aligned");
+    const int tile = ctx->opt.rasterTile ? ctx->opt.rasterTile : 32;
+    auto bad = [&](int v, int d, const char* m) {
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, "shadow_depth: view " + std::to_string(v) + (d >= 0 ? " draw " + std::to_string(d) : std::string()) + ": " + m);
+    };
+    RasterView hv[VQHIP_SHADOW_MAX_VIEWS];
+    uint64_t totalTris = 0, fillBlocks = 0;
+    size_t numJobs = 0;
+    for (int v = 0; v < numViews; ++v) {
+        const vqhip_shadow_view& V = views[v];
+        if (!V.depth) return bad(v, -1, "depth is NULL");
+        if (V.dim < 1 || V.dim > VQHIP_SHADOW_MAX_DIM) return bad(v, -1, "dim must be 1..8192");
+        const size_t pitch = V.pitchBytes ? V.pitchBytes : (size_t)V.dim * 4;
+        if (pitch < (size_t)V.dim * 4 || pitch % 4) return bad(v, -1, "pitchBytes below 4 * dim or not a multiple of 4");
+        if (pitch / 4 > 0x7fffffffu) return bad(v, -1, "pitch too large");
+        if ((uintptr_t)V.depth % 4) return bad(v, -1, "depth is not 4-byte aligned");
+        if (V.numDraws < 0 || (V.numDraws > 0 && !V.draws)) return bad(v, -1, "numDraws < 0, or draws is NULL");
+        if (V.linearDepth != 0 && V.linearDepth != 1) return bad(v, -1, "linearDepth must be 0 or 1");
+        uint64_t viewTris = 0;
+        for (int d = 0; d < V.numDraws; ++d) {
+            const vqhip_shadow_draw& D = V.draws[d];
+            if (!D.mesh.positions || !D.mesh.indices || !D.matWorldViewProj) return bad(v, d, "positions, indices or matWorldViewProj is NULL");
+            if (V.linearDepth && !D.matWorld) return bad(v, d, "matWorld is NULL in a linear-depth view");
+            if (D.mesh.indexBits != 16 && D.mesh.indexBits != 32) return bad(v, d, "indexBits must be 16 or 32");
+            if (D.mesh.numIndices % 3) return bad(v, d, "numIndices is not a multiple of 3");
+            if (D.mesh.strideBytes < 12 || D.mesh.strideBytes % 4) return bad(v, d, "strideBytes below 12 or not a multiple of 4");
+            if (D.numInstances < 1 || D.numInstances > VQHIP_SHADOW_MAX_INSTANCES) return bad(v, d, "numInstances must be 1..128");
+            if (D.cullMode != VQHIP_CULL_NONE && D.cullMode != VQHIP_CULL_FRONT && D.cullMode != VQHIP_CULL_BACK) return bad(v, d, "unknown cullMode");
+            if ((uintptr_t)D.mesh.positions % 4 || (uintptr_t)D.matWorldViewProj % 4 || (uintptr_t)D.matWorld % 4 || (uintptr_t)D.mesh.indices % (D.mesh.indexBits / 8))
+                return bad(v, d, "positions / matrices must be 4-byte aligned, indices aligned to their size");
+            if (D.mesh.numIndices) { viewTris += (uint64_t)(D.mesh.numIndices / 3) * D.numInstances; ++numJobs; }
+        }
+        RasterView& R = hv[v];
+        std::memset(&R, 0, sizeof(R));
+        R.depth = V.depth; R.pitch = (uint32_t)(pitch / 4); R.dim = V.dim; R.linear = V.linearDepth;
+        R.recBase = totalTris * 6; R.recCap = viewTris * 6;
+        R.cam[0] = V.cameraPosition.x; R.cam[1] = V.cameraPosition.y; R.cam[2] = V.cameraPosition.z; R.farPlane = V.farPlane;
+        R.firstFillBlock = (uint32_t)fillBlocks;
+        const uint64_t tiles = (uint64_t)((V.dim + tile - 1) / tile);
+        fillBlocks += tiles * tiles;
+        totalTris += viewTris;
+        if (viewTris * 6 > 0xffffffffull) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "shadow_depth: a view draws more than 2^32 / 6 instanced triangles");
+    }
+    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "shadow_depth: more than 20000 draws in one call");
+    if ((totalTris + 255) / 256 + numJobs > 0x7fffffffull) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "shadow_depth: more than 2^31 triangle lanes in one call");
+    size_t offBoxes, offRecords, need;
+    if (!rasterLayout(totalTris, &offBoxes, &offRecords, &need) || workBytes < need)
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, "shadow_depth: workBytes below vqhip_shadow_depth_work_bytes(the call's instanced triangles, numViews)");
+    for (int v = 0; v < numViews; ++v) {
+        const size_t bytes = (size_t)(hv[v].dim - 1) * hv[v].pitch * 4 + (size_t)hv[v].dim * 4;
+        if (rangesOverlap(work, need, hv[v].depth, bytes)) return bad(v, -1, "depth overlaps the work buffer");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* counters = (uint32_t*)work;
+    void* boxes = (char*)work + offBoxes;
+    void* records = (char*)work + offRecords;
+    int viewSlot;
+    if (int rc = acquireSlot(ctx, &viewSlot)) return rc;
+    std::memcpy(ctx->hostRing + (size_t)viewSlot * kConstSlotBytes, hv, sizeof(RasterView) * numViews);
+    if (int rc = commitSlot(ctx, viewSlot, sizeof(RasterView) * numViews, st)) return rc;
+    const RasterView* dviews = (const RasterView*)(ctx->devRing + (size_t)viewSlot * kConstSlotBytes);
+    hipError_t e = launch_raster_begin(st, counters, numViews);
+    if (e != hipSuccess) return failHip(ctx, e, "shadow_depth counters launch");
+    // the draws, in ring slots of kRasterJobsPerSlot jobs: one setup launch per slot
+    int v = 0, d = 0;
+    size_t left = numJobs;
+    while (left) {
+        int slot;
+        if (int rc = acquireSlot(ctx, &slot)) return rc;
+        RasterJob* jobs = (RasterJob*)(ctx->hostRing + (size_t)slot * kConstSlotBytes);
+        const size_t n = left < kRasterJobsPerSlot ? left : kRasterJobsPerSlot;
+        uint64_t blocks = 0;
+        for (size_t k = 0; k < n;) {
+            if (d >= views[v].numDraws) { ++v; d = 0; continue; }
+            const vqhip_shadow_draw& D = views[v].draws[d++];
+            if (!D.mesh.numIndices) continue;
+            RasterJob& J = jobs[k++];
+            J.positions = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices; J.wvp = D.matWorldViewProj; J.world = D.matWorld;
+            J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numTris = D.mesh.numIndices / 3; J.numInstances = D.numInstances;
+            J.indexBits = D.mesh.indexBits; J.cullMode = D.cullMode; J.view = v; J.firstBlock = (uint32_t)blocks;
+            blocks += ((uint64_t)J.numTris * J.numInstances + 255) / 256;
+        }
+        if (int rc = commitSlot(ctx, slot, sizeof(RasterJob) * n, st)) return rc;
+        e = launch_raster_setup(st, (const RasterJob*)(ctx->devRing + (size_t)slot * kConstSlotBytes), (int)n, (uint32_t)blocks, dviews, counters, boxes, records);
+        if (e != hipSuccess) return failHip(ctx, e, "shadow_depth setup launch");
+        if (int rc = releaseSlot(ctx, slot, st)) return rc;
+        left -= n;
+    }
+    e = launch_raster_fill(st, dviews, numViews, (uint32_t)fillBlocks, tile, counters, boxes, records);
+    if (e != hipSuccess) return failHip(ctx, e, "shadow_depth fill launch");
+    return releaseSlot(ctx, viewSlot, st);
 }
 
 } // extern "C"

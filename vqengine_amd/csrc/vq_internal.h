@@ -30,6 +30,7 @@ struct Options {
     int diffuseForm = 0;        // "diffuse_form"      : 1 "texels", 2 "general" (default: footprint records)
     int specularForm = 0;       // "specular_form"     : 1 "general" (default: the branch-free sample with one validity flag)
     int diffuseSeqForm = 0;     // "diffuse_seq_form"  : 1 "lane" (default: k_conv_diffuse_ordered)
+    int rasterTile = 0;         // "raster_tile"       : 32 | 64 texels per side of k_raster_fill's tile (default 32, profiles/r14a_shadow_raster.md)
 };
 
 // Device-resident per-call constant block == the cbuffers b0/b1 of ForwardLighting.hlsl:76-77 plus the
@@ -248,6 +249,27 @@ hipError_t launch_cacao(hipStream_t s, const CacaoArgs& a, const VQ_CacaoConstan
 // Quality HIGHEST (vqhip_adaptive_cacao; §7.15): the three planes appended to the work buffer — the importance map and its pong, R8_UNORM iw x ih, and the load counter
 struct CacaoAdaptiveArgs { size_t offImportance, offImportancePong, offCounter; int iw, ih; };
 hipError_t launch_cacao_adaptive(hipStream_t s, const CacaoArgs& a, const CacaoAdaptiveArgs& ad, const VQ_CacaoConstants& shared, const VQ_CacaoConstants perPass[4]);
+
+// Shadow-map rasteriser (vqhip_shadow_depth, raster.hip; docs/DESIGN_DETAILS.md §7.16). The view table and the draw jobs travel in constant-ring slots.
+// Work buffer: 64 record counters (one per view), the records' texel boxes (8 B each), the records (80 B each); a view owns the region
+// [recBase, recBase + recCap) of both arrays, recCap = 6 x its instanced triangles.
+struct alignas(16) RasterView {
+    float* depth; uint64_t recBase, recCap;
+    uint32_t pitch;                  // floats per row
+    int32_t dim, linear;
+    uint32_t firstFillBlock;         // of k_raster_fill's grid
+    float cam[3]; float farPlane;
+};
+struct alignas(16) RasterJob {       // one vqhip_shadow_draw of one view
+    const uint8_t* positions; const void* indices; const VQ_matrix* wvp; const VQ_matrix* world;
+    uint32_t strideBytes, numVertices, numTris, numInstances;
+    int32_t indexBits, cullMode, view;
+    uint32_t firstBlock;             // of this k_raster_setup launch: ceil(numTris * numInstances / 256) blocks per job
+};
+static constexpr size_t kRasterBoxBytes = 8, kRasterRecordBytes = 80, kRasterCounterBytes = 256;
+hipError_t launch_raster_begin(hipStream_t s, uint32_t* counters, int numViews);
+hipError_t launch_raster_setup(hipStream_t s, const RasterJob* jobs, int numJobs, uint32_t blocks, const RasterView* views, uint32_t* counters, void* boxes, void* records);
+hipError_t launch_raster_fill(hipStream_t s, const RasterView* views, int numViews, uint32_t blocks, int tile, const uint32_t* counters, const void* boxes, const void* records);
 
 // launchers (each returns the hipError_t of the launch)
 hipError_t launch_forward_lighting(hipStream_t s, const ShadeArgs& a, bool hasEnv, bool hasCasters, int outFmt, const Options& opt);
