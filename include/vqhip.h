@@ -347,7 +347,8 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * Later additions to 3: vqhip_gbuffer_msaa, vqhip_forward_lighting_msaa; vqhip_msaa_surfaces, vqhip_msaa_resolve_surfaces, vqhip_depth_hierarchy (+ _bytes, _level_offset_bytes);
                                * vqhip_ssr_classify, vqhip_ssr_intersect; vqhip_ssr_prefilter, vqhip_ssr_resolve_temporal, VQHIP_FMT_R11G11B10_FLOAT; vqhip_ssr_reproject, vqhip_ssr_reproject_surfaces;
                                * VQ_CacaoConstants, vqhip_cacao (+ _work_bytes, _plane_offset_bytes); vqhip_adaptive_cacao (+ _work_bytes, _plane_offset_bytes) and three plane ids;
-                               * vqhip_shadow_depth (+ _work_bytes), vqhip_shadow_mesh / _draw / _view, VQHIP_CULL_*, option raster_tile */
+                               * vqhip_shadow_depth (+ _work_bytes), vqhip_shadow_mesh / _draw / _view, VQHIP_CULL_*, option raster_tile;
+                               * vqhip_scene_depth (+ _work_bytes), vqhip_scene_depth_draw / _targets */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -1122,6 +1123,64 @@ VQHIP_API size_t vqhip_shadow_depth_work_bytes(uint64_t instancedTriangles, int 
  * unknown cullMode, positions or matrices not 4-byte aligned, indices not aligned to their size, work not 256-byte aligned or workBytes below vqhip_shadow_depth_work_bytes of the
  * call's own triangle count; VQHIP_ERR_UNSUPPORTED for more than 20 000 draws or 2^31 triangle lanes in one call. */
 VQHIP_API int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_view* views, int numViews, void* work, size_t workBytes);
+
+/* ---- Main-view depth pre-pass: VQRenderer::RenderDepthPrePass (SceneRendering.cpp:1265-1363) == DepthPrePass.hlsl drawn through FDepthPrePassPSOs
+ * (PipelineStateObjects.cpp:1580-1635): the rasteriser above with the four things the Z pre-pass changes — a rectangular viewport {0, 0, W, H, 0, 1}, DepthClipEnable
+ * TRUE (two z planes), SampleDesc.Count 1 or 4 (D3D's standard 4x pattern, coverage per sample), and DepthFunc LESS with depth writes on, whose winner the call can
+ * report. docs/DESIGN_DETAILS.md §7.17 is the normative statement (V1 vertex stage = R1, V2 clipping against seven planes, V3 viewport, V4 sample positions, V5
+ * per-sample z/w and the depth test as one 64-bit minimum); tests/scene_depth_ref.py states it in numpy. V2's z planes (a guard band is as legal), V4's sample
+ * positions and V5's interpolation precision are UNPINNED against a D3D12 device (docs/WARP_CALIBRATION.md §5).
+ * Out of scope: the ENABLE_ALPHA_MASK variant, the tessellation and heightmap variants (the null heightmap's + 0.0f is kept), wireframe, the pass's normals target
+ * (vqhip_scene_normals_from_materials writes it from interpolants) and the interpolant planes themselves.
+ * Outputs (pitches in pixels, coverage_pitch in bytes, 0 = dense = width; every pointer but depth may be NULL):
+ *   depth           samples 1: float [height][pitch] — the `depth` of vqhip_depth_hierarchy; samples 4: float [height][pitch][4], 16-byte aligned — the depth_ms of
+ *                   vqhip_msaa_resolve_surfaces. An uncovered sample holds 1.0.
+ *   primitive       uint32, the shape (and at 4x the alignment) of depth: the sequence number of the primitive that owns the sample, 0xFFFFFFFF for none.
+ *                   q = first(draw) + instance * numTris + tri, first(draw) = the instanced triangles of the draws before: D3D's submission order. Among the
+ *                   fragments of a sample the smallest depth wins, and on equal depth bits the smallest q (LESS rejects the later equal fragment); a fragment whose
+ *                   saturated depth is 1.0 fails against the clear value and leaves depth and primitive untouched.
+ *   coverage[k], layerPrimitive[k]  (samples 4 only, k < layers <= 4): uint8 [height][coverage_pitch] masks in the representation vqhip_gbuffer_msaa and
+ *                   vqhip_msaa_surfaces read, and uint32 [height][pitch]. Per pixel, walking samples 0, 1, 2, 3: a sample with no owner belongs to no layer; a
+ *                   sample whose owner is the layerPrimitive of an open layer sets bit s of that layer's mask; otherwise it opens the next layer. Unused layers
+ *                   hold mask 0 and primitive 0xFFFFFFFF; bits 4-7 are 0; the masks are disjoint. A pixel has at most four owners: when `layers` is smaller than
+ *                   the pixel needs, the owners beyond it are DROPPED FROM THE LAYER PLANES ONLY (their samples are in no mask) — depth and primitive never change.
+ * Three kernels on `stream` (plus one setup launch per further ~700 draws): counter, triangle setup, tile fill. No allocation, no memset node, no readback; the
+ * call clears its own outputs (numDraws == 0 yields all 1.0 / 0xFFFFFFFF / mask 0). Draw descriptors are host memory, consumed before the call returns; meshes and
+ * matrices are device memory, read when the kernels run. The outputs must not overlap the work buffer. Option raster_tile 64 is honoured at samples 1; at samples 4
+ * the tile stays 32 x 32 (64 x 64 x 4 keys would be 128 KiB of LDS). */
+typedef struct vqhip_scene_depth_draw {  /* one DrawIndexedInstanced of RenderDepthPrePass */
+    vqhip_shadow_mesh mesh;
+    const VQ_matrix* matWorldViewProj;  /* device, [numInstances]: PerObjectData.matWorldViewProj */
+    uint32_t numInstances;              /* 1 .. 64 (MAX_INSTANCE_COUNT__SCENE_MESHES) */
+    int32_t  cullMode;                  /* VQHIP_CULL_NONE | _FRONT | _BACK */
+} vqhip_scene_depth_draw;
+typedef struct vqhip_scene_depth_targets {   /* device pointers */
+    float*    depth;
+    uint32_t* primitive;                /* or NULL */
+    uint8_t*  coverage[4];              /* [k] or NULL, k < layers */
+    uint32_t* layerPrimitive[4];        /* [k] or NULL, k < layers */
+    int32_t   layers;                   /* 0 .. 4; must be 0 when samples == 1 */
+    int32_t   pitch;                    /* pixels per row of depth, primitive and layerPrimitive; 0 = width */
+    int32_t   coverage_pitch;           /* bytes per row of coverage; 0 = width */
+    int32_t   reserved;                 /* 0 */
+} vqhip_scene_depth_targets;
+VQHIP_STATIC_ASSERT(sizeof(vqhip_scene_depth_draw) == 48 && offsetof(vqhip_scene_depth_draw, numInstances) == 40, "vqhip_scene_depth_draw layout");
+VQHIP_STATIC_ASSERT(sizeof(vqhip_scene_depth_targets) == 96 && offsetof(vqhip_scene_depth_targets, layers) == 80, "vqhip_scene_depth_targets layout");
+#define VQHIP_SCENE_DEPTH_MAX_DIM 8192
+#define VQHIP_SCENE_DEPTH_MAX_INSTANCES 64
+#define VQHIP_SCENE_DEPTH_MAX_LAYERS 4
+/* Bytes of work for a call that draws `instancedTriangles` triangles (sum over draws of numIndices / 3 * numInstances): eight records per triangle (a triangle
+ * clipped by seven planes is a fan of at most eight). 0 for a count of 2^29 or more, or a size that does not fit size_t. Host-only. */
+VQHIP_API size_t vqhip_scene_depth_work_bytes(uint64_t instancedTriangles);
+/* Returns VQHIP_ERR_INVALID_ARG — launching nothing, leaving the outputs untouched — for NULL pointers (ctx, out, out->depth, draws with numDraws > 0, a mesh's
+ * positions or indices, matWorldViewProj, work), samples other than 1 or 4, layers outside 0 .. 4 or not 0 at samples 1, width or height outside 1 .. 8192, a pitch
+ * below width (either kind) or negative, reserved != 0, depth or primitive not 4-byte (samples 1) / 16-byte (samples 4) aligned, layerPrimitive not 4-byte aligned,
+ * numDraws < 0, an indexBits other than 16 / 32, numIndices % 3 != 0, a stride below 12 or not a multiple of 4, numInstances outside 1 .. 64, an unknown cullMode,
+ * positions or matrices not 4-byte aligned, indices not aligned to their size, work not 256-byte aligned, workBytes below vqhip_scene_depth_work_bytes of the call's
+ * own triangle count, or an output that overlaps the work buffer; VQHIP_ERR_UNSUPPORTED for 2^29 or more instanced triangles (q must stay below the no-owner value, which
+ * alone would allow up to 2^32 - 2; eight records per triangle must also fit the 32-bit record counter) or more than 20 000 draws in one call. */
+VQHIP_API int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_depth_draw* draws, int numDraws, int width, int height, int samples,
+        const vqhip_scene_depth_targets* out, void* work, size_t workBytes);
 
 #ifdef __cplusplus
 }

@@ -563,6 +563,61 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// Z pre-pass, depth half == VQRenderer::RenderDepthPrePass (SceneRendering.cpp:1265-1363) through FDepthPrePassPSOs: vqhip_scene_depth. FDrawParameters carries
+// what the function holds: the main view's draw list (FSceneDrawData::mainViewDrawParams, each FInstancedDrawParameters as a vqhip_scene_depth_draw whose matrices
+// are the uploaded PerObjectData), the stream and the depth target (DSV_SceneDepthMSAA when bMSAA, else DSV_SceneDepth, as R32F memory). W and H are the window's
+// (OnCreateWindowSizeDependentResources, the viewport of :1330); bMSAA selects 4 samples, the engine's default, else 1. The primitive and layer planes are the
+// library's addition (the masks vqhip_forward_lighting_msaa and vqhip_msaa_resolve_surfaces read); leave them NULL for the engine's own outputs. The pass's
+// normals target stays with vqhip_scene_normals_from_materials. The pass owns the work buffer, as ShadowDepthPass does.
+// ---------------------------------------------------------------------------------------------------------------
+class DepthPrePass : public RenderPassBase {
+public:
+    struct FResourceParameters : public IRenderPassResourceCollection {};
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        const std::vector<vqhip_scene_depth_draw>* Draws = nullptr;             // nullptr or empty: the target is cleared (:1318 clears before the draw loop)
+        bool bMSAA = true;                                                      // SceneView.sceneParameters.bMSAA (:1268)
+        float* SceneDepth = nullptr;                                            // [H][W] or, bMSAA, [H][W][4]
+        uint32_t* Primitive = nullptr;                                          // optional, the shape of SceneDepth
+        int NumLayers = 0;                                                      // bMSAA only
+        uint8_t* Coverage[VQHIP_SCENE_DEPTH_MAX_LAYERS] = {};
+        uint32_t* LayerPrimitive[VQHIP_SCENE_DEPTH_MAX_LAYERS] = {};
+    };
+    explicit DepthPrePass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    ~DepthPrePass() override { Free(mWork); }
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { Free(mWork); mWorkBytes = 0; }
+    void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override { mWidth = Width; mHeight = Height; }
+    void OnDestroyWindowSizeDependentResources() override { mWidth = mHeight = 0; }
+    bool Reserve(uint64_t InstancedTriangles) {
+        const size_t need = vqhip_scene_depth_work_bytes(InstancedTriangles);
+        if (!need) return false;
+        if (need <= mWorkBytes) return true;
+        Free(mWork); mWorkBytes = 0;
+        mWork = Alloc(need);
+        if (mWork) mWorkBytes = need;
+        return mWork != nullptr;
+    }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p || p->NumLayers < 0 || p->NumLayers > VQHIP_SCENE_DEPTH_MAX_LAYERS) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        uint64_t triangles = 0;
+        const int numDraws = p->Draws ? (int)p->Draws->size() : 0;
+        for (int d = 0; d < numDraws; ++d) triangles += (uint64_t)((*p->Draws)[d].mesh.numIndices / 3) * (*p->Draws)[d].numInstances;
+        if (!Reserve(triangles)) { mStatus = VQHIP_ERR_HIP; return; }
+        vqhip_scene_depth_targets t = {};
+        t.depth = p->SceneDepth; t.primitive = p->Primitive; t.layers = p->bMSAA ? p->NumLayers : 0;
+        for (int k = 0; k < t.layers; ++k) { t.coverage[k] = p->Coverage[k]; t.layerPrimitive[k] = p->LayerPrimitive[k]; }
+        mStatus = vqhip_scene_depth(mCtx, p->Stream, numDraws ? p->Draws->data() : nullptr, numDraws, (int)mWidth, (int)mHeight, p->bMSAA ? 4 : 1, &t, mWork, mWorkBytes);
+    }
+    const void* GetWorkBuffer() const { return mWork; }
+    size_t GetWorkBytes() const { return mWorkBytes; }
+private:
+    void* mWork = nullptr; size_t mWorkBytes = 0;
+    unsigned mWidth = 0, mHeight = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // Reflection denoiser, pass 1 == the "FFX DNSR Reproject" dispatch of ScreenSpaceReflectionsPass::RecordCommands: vqhip_ssr_reproject. Buffer roles as
 // ScreenSpaceReflections.cpp:1177-1198 binds them for frame index i: reads the surfaces of this frame and their history copies, TexRadiance[i] (what the march
 // wrote), TexRadiance[1 - i] (last frame's resolved radiance), the motion vectors, TexVariance[1 - i] and TexSampleCount[1 - i]; writes TexReprojectedRadiance,

@@ -244,6 +244,21 @@ class ShadowView(C.Structure):  # vqhip_shadow_view
                 ("draws", C.POINTER(ShadowDraw)), ("numDraws", C.c_int32)]
 
 
+SCENE_DEPTH_MAX_DIM = 8192                   # VQHIP_SCENE_DEPTH_MAX_DIM
+SCENE_DEPTH_MAX_INSTANCES = 64               # VQHIP_SCENE_DEPTH_MAX_INSTANCES == MAX_INSTANCE_COUNT__SCENE_MESHES
+SCENE_DEPTH_MAX_LAYERS = 4                   # VQHIP_SCENE_DEPTH_MAX_LAYERS
+NO_PRIMITIVE = 0xFFFFFFFF                    # vqhip_scene_depth's primitive / layerPrimitive value for "no owner"
+
+
+class SceneDepthDraw(C.Structure):  # vqhip_scene_depth_draw
+    _fields_ = [("mesh", ShadowMesh), ("matWorldViewProj", C.c_void_p), ("numInstances", C.c_uint32), ("cullMode", C.c_int32)]
+
+
+class SceneDepthTargets(C.Structure):  # vqhip_scene_depth_targets
+    _fields_ = [("depth", C.c_void_p), ("primitive", C.c_void_p), ("coverage", C.c_void_p * 4), ("layerPrimitive", C.c_void_p * 4), ("layers", C.c_int32),
+                ("pitch", C.c_int32), ("coverage_pitch", C.c_int32), ("reserved", C.c_int32)]
+
+
 def _chk(t, size, **offs):
     assert C.sizeof(t) == size, (t.__name__, C.sizeof(t), size)
     for k, v in offs.items():
@@ -270,6 +285,8 @@ _chk(BlurParams, 8)
 _chk(SSSRConstants, 512, bufferDimensions=448, roughnessThreshold=472, envMapSpecularIrradianceCubemapMipLevelCount=504)
 _chk(ShadowMesh, 32, strideBytes=8, numVertices=12, indices=16, indexBits=24, numIndices=28)
 _chk(ShadowDraw, 56, matWorldViewProj=32, matWorld=40, numInstances=48, cullMode=52)
+_chk(SceneDepthDraw, 48, matWorldViewProj=32, numInstances=40, cullMode=44)
+_chk(SceneDepthTargets, 96, primitive=8, coverage=16, layerPrimitive=48, layers=80, pitch=84, coverage_pitch=88, reserved=92)
 _chk(ShadowView, 56, pitchBytes=8, dim=16, linearDepth=20, cameraPosition=24, farPlane=36, draws=40, numDraws=48)
 _chk(CacaoConstants, 384, EffectRadius=48, InvSharpness=96, PassIndex=100, PatternRotScaleMatrices=112, NormalsUnpackMul=192, SSAOBufferDimensions=208,
      DepthBufferOffset=240, PerPassFullResUVOffset=248, DeinterleavedDepthBufferNormalisedOffset=312, NormalsWorldToViewspaceMatrix=320)

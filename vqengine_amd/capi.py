@@ -112,6 +112,8 @@ def load_library():
         "vqhip_adaptive_cacao": (i32, [vp, vp, vp, sz, vp, i32, sz, C.POINTER(abi.CacaoConstants), C.POINTER(abi.CacaoConstants), i32, vp, sz, vp, sz, i32, i32]),
         "vqhip_shadow_depth_work_bytes": (sz, [C.c_uint64, i32]),
         "vqhip_shadow_depth": (i32, [vp, vp, C.POINTER(abi.ShadowView), i32, vp, sz]),
+        "vqhip_scene_depth_work_bytes": (sz, [C.c_uint64]),
+        "vqhip_scene_depth": (i32, [vp, vp, C.POINTER(abi.SceneDepthDraw), i32, i32, i32, i32, C.POINTER(abi.SceneDepthTargets), vp, sz]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -147,7 +149,13 @@ EXPORTED_SYMBOLS = [
     "vqhip_cacao", "vqhip_cacao_work_bytes", "vqhip_cacao_plane_offset_bytes",
     "vqhip_adaptive_cacao", "vqhip_adaptive_cacao_work_bytes", "vqhip_adaptive_cacao_plane_offset_bytes",
     "vqhip_shadow_depth", "vqhip_shadow_depth_work_bytes",
+    "vqhip_scene_depth", "vqhip_scene_depth_work_bytes",
 ]
+
+
+def scene_depth_work_bytes(instanced_triangles):
+    """vqhip_scene_depth_work_bytes: the work buffer of a vqhip_scene_depth call that draws `instanced_triangles` triangles in all. Host-only."""
+    return load_library().vqhip_scene_depth_work_bytes(int(instanced_triangles))
 
 
 def shadow_depth_work_bytes(instanced_triangles, num_views):
@@ -622,6 +630,100 @@ class Context:
         def call(stream=None, _keep=keep):
             self._ck(self.lib.vqhip_shadow_depth(self._h, self._stream(stream), cviews, len(views), _ptr(work), work.numel()))
         return call, work
+
+    def scene_depth(self, draws, width, height, samples=1, primitive=False, layers=0, layer_primitive=True, out=None, work=None, stream=None):
+        """vqhip_scene_depth: rasterise the ShadowDraw list `draws` (world ignored; at most 64 instances each) as the main view's depth pre-pass into a
+        width x height target of `samples` (1 | 4) samples. primitive: also return the owning primitive's sequence number per sample; layers (samples 4):
+        the number of coverage-mask layers to return, with their primitives when layer_primitive. out: a dict of preallocated tensors under the keys of the
+        result (their row strides are the pitches), else they are allocated dense. Returns a dict: depth float32 [H,W] | [H,W,4], primitive int32 of the same
+        shape (the bits are uint32; -1 = no owner), coverage [layers] uint8 [H,W], layer_primitive [layers] int32 [H,W], work."""
+        call, res = self.scene_depth_prepared(draws, width, height, samples, primitive, layers, layer_primitive, out, work)
+        call(stream)
+        return res
+
+    def scene_depth_prepared(self, draws, width, height, samples=1, primitive=False, layers=0, layer_primitive=True, out=None, work=None):
+        """The descriptors of a scene_depth call built once: returns (call, result) with call(stream=None) issuing vqhip_scene_depth on the same draws and
+        targets again. The tensors must stay alive and in place."""
+        draws, out = list(draws), dict(out or {})
+        w, h = int(width), int(height)
+        if samples not in (1, 4):
+            raise ValueError(f"scene_depth: samples: expected 1 or 4, got {samples}")
+        if not 0 <= layers <= abi.SCENE_DEPTH_MAX_LAYERS or (samples == 1 and layers):
+            raise ValueError("scene_depth: layers: expected 0..4, and 0 at samples 1")
+        if not (1 <= w <= abi.SCENE_DEPTH_MAX_DIM and 1 <= h <= abi.SCENE_DEPTH_MAX_DIM):
+            raise ValueError(f"scene_depth: width and height must be 1..{abi.SCENE_DEPTH_MAX_DIM}")
+        shape = (h, w) if samples == 1 else (h, w, 4)
+
+        def plane(key, dtype, shp, t):
+            if t is None:
+                t = torch.empty(shp, dtype=dtype, device=self.device)
+            px = 1 if len(shp) == 2 else shp[2]
+            if not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == tuple(shp) and t.stride(-1) == 1 and (len(shp) == 2 or t.stride(1) == px)
+                    and t.stride(0) % px == 0 and t.stride(0) >= w * px):
+                raise ValueError(f"scene_depth: {key}: expected cuda {dtype} {tuple(shp)} with dense pixels, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+            return t, t.stride(0) // px
+        res, pitches, cov_pitches = {}, set(), set()
+        res["depth"], p = plane("depth", torch.float32, shape, out.get("depth"))
+        pitches.add(p)
+        if primitive:
+            res["primitive"], p = plane("primitive", torch.int32, shape, out.get("primitive"))
+            pitches.add(p)
+        if layers:
+            given = list(out.get("coverage") or [None] * layers)
+            res["coverage"] = []
+            for k in range(layers):
+                t, p = plane("coverage", torch.uint8, (h, w), given[k])
+                res["coverage"].append(t)
+                cov_pitches.add(p)
+            if layer_primitive:
+                given = list(out.get("layer_primitive") or [None] * layers)
+                res["layer_primitive"] = []
+                for k in range(layers):
+                    t, p = plane("layer_primitive", torch.int32, (h, w), given[k])
+                    res["layer_primitive"].append(t)
+                    pitches.add(p)
+        if len(pitches) != 1 or len(cov_pitches) > 1:
+            raise ValueError("scene_depth: depth, primitive and layer_primitive share one pitch in pixels, the coverage planes one pitch in bytes")
+        cdraws = (abi.SceneDepthDraw * max(1, len(draws)))()
+        tris = 0
+        for j, dr in enumerate(draws):
+            who = f"scene_depth: draw {j}"
+            p, ix = dr.positions, dr.indices
+            if not (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and p.shape[1] >= 3 and p.stride(1) == 1 and p.stride(0) >= p.shape[1]):
+                raise ValueError(f"{who}: positions: expected cuda float32 [V, k >= 3] with unit column stride")
+            bits = {2: 16, 4: 32}.get(ix.element_size()) if not ix.dtype.is_floating_point else None
+            if not (ix.is_cuda and ix.dim() == 1 and ix.is_contiguous() and bits and ix.numel() % 3 == 0):
+                raise ValueError(f"{who}: indices: expected a contiguous cuda 1-D 16-bit or 32-bit integer tensor whose length is a multiple of 3")
+            m = dr.wvp
+            if not (m.is_cuda and m.dtype == torch.float32 and m.dim() == 3 and tuple(m.shape[1:]) == (4, 4) and m.is_contiguous()):
+                raise ValueError(f"{who}: wvp: expected cuda float32 [n, 4, 4] contiguous")
+            if not 1 <= m.shape[0] <= abi.SCENE_DEPTH_MAX_INSTANCES:
+                raise ValueError(f"{who}: 1..{abi.SCENE_DEPTH_MAX_INSTANCES} instances, got {m.shape[0]}")
+            if dr.cull not in (abi.CULL_NONE, abi.CULL_FRONT, abi.CULL_BACK):
+                raise ValueError(f"{who}: cull: expected abi.CULL_NONE, CULL_FRONT or CULL_BACK")
+            c = cdraws[j]
+            c.mesh.positions, c.mesh.strideBytes, c.mesh.numVertices = p.data_ptr(), p.stride(0) * 4, p.shape[0]
+            c.mesh.indices, c.mesh.indexBits, c.mesh.numIndices = ix.data_ptr(), bits, ix.numel()
+            c.matWorldViewProj, c.numInstances, c.cullMode = m.data_ptr(), m.shape[0], dr.cull
+            tris += (ix.numel() // 3) * m.shape[0]
+        need = scene_depth_work_bytes(tris)
+        if work is None:
+            work = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.numel() >= need and need):
+            raise ValueError(f"scene_depth: work: expected a contiguous cuda uint8 tensor of at least {need} bytes (0: too many triangles)")
+        res["work"] = work
+        tg = abi.SceneDepthTargets()
+        tg.depth = res["depth"].data_ptr()
+        tg.primitive = res["primitive"].data_ptr() if primitive else None
+        for k in range(layers):
+            tg.coverage[k] = res["coverage"][k].data_ptr()
+            tg.layerPrimitive[k] = res["layer_primitive"][k].data_ptr() if layer_primitive else None
+        tg.layers, tg.pitch, tg.coverage_pitch = layers, pitches.pop(), (cov_pitches.pop() if cov_pitches else 0)
+        keep = (draws, res)
+
+        def call(stream=None, _keep=keep):
+            self._ck(self.lib.vqhip_scene_depth(self._h, self._stream(stream), cdraws, len(draws), w, h, samples, C.byref(tg), _ptr(work), work.numel()))
+        return call, res
 
     def msaa_resolve_surfaces(self, depth_ms, coverage=None, normals=None, normals_fmt=abi.FMT_R10G10B10A2_UNORM, roughness=None, background=None,
                               out_depth=False, out_normals_fmt=None, scene_color=None, scene_fmt=FMT_RGBA16F, hierarchy=False, flags=0, stream=None):

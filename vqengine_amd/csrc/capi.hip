@@ -1912,4 +1912,116 @@ int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_view* vi
     return releaseSlot(ctx, viewSlot, st);
 }
 
+// ---- Main-view depth pre-pass (raster_view.hip; docs/DESIGN_DETAILS.md §7.17) ------------------------------------------------------------------------------------
+namespace {
+constexpr size_t kSceneJobsPerSlot = kConstSlotBytes / sizeof(SceneDepthJob);
+constexpr uint64_t kSceneMaxTriangles = (uint64_t)1 << 29;     // eight records each: the record counter is 32 bits wide; q stays far below 0xFFFFFFFF
+static_assert((kRasterMaxDraws + kSceneJobsPerSlot - 1) / kSceneJobsPerSlot < vqhip_ctx::kSlots, "one call never laps the ring");
+// counter | boxes[8 n] | records[8 n]; false when the sizes do not fit
+bool sceneDepthLayout(uint64_t instancedTriangles, size_t* boxes, size_t* records, size_t* total) {
+    if (instancedTriangles >= kSceneMaxTriangles) return false;
+    const uint64_t cap = instancedTriangles * kSceneFanMax;
+    const uint64_t b = kSceneCounterBytes, r = align256(b + cap * kSceneBoxBytes), t = align256(r + cap * kSceneRecordBytes);
+    if (t > (uint64_t)SIZE_MAX) return false;
+    *boxes = (size_t)b; *records = (size_t)r; *total = (size_t)t;
+    return true;
+}
+} // namespace
+
+size_t vqhip_scene_depth_work_bytes(uint64_t instancedTriangles) {
+    size_t b, r, t;
+    return sceneDepthLayout(instancedTriangles, &b, &r, &t) ? t : 0;
+}
+
+int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_depth_draw* draws, int numDraws, int width, int height, int samples,
+                      const vqhip_scene_depth_targets* out, void* work, size_t workBytes) {
+    vqk::Range range_("RenderDepthPrePass");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "scene_depth: ctx is NULL");
+    CTX_GUARD(ctx, "scene_depth");
+    auto bad = [&](const std::string& m) { return fail(ctx, VQHIP_ERR_INVALID_ARG, "scene_depth: " + m); };
+    if (!out || !out->depth || !work) return bad("NULL argument (out, out->depth or work)");
+    if (numDraws < 0 || (numDraws > 0 && !draws)) return bad("numDraws < 0, or draws is NULL");
+    if (samples != 1 && samples != 4) return bad("samples must be 1 or 4");
+    if (width < 1 || width > VQHIP_SCENE_DEPTH_MAX_DIM || height < 1 || height > VQHIP_SCENE_DEPTH_MAX_DIM) return bad("width and height must be 1..8192");
+    if (out->layers < 0 || out->layers > VQHIP_SCENE_DEPTH_MAX_LAYERS) return bad("layers must be 0..4");
+    if (samples == 1 && out->layers != 0) return bad("layers are defined at samples == 4 only");
+    if (out->reserved != 0) return bad("reserved must be 0");
+    if (out->pitch < 0 || out->coverage_pitch < 0) return bad("negative pitch");
+    const size_t pitch = out->pitch ? (size_t)out->pitch : (size_t)width, covPitch = out->coverage_pitch ? (size_t)out->coverage_pitch : (size_t)width;
+    if (pitch < (size_t)width || covPitch < (size_t)width) return bad("a pitch below width");
+    const size_t px = (size_t)samples * 4;                     // bytes per pixel of depth / primitive
+    if ((uintptr_t)out->depth % px || (uintptr_t)out->primitive % px) return bad("depth / primitive must be 4-byte (samples 1) or 16-byte (samples 4) aligned");
+    if ((uintptr_t)work % 256) return bad("work must be 256-byte aligned");
+    for (int k = 0; k < out->layers; ++k) if ((uintptr_t)out->layerPrimitive[k] % 4) return bad("layerPrimitive must be 4-byte aligned");
+    uint64_t totalTris = 0;
+    size_t numJobs = 0;
+    for (int d = 0; d < numDraws; ++d) {
+        const vqhip_scene_depth_draw& D = draws[d];
+        auto badDraw = [&](const char* m) { return bad("draw " + std::to_string(d) + ": " + m); };
+        if (!D.mesh.positions || !D.mesh.indices || !D.matWorldViewProj) return badDraw("positions, indices or matWorldViewProj is NULL");
+        if (D.mesh.indexBits != 16 && D.mesh.indexBits != 32) return badDraw("indexBits must be 16 or 32");
+        if (D.mesh.numIndices % 3) return badDraw("numIndices is not a multiple of 3");
+        if (D.mesh.strideBytes < 12 || D.mesh.strideBytes % 4) return badDraw("strideBytes below 12 or not a multiple of 4");
+        if (D.numInstances < 1 || D.numInstances > VQHIP_SCENE_DEPTH_MAX_INSTANCES) return badDraw("numInstances must be 1..64");
+        if (D.cullMode != VQHIP_CULL_NONE && D.cullMode != VQHIP_CULL_FRONT && D.cullMode != VQHIP_CULL_BACK) return badDraw("unknown cullMode");
+        if ((uintptr_t)D.mesh.positions % 4 || (uintptr_t)D.matWorldViewProj % 4 || (uintptr_t)D.mesh.indices % (D.mesh.indexBits / 8))
+            return badDraw("positions / matrices must be 4-byte aligned, indices aligned to their size");
+        if (D.mesh.numIndices) { totalTris += (uint64_t)(D.mesh.numIndices / 3) * D.numInstances; ++numJobs; }
+    }
+    if (totalTris >= kSceneMaxTriangles) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "scene_depth: 2^29 or more instanced triangles in one call");
+    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "scene_depth: more than 20000 draws in one call");
+    size_t offBoxes, offRecords, need;
+    if (!sceneDepthLayout(totalTris, &offBoxes, &offRecords, &need) || workBytes < need)
+        return bad("workBytes below vqhip_scene_depth_work_bytes(the call's instanced triangles)");
+    const size_t rows = (size_t)(height - 1);
+    bool overlap = rangesOverlap(work, need, out->depth, (rows * pitch + width) * px) ||
+                   (out->primitive && rangesOverlap(work, need, out->primitive, (rows * pitch + width) * px));
+    for (int k = 0; k < out->layers; ++k)
+        overlap = overlap || (out->coverage[k] && rangesOverlap(work, need, out->coverage[k], rows * covPitch + width)) ||
+                  (out->layerPrimitive[k] && rangesOverlap(work, need, out->layerPrimitive[k], (rows * pitch + width) * 4));
+    if (overlap) return bad("an output overlaps the work buffer");
+
+    SceneDepthArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.depth = out->depth; a.primitive = out->primitive;
+    for (int k = 0; k < out->layers; ++k) { a.coverage[k] = out->coverage[k]; a.layerPrimitive[k] = out->layerPrimitive[k]; }
+    a.recCap = totalTris * kSceneFanMax; a.pitch = (uint32_t)pitch; a.coveragePitch = (uint32_t)covPitch;
+    a.width = width; a.height = height; a.samples = samples; a.layers = out->layers;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* counter = (uint32_t*)work;
+    void* boxes = (char*)work + offBoxes;
+    void* records = (char*)work + offRecords;
+    hipError_t e = launch_raster_begin(st, counter, 1);
+    if (e != hipSuccess) return failHip(ctx, e, "scene_depth counter launch");
+    // the draws, in ring slots of kSceneJobsPerSlot jobs: one setup launch per slot
+    int d = 0;
+    size_t left = numJobs;
+    uint64_t firstQ = 0;
+    while (left) {
+        int slot;
+        if (int rc = acquireSlot(ctx, &slot)) return rc;
+        SceneDepthJob* jobs = (SceneDepthJob*)(ctx->hostRing + (size_t)slot * kConstSlotBytes);
+        const size_t n = left < kSceneJobsPerSlot ? left : kSceneJobsPerSlot;
+        uint64_t blocks = 0;
+        for (size_t k = 0; k < n;) {
+            const vqhip_scene_depth_draw& D = draws[d++];
+            if (!D.mesh.numIndices) continue;
+            SceneDepthJob& J = jobs[k++];
+            J.positions = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices; J.wvp = D.matWorldViewProj;
+            J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numTris = D.mesh.numIndices / 3; J.numInstances = D.numInstances;
+            J.indexBits = D.mesh.indexBits; J.cullMode = D.cullMode; J.firstBlock = (uint32_t)blocks; J.firstQ = (uint32_t)firstQ;
+            blocks += ((uint64_t)J.numTris * J.numInstances + 255) / 256;
+            firstQ += (uint64_t)J.numTris * J.numInstances;
+        }
+        if (int rc = commitSlot(ctx, slot, sizeof(SceneDepthJob) * n, st)) return rc;
+        e = launch_scene_setup(st, (const SceneDepthJob*)(ctx->devRing + (size_t)slot * kConstSlotBytes), (int)n, (uint32_t)blocks, a, counter, boxes, records);
+        if (e != hipSuccess) return failHip(ctx, e, "scene_depth setup launch");
+        if (int rc = releaseSlot(ctx, slot, st)) return rc;
+        left -= n;
+    }
+    e = launch_scene_fill(st, a, scene_depth_tile(ctx->opt.rasterTile, samples), counter, boxes, records);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "scene_depth fill launch");
+}
+
 } // extern "C"

@@ -271,6 +271,28 @@ hipError_t launch_raster_begin(hipStream_t s, uint32_t* counters, int numViews);
 hipError_t launch_raster_setup(hipStream_t s, const RasterJob* jobs, int numJobs, uint32_t blocks, const RasterView* views, uint32_t* counters, void* boxes, void* records);
 hipError_t launch_raster_fill(hipStream_t s, const RasterView* views, int numViews, uint32_t blocks, int tile, const uint32_t* counters, const void* boxes, const void* records);
 
+// Main-view depth pre-pass (vqhip_scene_depth, raster_view.hip; docs/DESIGN_DETAILS.md §7.17). The draw jobs travel in constant-ring slots, the targets as kernel arguments.
+// Work buffer: one record counter (256 B), the records' pixel boxes (8 B each), the records (48 B each: three snapped vertices, three z/w, q); recCap = 8 x the
+// call's instanced triangles (a triangle clipped by seven planes is a fan of at most eight).
+struct SceneDepthArgs {
+    float* depth; uint32_t* primitive;
+    uint8_t* coverage[4]; uint32_t* layerPrimitive[4];
+    uint64_t recCap;
+    uint32_t pitch, coveragePitch;   // pixels per row of depth / primitive / layerPrimitive; bytes per row of coverage
+    int32_t width, height, samples, layers;
+};
+struct alignas(16) SceneDepthJob {   // one vqhip_scene_depth_draw
+    const uint8_t* positions; const void* indices; const VQ_matrix* wvp;
+    uint32_t strideBytes, numVertices, numTris, numInstances;
+    int32_t indexBits, cullMode;
+    uint32_t firstBlock;             // of this k_scene_setup launch: ceil(numTris * numInstances / 256) blocks per job
+    uint32_t firstQ;                 // sequence number of (instance 0, triangle 0): the instanced triangles of the draws before
+};
+static constexpr size_t kSceneBoxBytes = 8, kSceneRecordBytes = 48, kSceneCounterBytes = 256, kSceneFanMax = 8;
+int scene_depth_tile(int rasterTile, int samples);      // pixels per side of k_scene_fill's tile: the option where the LDS budget allows it (not 64 at 4x), else 32
+hipError_t launch_scene_setup(hipStream_t s, const SceneDepthJob* jobs, int numJobs, uint32_t blocks, const SceneDepthArgs& a, uint32_t* counter, void* boxes, void* records);
+hipError_t launch_scene_fill(hipStream_t s, const SceneDepthArgs& a, int tile, const uint32_t* counter, const void* boxes, const void* records);
+
 // launchers (each returns the hipError_t of the launch)
 hipError_t launch_forward_lighting(hipStream_t s, const ShadeArgs& a, bool hasEnv, bool hasCasters, int outFmt, const Options& opt);
 hipError_t launch_blur_x(hipStream_t s, const void* in, void* out, int W, int H, int fmt, const Options& opt);

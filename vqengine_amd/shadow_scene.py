@@ -1,4 +1,5 @@
-"""Host-side producers of what vqhip_shadow_depth consumes: procedural meshes, instance transforms and light view-projections. numpy only.
+"""Host-side producers of what vqhip_shadow_depth and vqhip_scene_depth consume: procedural meshes, instance transforms, light view-projections and the main
+camera's. numpy only.
 
 Everything here is an INPUT of the library: the rasteriser reads positions, indices and VQ_matrix blocks as handed over, so this module is a valid producer of
 them and is not bit-pinned to DirectXMath (its matrices are formed in binary64 and rounded once; XMMatrixLookAtLH / XMMatrixPerspectiveFovLH work in binary32
@@ -161,6 +162,12 @@ def point_face_view_proj(position, face, near, far):
     position = np.asarray(position, dtype=np.float64)
     look, up = CUBE_FACES[face]
     return look_at_lh(position, position + np.asarray(look, dtype=np.float64), up) @ perspective_fov_lh(0.5 * np.pi, 1.0, near, far)
+
+
+def camera_view_proj(eye, at, fov_y, aspect, near, far, up=(0.0, 1.0, 0.0)):
+    """The main camera of vqhip_scene_depth: Camera::UpdateViewMatrix x XMMatrixPerspectiveFovLH (Camera.cpp) — look from `eye` at `at`, perspective, left-handed,
+    depth 0 .. 1, aspect = width / height of the viewport."""
+    return look_at_lh(eye, at, up) @ perspective_fov_lh(fov_y, aspect, near, far)
 
 
 def instance_matrices(worlds, view_proj):
