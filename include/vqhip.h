@@ -276,8 +276,9 @@ VQHIP_STATIC_ASSERT(sizeof(vqhip_material) == 256 && offsetof(vqhip_material, te
  *   ip0 = (WorldSpacePosition.xyz, uv.x)
  *   ip1 = (WorldSpaceNormal.xyz,   uv.y)
  *   ip2 = (WorldSpaceTangent.xyz,  asfloat(int32 materialIndex))   materialIndex < 0: no geometry
- * SV_POSITION.xy is implied: (x + 0.5, y + 0.5). Producing these planes (VS + rasteriser, or a
- * visibility-buffer resolve) stays with the caller. */
+ * SV_POSITION.xy is implied: (x + 0.5, y + 0.5). vqhip_scene_interpolants produces these planes from
+ * meshes and the owner plane of vqhip_scene_depth (a visibility-buffer resolve); a caller with a
+ * rasteriser of its own may hand over its planes instead. */
 typedef struct vqhip_interpolants {
     const void* ip0; const void* ip1; const void* ip2;
     int32_t width, height, row_pitch_px;
@@ -332,7 +333,7 @@ VQHIP_API int  vqhip_set_fresnel_pow(vqhip_ctx* ctx, vqhip_fresnel_pow mode);
  * undefined behaviour, and VQEngine records on many threads, SceneRendering.cpp:563-706). value NULL, "" or "default" restores the default. Every
  * form selected here gives the bits of the default form (tests/test_gpu_conv_forms.py, tests/test_gpu_round3.py); unknown keys / values: VQHIP_ERR_INVALID_ARG.
  *   shade_wg 64|128|256 · psmain_waves 4|5|6 · blur_y_wgs n · post_form two|chain · post_strips n · lut_form general ·
- *   specular_form general · diffuse_form records|texels|general · diffuse_seq_form ordered|lane · raster_tile 32|64
+ *   specular_form general · diffuse_form records|texels|general · diffuse_seq_form ordered|lane · raster_tile 32|64 · interp_form lane|wave
  * (the non-default values are the general / fallback forms of the same kernels; the measured-and-rejected kernel forms of rounds 2-5 — the compact tonemap
  * tables, the per-sample LUT and per-mip specular kernels, the persistent X pass, the rolling-ring Y pass — are not in the library: docs/HISTORY.md).
  * psmain_waves applies to the literal reading only (the DXC-reading instantiation of the fused PSMain kernel has one register cap). post_form: "two" = vqhip_post_process[_tile] always runs blur X, then blur Y + tonemap (two kernels); "chain" = the one-kernel chain whatever the frame size
@@ -348,7 +349,8 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * vqhip_ssr_classify, vqhip_ssr_intersect; vqhip_ssr_prefilter, vqhip_ssr_resolve_temporal, VQHIP_FMT_R11G11B10_FLOAT; vqhip_ssr_reproject, vqhip_ssr_reproject_surfaces;
                                * VQ_CacaoConstants, vqhip_cacao (+ _work_bytes, _plane_offset_bytes); vqhip_adaptive_cacao (+ _work_bytes, _plane_offset_bytes) and three plane ids;
                                * vqhip_shadow_depth (+ _work_bytes), vqhip_shadow_mesh / _draw / _view, VQHIP_CULL_*, option raster_tile;
-                               * vqhip_scene_depth (+ _work_bytes), vqhip_scene_depth_draw / _targets */
+                               * vqhip_scene_depth (+ _work_bytes), vqhip_scene_depth_draw / _targets;
+                               * vqhip_scene_interpolants (+ _work_bytes), vqhip_scene_surface_draw, vqhip_scene_interpolant_targets, option interp_form */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -434,7 +436,7 @@ VQHIP_API int vqhip_forward_lighting_msaa(vqhip_ctx* ctx, void* stream, const vq
  * of the nearest sample into the alpha of the resolved scene colour (its `sceneColorRoughness` argument). Inputs, in the representation of
  * vqhip_forward_lighting_msaa (layers + coverage masks, same ownership rule: the lowest layer whose mask has bit s owns sample s, no owner = background):
  *   depth_ms     : float [height][depth_pitch_px][4], 16-byte aligned — the Texture2DMS<float> depth, sample s of a pixel at [..][s]; NDC z, far plane /
- *                  clear value 1. Producing it stays with the caller (the rasteriser's z), like the interpolant planes.
+ *                  clear value 1. vqhip_scene_depth produces it (samples 4); a caller's own rasteriser may hand over its z instead.
  *   coverage[k]  : as vqhip_gbuffer_msaa; read only when outNormals or sceneColor is given
  *   normals[k]   : layer k's pre-pass normals == what vqhip_scene_normals_from_materials writes for that layer's interpolants, normals_fmt
  *                  R10G10B10A2_UNORM | RGBA32F (one format for all layers), normals_pitch_px[k] pixels per row. A background sample reads the clear value 0.
@@ -649,7 +651,7 @@ VQHIP_API int vqhip_forward_lighting_from_materials_mrt(vqhip_ctx* ctx, void* st
  *            r in bits 0-9, g 10-19, b 20-29, alpha 30-31 (1 -> 3); float -> UNORM n = trunc(saturate(c) * (2^n - 1) + 0.5) —
  *            or RGBA32F holding the unquantised float4 (w = 1 covered / 0 not). out_row_pitch_px pixels per row (0 = width).
  *   materials : HOST array, as for vqhip_gbuffer_from_materials; vqhip_set_arithmetic selects the reading of normalize / dot here too.
- * The depth half of the pre-pass (the rasteriser's z) stays with the caller, like the interpolant planes. */
+ * The depth half of the pre-pass is vqhip_scene_depth; the interpolant planes are vqhip_scene_interpolants'. */
 VQHIP_API int vqhip_scene_normals_from_materials(vqhip_ctx* ctx, void* stream,
         const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
         void* out, vqhip_format outFmt, int out_row_pitch_px);
@@ -1131,7 +1133,7 @@ VQHIP_API int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shado
  * per-sample z/w and the depth test as one 64-bit minimum); tests/scene_depth_ref.py states it in numpy. V2's z planes (a guard band is as legal), V4's sample
  * positions and V5's interpolation precision are UNPINNED against a D3D12 device (docs/WARP_CALIBRATION.md §5).
  * Out of scope: the ENABLE_ALPHA_MASK variant, the tessellation and heightmap variants (the null heightmap's + 0.0f is kept), wireframe, the pass's normals target
- * (vqhip_scene_normals_from_materials writes it from interpolants) and the interpolant planes themselves.
+ * (vqhip_scene_normals_from_materials writes it from interpolants). The interpolant planes are vqhip_scene_interpolants' (below), from this call's owner planes.
  * Outputs (pitches in pixels, coverage_pitch in bytes, 0 = dense = width; every pointer but depth may be NULL):
  *   depth           samples 1: float [height][pitch] — the `depth` of vqhip_depth_hierarchy; samples 4: float [height][pitch][4], 16-byte aligned — the depth_ms of
  *                   vqhip_msaa_resolve_surfaces. An uncovered sample holds 1.0.
@@ -1181,6 +1183,56 @@ VQHIP_API size_t vqhip_scene_depth_work_bytes(uint64_t instancedTriangles);
  * alone would allow up to 2^32 - 2; eight records per triangle must also fit the 32-bit record counter) or more than 20 000 draws in one call. */
 VQHIP_API int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_depth_draw* draws, int numDraws, int width, int height, int samples,
         const vqhip_scene_depth_targets* out, void* work, size_t workBytes);
+
+/* ---- The lit draw's interpolants from meshes: the vertex stage of ForwardLighting.hlsl (TransformVertex, :143-188) and the perspective-correct interpolation of
+ * PSInput at the pixel centre, as a visibility-buffer resolve over the owner plane vqhip_scene_depth writes. With it the chain meshes -> vqhip_scene_depth ->
+ * vqhip_scene_interpolants -> vqhip_gbuffer_from_materials / vqhip_forward_lighting_from_materials[_mrt] / vqhip_scene_normals_from_materials runs inside the
+ * library, at 1x and — one call per layer — at 4x MSAA. docs/DESIGN_DETAILS.md §7.18 is the normative statement (I0 owner lookup, I1 vertex stage in binary32
+ * whatever vqhip_set_arithmetic says, I2 weights at the pixel centre and I3 attributes in binary64, rounded once); tests/scene_interp_ref.py states it in numpy.
+ * I2 and I3 are UNPINNED against a D3D12 device (docs/WARP_CALIBRATION.md §5): D3D leaves interpolation precision to the device.
+ *   draws   the draw list of the vqhip_scene_depth call that produced `owner`: the same order, index counts and instance counts — that gives q its meaning.
+ *   owner   uint32 [height][owner_pitch_px] (0 = width), 4-byte aligned: `primitive` at 1x, one `layerPrimitive[k]` at 4x. Any content is safe: a pixel whose q
+ *           is 0xFFFFFFFF, at or beyond the call's instanced triangles, or whose triangle has an index >= numVertices has NO OWNER and receives
+ *           ip0 = ip1 = (0, 0, 0, 0), ip2 = (0, 0, 0, asfloat(int32 -1)) and, if asked for, svPositionCurr = svPositionPrev = (0, 0, 0, 1).
+ *   out     ip0 = (world, uv.x), ip1 = (N, uv.y), ip2 = (T, asfloat(materialIndex)): the planes of vqhip_interpolants; svPositionCurr = clip, svPositionPrev =
+ *           the previous frame's clip: the planes of vqhip_psmain_targets (both or neither). A NaN is stored as 0x7FC00000. At 4x a pixel centre outside its
+ *           owner extrapolates, as D3D does for a PSInput without `centroid`.
+ *   work    vqhip_scene_interpolants_work_bytes(numDraws) bytes, 256-byte aligned: the device home of the draw table (any pixel may look up any draw).
+ * The table is staged through the context's constant ring (one table-copy launch per ring slot of 556 draws), then ONE kernel (a wave whose 64 pixels share
+ * one owner fetches it once; option interp_form lane switches that path off, same bits). No allocation, no memset node, no
+ * readback. Draw descriptors are host memory, consumed before the call returns; meshes and matrices are device memory, read when the kernel runs. Not modelled:
+ * the heightmap (the null heightmap's float3 add is kept), tessellation, alpha mask. vqhip_gbuffer_from_materials still takes its uv LOD from neighbouring pixels
+ * of the planes, so at primitive edges it differs from a helper-lane derivative. */
+typedef struct vqhip_scene_surface_draw {   /* one DrawIndexedInstanced of the lit pass */
+    vqhip_shadow_mesh mesh;                 /* the engine's vertex: position @0, normal @12, tangent @24, uv @36; strideBytes >= 44, a multiple of 4 */
+    const VQ_matrix* matWorldViewProj;      /* device, [numInstances]: PerObjectLightingData */
+    const VQ_matrix* matWorld;
+    const VQ_matrix* matNormal;
+    const VQ_matrix* matWorldViewProjPrev;  /* may be NULL when no svPosition plane is asked for */
+    uint32_t numInstances;                  /* 1 .. 64 */
+    int32_t  materialIndex;                 /* >= 0; written to ip2.w */
+} vqhip_scene_surface_draw;
+typedef struct vqhip_scene_interpolant_targets {   /* device pointers, float4 planes, 16-byte aligned */
+    void* ip0; void* ip1; void* ip2;               /* the planes of vqhip_interpolants */
+    void* svPositionCurr; void* svPositionPrev;    /* both or neither: the planes of vqhip_psmain_targets */
+    int32_t pitch, sv_pitch;                       /* pixels per row of ip0..2 / of the sv planes; 0 = width */
+} vqhip_scene_interpolant_targets;
+VQHIP_STATIC_ASSERT(sizeof(vqhip_scene_surface_draw) == 72 && offsetof(vqhip_scene_surface_draw, matWorldViewProj) == 32 &&
+                    offsetof(vqhip_scene_surface_draw, numInstances) == 64, "vqhip_scene_surface_draw layout");
+VQHIP_STATIC_ASSERT(sizeof(vqhip_scene_interpolant_targets) == 48 && offsetof(vqhip_scene_interpolant_targets, svPositionCurr) == 24 &&
+                    offsetof(vqhip_scene_interpolant_targets, pitch) == 40, "vqhip_scene_interpolant_targets layout");
+/* Bytes of work for a call of numDraws draws: 80 per draw, rounded up to 256 (256 for numDraws == 0). 0 for numDraws < 0. Host-only. */
+VQHIP_API size_t vqhip_scene_interpolants_work_bytes(int numDraws);
+/* Returns VQHIP_ERR_INVALID_ARG — launching nothing, leaving the outputs untouched — for NULL pointers (ctx, out, ip0, ip1, ip2, owner, work, draws with
+ * numDraws > 0, a mesh's positions or indices, matWorldViewProj, matWorld, matNormal), numDraws < 0, exactly one of the two sv planes, sv planes asked for while a
+ * draw has matWorldViewProjPrev == NULL, width or height outside 1 .. 8192, a pitch (owner, ip, sv) that is negative or below width, a target not 16-byte aligned,
+ * owner not 4-byte aligned, a stride below 44 or not a multiple of 4, an indexBits other than 16 / 32, numIndices % 3 != 0, numInstances outside 1 .. 64,
+ * materialIndex < 0, positions or matrices not 4-byte aligned, indices not aligned to their size, work not 256-byte aligned, workBytes below
+ * vqhip_scene_interpolants_work_bytes(numDraws), or an output that overlaps the work buffer or the owner plane; VQHIP_ERR_UNSUPPORTED for more than 20 000 draws with numIndices > 0 (empty draws are not counted,
+ * though the work size is that of numDraws)
+ * or 2^29 or more instanced triangles in one call (the limits of vqhip_scene_depth). */
+VQHIP_API int vqhip_scene_interpolants(vqhip_ctx* ctx, void* stream, const vqhip_scene_surface_draw* draws, int numDraws, int width, int height,
+        const uint32_t* owner, int owner_pitch_px, const vqhip_scene_interpolant_targets* out, void* work, size_t workBytes);
 
 #ifdef __cplusplus
 }

@@ -568,7 +568,8 @@ private:
 // are the uploaded PerObjectData), the stream and the depth target (DSV_SceneDepthMSAA when bMSAA, else DSV_SceneDepth, as R32F memory). W and H are the window's
 // (OnCreateWindowSizeDependentResources, the viewport of :1330); bMSAA selects 4 samples, the engine's default, else 1. The primitive and layer planes are the
 // library's addition (the masks vqhip_forward_lighting_msaa and vqhip_msaa_resolve_surfaces read); leave them NULL for the engine's own outputs. The pass's
-// normals target stays with vqhip_scene_normals_from_materials. The pass owns the work buffer, as ShadowDepthPass does.
+// normals target stays with vqhip_scene_normals_from_materials; the interpolant planes are SceneInterpolantsPass's (below). The pass owns the work buffer, as
+// ShadowDepthPass does.
 // ---------------------------------------------------------------------------------------------------------------
 class DepthPrePass : public RenderPassBase {
 public:
@@ -609,6 +610,57 @@ public:
         t.depth = p->SceneDepth; t.primitive = p->Primitive; t.layers = p->bMSAA ? p->NumLayers : 0;
         for (int k = 0; k < t.layers; ++k) { t.coverage[k] = p->Coverage[k]; t.layerPrimitive[k] = p->LayerPrimitive[k]; }
         mStatus = vqhip_scene_depth(mCtx, p->Stream, numDraws ? p->Draws->data() : nullptr, numDraws, (int)mWidth, (int)mHeight, p->bMSAA ? 4 : 1, &t, mWork, mWorkBytes);
+    }
+    const void* GetWorkBuffer() const { return mWork; }
+    size_t GetWorkBytes() const { return mWorkBytes; }
+private:
+    void* mWork = nullptr; size_t mWorkBytes = 0;
+    unsigned mWidth = 0, mHeight = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// The lit draw's vertex stage and interpolation == what VQRenderer::RenderSceneColor (SceneRendering.cpp:1619-1760) leaves to the rasteriser between the draw call
+// and PSMain: vqhip_scene_interpolants. FDrawParameters carries the pass's draw list (FSceneDrawData::mainViewDrawParams again, each FInstancedDrawParameters as a
+// vqhip_scene_surface_draw whose four matrix blocks are the uploaded PerObjectLightingData and whose materialIndex is the draw's material) — the SAME list, in the
+// same order, that DepthPrePass rasterised — and the owner plane DepthPrePass wrote: Primitive without MSAA, one LayerPrimitive[k] per call with it. The planes
+// written are HipSceneColorPass's pInterpolants (and its svPosition planes when SvPositionCurr / SvPositionPrev are given). W and H are the window's. The pass owns
+// the work buffer (the draw table's device home).
+// ---------------------------------------------------------------------------------------------------------------
+class SceneInterpolantsPass : public RenderPassBase {
+public:
+    struct FResourceParameters : public IRenderPassResourceCollection {};
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        const std::vector<vqhip_scene_surface_draw>* Draws = nullptr;           // nullptr or empty: every pixel receives the no-owner record
+        const uint32_t* Owner = nullptr;                                        // [H][OwnerPitch]
+        int OwnerPitch = 0;                                                     // pixels per row, 0 = W
+        void* Ip0 = nullptr; void* Ip1 = nullptr; void* Ip2 = nullptr;          // float4 [H][W]
+        void* SvPositionCurr = nullptr; void* SvPositionPrev = nullptr;         // both or neither
+    };
+    explicit SceneInterpolantsPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    ~SceneInterpolantsPass() override { Free(mWork); }
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { Free(mWork); mWorkBytes = 0; }
+    void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override { mWidth = Width; mHeight = Height; }
+    void OnDestroyWindowSizeDependentResources() override { mWidth = mHeight = 0; }
+    bool Reserve(int NumDraws) {
+        const size_t need = vqhip_scene_interpolants_work_bytes(NumDraws);
+        if (!need) return false;
+        if (need <= mWorkBytes) return true;
+        Free(mWork); mWorkBytes = 0;
+        mWork = Alloc(need);
+        if (mWork) mWorkBytes = need;
+        return mWork != nullptr;
+    }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        const int numDraws = p->Draws ? (int)p->Draws->size() : 0;
+        if (!Reserve(numDraws)) { mStatus = VQHIP_ERR_HIP; return; }
+        vqhip_scene_interpolant_targets t = {};
+        t.ip0 = p->Ip0; t.ip1 = p->Ip1; t.ip2 = p->Ip2; t.svPositionCurr = p->SvPositionCurr; t.svPositionPrev = p->SvPositionPrev;
+        mStatus = vqhip_scene_interpolants(mCtx, p->Stream, numDraws ? p->Draws->data() : nullptr, numDraws, (int)mWidth, (int)mHeight, p->Owner, p->OwnerPitch, &t,
+                                           mWork, mWorkBytes);
     }
     const void* GetWorkBuffer() const { return mWork; }
     size_t GetWorkBytes() const { return mWorkBytes; }
@@ -742,7 +794,7 @@ public:
 // ---------------------------------------------------------------------------------------------------------------
 // Z pre-pass colour target == the pixel-shader half of VQRenderer::RenderDepthPrePass (SceneRendering.cpp:1264-1360, DepthPrePass.hlsl:PSMain): owns
 // Tex_SceneNormals (R10G10B10A2_UNORM, RenderResources.cpp:185-197) — HipSSREnvironmentFallbackPass::FDrawParameters::TexNormals. The depth target of the
-// same draws is the rasteriser's and stays with the caller, like the interpolant planes.
+// same draws is DepthPrePass's (above); the interpolant planes are SceneInterpolantsPass's.
 // ---------------------------------------------------------------------------------------------------------------
 class HipDepthPrePassNormals : public RenderPassBase {
 public:

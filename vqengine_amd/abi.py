@@ -259,6 +259,20 @@ class SceneDepthTargets(C.Structure):  # vqhip_scene_depth_targets
                 ("pitch", C.c_int32), ("coverage_pitch", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SceneSurfaceDraw(C.Structure):  # vqhip_scene_surface_draw
+    _fields_ = [("mesh", ShadowMesh), ("matWorldViewProj", C.c_void_p), ("matWorld", C.c_void_p), ("matNormal", C.c_void_p), ("matWorldViewProjPrev", C.c_void_p),
+                ("numInstances", C.c_uint32), ("materialIndex", C.c_int32)]
+
+
+class SceneInterpolantTargets(C.Structure):  # vqhip_scene_interpolant_targets
+    _fields_ = [("ip0", C.c_void_p), ("ip1", C.c_void_p), ("ip2", C.c_void_p), ("svPositionCurr", C.c_void_p), ("svPositionPrev", C.c_void_p),
+                ("pitch", C.c_int32), ("sv_pitch", C.c_int32)]
+
+
+SURFACE_VERTEX_BYTES = 44                    # the engine's vertex: position @0, normal @12, tangent @24, uv @36
+SURFACE_JOB_BYTES = 80                       # one draw's entry of vqhip_scene_interpolants' table in its work buffer
+
+
 def _chk(t, size, **offs):
     assert C.sizeof(t) == size, (t.__name__, C.sizeof(t), size)
     for k, v in offs.items():
@@ -287,6 +301,8 @@ _chk(ShadowMesh, 32, strideBytes=8, numVertices=12, indices=16, indexBits=24, nu
 _chk(ShadowDraw, 56, matWorldViewProj=32, matWorld=40, numInstances=48, cullMode=52)
 _chk(SceneDepthDraw, 48, matWorldViewProj=32, numInstances=40, cullMode=44)
 _chk(SceneDepthTargets, 96, primitive=8, coverage=16, layerPrimitive=48, layers=80, pitch=84, coverage_pitch=88, reserved=92)
+_chk(SceneSurfaceDraw, 72, matWorldViewProj=32, matWorld=40, matNormal=48, matWorldViewProjPrev=56, numInstances=64, materialIndex=68)
+_chk(SceneInterpolantTargets, 48, ip1=8, ip2=16, svPositionCurr=24, svPositionPrev=32, pitch=40, sv_pitch=44)
 _chk(ShadowView, 56, pitchBytes=8, dim=16, linearDepth=20, cameraPosition=24, farPlane=36, draws=40, numDraws=48)
 _chk(CacaoConstants, 384, EffectRadius=48, InvSharpness=96, PassIndex=100, PatternRotScaleMatrices=112, NormalsUnpackMul=192, SSAOBufferDimensions=208,
      DepthBufferOffset=240, PerPassFullResUVOffset=248, DeinterleavedDepthBufferNormalisedOffset=312, NormalsWorldToViewspaceMatrix=320)

@@ -114,6 +114,8 @@ def load_library():
         "vqhip_shadow_depth": (i32, [vp, vp, C.POINTER(abi.ShadowView), i32, vp, sz]),
         "vqhip_scene_depth_work_bytes": (sz, [C.c_uint64]),
         "vqhip_scene_depth": (i32, [vp, vp, C.POINTER(abi.SceneDepthDraw), i32, i32, i32, i32, C.POINTER(abi.SceneDepthTargets), vp, sz]),
+        "vqhip_scene_interpolants_work_bytes": (sz, [i32]),
+        "vqhip_scene_interpolants": (i32, [vp, vp, C.POINTER(abi.SceneSurfaceDraw), i32, i32, i32, vp, i32, C.POINTER(abi.SceneInterpolantTargets), vp, sz]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -150,7 +152,26 @@ EXPORTED_SYMBOLS = [
     "vqhip_adaptive_cacao", "vqhip_adaptive_cacao_work_bytes", "vqhip_adaptive_cacao_plane_offset_bytes",
     "vqhip_shadow_depth", "vqhip_shadow_depth_work_bytes",
     "vqhip_scene_depth", "vqhip_scene_depth_work_bytes",
+    "vqhip_scene_interpolants", "vqhip_scene_interpolants_work_bytes",
 ]
+
+
+def scene_interpolants_work_bytes(num_draws):
+    """vqhip_scene_interpolants_work_bytes: the work buffer (the draw table's device home) of a vqhip_scene_interpolants call of `num_draws` draws. Host-only."""
+    return load_library().vqhip_scene_interpolants_work_bytes(int(num_draws))
+
+
+class SurfaceDraw:
+    """One vqhip_scene_surface_draw. vertices: cuda float32 [V, k] with k >= 11 and unit column stride (position 3, normal 3, tangent 3, uv 2; the row stride is
+    the vertex stride); indices: cuda 1-D int16 / uint16 (read as 16-bit unsigned) or int32, a triangle list; wvp / world / normal / wvp_prev: cuda float32
+    [n, 4, 4] contiguous, VQ_matrix memory order (wvp_prev may be None when no svPosition plane is asked for); material: the index written to ip2.w."""
+
+    def __init__(self, vertices, indices, wvp, world, normal, wvp_prev=None, material=0):
+        self.vertices, self.indices, self.wvp, self.world, self.normal, self.wvp_prev, self.material = vertices, indices, wvp, world, normal, wvp_prev, int(material)
+
+    def depth_draw(self, cull=abi.CULL_NONE):
+        """the same draw for vqhip_scene_depth / vqhip_shadow_depth"""
+        return ShadowDraw(self.vertices, self.indices, self.wvp, self.world, cull)
 
 
 def scene_depth_work_bytes(instanced_triangles):
@@ -723,6 +744,80 @@ class Context:
 
         def call(stream=None, _keep=keep):
             self._ck(self.lib.vqhip_scene_depth(self._h, self._stream(stream), cdraws, len(draws), w, h, samples, C.byref(tg), _ptr(work), work.numel()))
+        return call, res
+
+    def scene_interpolants(self, draws, width, height, owner, sv=False, out=None, work=None, stream=None):
+        """vqhip_scene_interpolants: the lit draw's PSInput planes of the SurfaceDraw list `draws` (the draw list of the scene_depth call that wrote `owner`, in
+        the same order) under the owner plane `owner`: cuda int32 [H, W] with unit column stride — scene_depth's `primitive` at 1x, one `layer_primitive[k]` at
+        4x. sv: also the svPositionCurr / svPositionPrev planes of psmain targets. out: a dict of preallocated cuda float32 [H, W, 4] tensors under the keys of
+        the result (their row strides are the pitches), else they are allocated dense. Returns a dict: ip0, ip1, ip2, with sv also sv_curr and sv_prev, work."""
+        call, res = self.scene_interpolants_prepared(draws, width, height, owner, sv, out, work)
+        call(stream)
+        return res
+
+    def scene_interpolants_prepared(self, draws, width, height, owner, sv=False, out=None, work=None):
+        """The descriptors of a scene_interpolants call built once: returns (call, result) with call(stream=None) issuing vqhip_scene_interpolants on the same
+        draws, owner plane and targets again. The tensors must stay alive and in place."""
+        draws, out = list(draws), dict(out or {})
+        w, h = int(width), int(height)
+        if not (1 <= w <= abi.SCENE_DEPTH_MAX_DIM and 1 <= h <= abi.SCENE_DEPTH_MAX_DIM):
+            raise ValueError(f"scene_interpolants: width and height must be 1..{abi.SCENE_DEPTH_MAX_DIM}")
+        if not (owner.is_cuda and owner.dtype == torch.int32 and tuple(owner.shape) == (h, w) and owner.stride(1) == 1 and owner.stride(0) >= w):
+            raise ValueError(f"scene_interpolants: owner: expected cuda int32 {(h, w)} with unit column stride, got {tuple(owner.shape)} {owner.dtype} strides {owner.stride()}")
+        res, pitches = {}, {}
+        for key in ("ip0", "ip1", "ip2") + (("sv_curr", "sv_prev") if sv else ()):
+            t = out.get(key)
+            if t is None:
+                t = torch.empty((h, w, 4), dtype=torch.float32, device=self.device)
+            if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.stride(2) == 1 and t.stride(1) == 4 and t.stride(0) % 4 == 0
+                    and t.stride(0) >= 4 * w):
+                raise ValueError(f"scene_interpolants: {key}: expected cuda float32 {(h, w, 4)} with dense pixels, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+            res[key] = t
+            pitches.setdefault(key[:2], set()).add(t.stride(0) // 4)
+        if any(len(p) != 1 for p in pitches.values()):
+            raise ValueError("scene_interpolants: ip0, ip1 and ip2 share one pitch in pixels, sv_curr and sv_prev another")
+        cdraws = (abi.SceneSurfaceDraw * max(1, len(draws)))()
+        for j, dr in enumerate(draws):
+            who = f"scene_interpolants: draw {j}"
+            p, ix = dr.vertices, dr.indices
+            if not (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and p.shape[1] >= 11 and p.stride(1) == 1 and p.stride(0) >= p.shape[1]):
+                raise ValueError(f"{who}: vertices: expected cuda float32 [V, k >= 11] with unit column stride")
+            bits = {2: 16, 4: 32}.get(ix.element_size()) if not ix.dtype.is_floating_point else None
+            if not (ix.is_cuda and ix.dim() == 1 and ix.is_contiguous() and bits and ix.numel() % 3 == 0):
+                raise ValueError(f"{who}: indices: expected a contiguous cuda 1-D 16-bit or 32-bit integer tensor whose length is a multiple of 3")
+            n = dr.wvp.shape[0] if dr.wvp.dim() == 3 else 0
+            for name, m in (("wvp", dr.wvp), ("world", dr.world), ("normal", dr.normal), ("wvp_prev", dr.wvp_prev)):
+                if m is None and name == "wvp_prev" and not sv:
+                    continue
+                if m is None or not (m.is_cuda and m.dtype == torch.float32 and tuple(m.shape) == (n, 4, 4) and m.is_contiguous()):
+                    raise ValueError(f"{who}: {name}: expected cuda float32 [n, 4, 4] contiguous, n the same for every matrix block")
+            if not 1 <= n <= abi.SCENE_DEPTH_MAX_INSTANCES:
+                raise ValueError(f"{who}: 1..{abi.SCENE_DEPTH_MAX_INSTANCES} instances, got {n}")
+            if dr.material < 0:
+                raise ValueError(f"{who}: material: expected an index >= 0")
+            c = cdraws[j]
+            c.mesh.positions, c.mesh.strideBytes, c.mesh.numVertices = p.data_ptr(), p.stride(0) * 4, p.shape[0]
+            # an empty tensor has no address, and the library refuses a NULL index buffer whatever its length: an empty draw names the vertex buffer (never read)
+            c.mesh.indices, c.mesh.indexBits, c.mesh.numIndices = ix.data_ptr() or p.data_ptr(), bits, ix.numel()
+            c.matWorldViewProj, c.matWorld, c.matNormal = dr.wvp.data_ptr(), dr.world.data_ptr(), dr.normal.data_ptr()
+            c.matWorldViewProjPrev = dr.wvp_prev.data_ptr() if dr.wvp_prev is not None else None
+            c.numInstances, c.materialIndex = n, dr.material
+        need = scene_interpolants_work_bytes(len(draws))
+        if work is None:
+            work = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.numel() >= need):
+            raise ValueError(f"scene_interpolants: work: expected a contiguous cuda uint8 tensor of at least {need} bytes")
+        res["work"] = work
+        tg = abi.SceneInterpolantTargets()
+        tg.ip0, tg.ip1, tg.ip2 = res["ip0"].data_ptr(), res["ip1"].data_ptr(), res["ip2"].data_ptr()
+        tg.pitch = pitches["ip"].pop()
+        if sv:
+            tg.svPositionCurr, tg.svPositionPrev, tg.sv_pitch = res["sv_curr"].data_ptr(), res["sv_prev"].data_ptr(), pitches["sv"].pop()
+        keep = (draws, res, owner)
+
+        def call(stream=None, _keep=keep):
+            self._ck(self.lib.vqhip_scene_interpolants(self._h, self._stream(stream), cdraws, len(draws), w, h, _ptr(owner), owner.stride(0), C.byref(tg),
+                                                       _ptr(work), work.numel()))
         return call, res
 
     def msaa_resolve_surfaces(self, depth_ms, coverage=None, normals=None, normals_fmt=abi.FMT_R10G10B10A2_UNORM, roughness=None, background=None,

@@ -698,6 +698,7 @@ int vqhip_set_option(vqhip_ctx* ctx, const char* key, const char* value) {
     if (k == "diffuse_form") { if (v == "records") { o.diffuseForm = 0; return VQHIP_OK; } return pick(&o.diffuseForm, { "texels", "general" }); }
     if (k == "diffuse_seq_form") { if (v == "ordered") { o.diffuseSeqForm = 0; return VQHIP_OK; } return pick(&o.diffuseSeqForm, { "lane" }); }
     if (k == "raster_tile") return num(&o.rasterTile, { 0, 32, 64 });
+    if (k == "interp_form") return pick(&o.interpForm, { "lane", "wave" });
     return fail(ctx, VQHIP_ERR_INVALID_ARG, "set_option: unknown key '" + k + "'");
 }
 int vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode) {
@@ -2022,6 +2023,106 @@ int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_depth_draw
     }
     e = launch_scene_fill(st, a, scene_depth_tile(ctx->opt.rasterTile, samples), counter, boxes, records);
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "scene_depth fill launch");
+}
+
+// ---- The lit draw's interpolants from meshes (raster_attr.hip; docs/DESIGN_DETAILS.md §7.18) ----------------------------------------------------------------------
+namespace {
+constexpr size_t kSurfaceJobsPerSlot = kConstSlotBytes / sizeof(SurfaceJob);
+// A call of 20 000 draws may take more slots than the ring has: acquireSlot then waits for the table copy that last read the slot, which this call enqueued.
+static_assert(kSurfaceJobsPerSlot >= 1, "a ring slot holds at least one SurfaceJob");
+} // namespace
+
+size_t vqhip_scene_interpolants_work_bytes(int numDraws) {
+    if (numDraws < 0) return 0;
+    return align256((size_t)(numDraws > 0 ? numDraws : 1) * sizeof(SurfaceJob));
+}
+
+int vqhip_scene_interpolants(vqhip_ctx* ctx, void* stream, const vqhip_scene_surface_draw* draws, int numDraws, int width, int height,
+                             const uint32_t* owner, int owner_pitch_px, const vqhip_scene_interpolant_targets* out, void* work, size_t workBytes) {
+    vqk::Range range_("RenderSceneColor");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "scene_interpolants: ctx is NULL");
+    CTX_GUARD(ctx, "scene_interpolants");
+    auto bad = [&](const std::string& m) { return fail(ctx, VQHIP_ERR_INVALID_ARG, "scene_interpolants: " + m); };
+    if (!out || !out->ip0 || !out->ip1 || !out->ip2 || !owner || !work) return bad("NULL argument (out, ip0, ip1, ip2, owner or work)");
+    if (numDraws < 0 || (numDraws > 0 && !draws)) return bad("numDraws < 0, or draws is NULL");
+    if (!out->svPositionCurr != !out->svPositionPrev) return bad("svPositionCurr and svPositionPrev: both or neither");
+    const bool sv = out->svPositionCurr != nullptr;
+    if (width < 1 || width > VQHIP_SCENE_DEPTH_MAX_DIM || height < 1 || height > VQHIP_SCENE_DEPTH_MAX_DIM) return bad("width and height must be 1..8192");
+    if (out->pitch < 0 || out->sv_pitch < 0 || owner_pitch_px < 0) return bad("negative pitch");
+    const size_t pitch = out->pitch ? (size_t)out->pitch : (size_t)width, svPitch = out->sv_pitch ? (size_t)out->sv_pitch : (size_t)width;
+    const size_t ownerPitch = owner_pitch_px ? (size_t)owner_pitch_px : (size_t)width;
+    if (pitch < (size_t)width || svPitch < (size_t)width || ownerPitch < (size_t)width) return bad("a pitch below width");
+    void* const planes[5] = { out->ip0, out->ip1, out->ip2, out->svPositionCurr, out->svPositionPrev };
+    for (int k = 0; k < 5; ++k) if ((uintptr_t)planes[k] % 16) return bad("a target is not 16-byte aligned");
+    if ((uintptr_t)owner % 4) return bad("owner must be 4-byte aligned");
+    if ((uintptr_t)work % 256) return bad("work must be 256-byte aligned");
+    uint64_t totalTris = 0;
+    size_t numJobs = 0;
+    for (int d = 0; d < numDraws; ++d) {
+        const vqhip_scene_surface_draw& D = draws[d];
+        auto badDraw = [&](const char* m) { return bad("draw " + std::to_string(d) + ": " + m); };
+        if (!D.mesh.positions || !D.mesh.indices || !D.matWorldViewProj || !D.matWorld || !D.matNormal)
+            return badDraw("positions, indices, matWorldViewProj, matWorld or matNormal is NULL");
+        if (sv && !D.matWorldViewProjPrev) return badDraw("matWorldViewProjPrev is NULL while the sv planes are asked for");
+        if (D.mesh.indexBits != 16 && D.mesh.indexBits != 32) return badDraw("indexBits must be 16 or 32");
+        if (D.mesh.numIndices % 3) return badDraw("numIndices is not a multiple of 3");
+        if (D.mesh.strideBytes < 44 || D.mesh.strideBytes % 4) return badDraw("strideBytes below 44 or not a multiple of 4");
+        if (D.numInstances < 1 || D.numInstances > VQHIP_SCENE_DEPTH_MAX_INSTANCES) return badDraw("numInstances must be 1..64");
+        if (D.materialIndex < 0) return badDraw("materialIndex is negative");
+        if ((uintptr_t)D.mesh.positions % 4 || (uintptr_t)D.matWorldViewProj % 4 || (uintptr_t)D.matWorld % 4 || (uintptr_t)D.matNormal % 4 ||
+            (uintptr_t)D.matWorldViewProjPrev % 4 || (uintptr_t)D.mesh.indices % (D.mesh.indexBits / 8))
+            return badDraw("positions / matrices must be 4-byte aligned, indices aligned to their size");
+        if (D.mesh.numIndices) { totalTris += (uint64_t)(D.mesh.numIndices / 3) * D.numInstances; ++numJobs; }
+    }
+    if (totalTris >= kSceneMaxTriangles) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "scene_interpolants: 2^29 or more instanced triangles in one call");
+    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "scene_interpolants: more than 20000 draws in one call");
+    const size_t need = vqhip_scene_interpolants_work_bytes(numDraws);
+    if (workBytes < need) return bad("workBytes below vqhip_scene_interpolants_work_bytes(numDraws)");
+    const size_t rows = (size_t)(height - 1);
+    const size_t ownerBytes = (rows * ownerPitch + width) * 4;
+    for (int k = 0; k < 5; ++k) {
+        if (!planes[k]) continue;
+        const size_t bytes = (rows * (k < 3 ? pitch : svPitch) + width) * 16;
+        if (rangesOverlap(work, need, planes[k], bytes)) return bad("an output overlaps the work buffer");
+        if (rangesOverlap(owner, ownerBytes, planes[k], bytes)) return bad("an output overlaps the owner plane");
+    }
+
+    SceneInterpArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.owner = owner; a.ip[0] = out->ip0; a.ip[1] = out->ip1; a.ip[2] = out->ip2; a.sv[0] = out->svPositionCurr; a.sv[1] = out->svPositionPrev;
+    a.ownerPitch = (uint32_t)ownerPitch; a.pitch = (uint32_t)pitch; a.svPitch = (uint32_t)svPitch;
+    a.width = width; a.height = height; a.numJobs = (int32_t)numJobs; a.totalTris = (uint32_t)totalTris;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    SurfaceJob* table = (SurfaceJob*)work;
+    // the draws, in ring slots of kSurfaceJobsPerSlot jobs: one table-copy launch per slot
+    int d = 0;
+    size_t left = numJobs, done = 0;
+    uint64_t firstQ = 0;
+    while (left) {
+        int slot;
+        if (int rc = acquireSlot(ctx, &slot)) return rc;
+        SurfaceJob* jobs = (SurfaceJob*)(ctx->hostRing + (size_t)slot * kConstSlotBytes);
+        const size_t n = left < kSurfaceJobsPerSlot ? left : kSurfaceJobsPerSlot;
+        for (size_t k = 0; k < n;) {
+            const vqhip_scene_surface_draw& D = draws[d++];
+            if (!D.mesh.numIndices) continue;
+            SurfaceJob& J = jobs[k++];
+            std::memset(&J, 0, sizeof(J));
+            J.vertices = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices;
+            J.wvp = D.matWorldViewProj; J.world = D.matWorld; J.normal = D.matNormal; J.wvpPrev = D.matWorldViewProjPrev;
+            J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numTris = D.mesh.numIndices / 3; J.numInstances = D.numInstances;
+            J.indexBits = D.mesh.indexBits; J.materialIndex = D.materialIndex; J.firstQ = (uint32_t)firstQ;
+            firstQ += (uint64_t)J.numTris * J.numInstances;
+        }
+        if (int rc = commitSlot(ctx, slot, sizeof(SurfaceJob) * n, st)) return rc;
+        hipError_t e = launch_table_copy(st, ctx->devRing + (size_t)slot * kConstSlotBytes, table + done, (uint32_t)(n * (sizeof(SurfaceJob) / 16)));
+        if (e != hipSuccess) return failHip(ctx, e, "scene_interpolants table-copy launch");
+        if (int rc = releaseSlot(ctx, slot, st)) return rc;
+        left -= n; done += n;
+    }
+    hipError_t e = launch_scene_interpolants(st, a, table, ctx->opt.interpForm != 1);        // default: the wave form
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "scene_interpolants launch");
 }
 
 } // extern "C"

@@ -30,6 +30,7 @@ struct Options {
     int diffuseForm = 0;        // "diffuse_form"      : 1 "texels", 2 "general" (default: footprint records)
     int specularForm = 0;       // "specular_form"     : 1 "general" (default: the branch-free sample with one validity flag)
     int diffuseSeqForm = 0;     // "diffuse_seq_form"  : 1 "lane" (default: k_conv_diffuse_ordered)
+    int interpForm = 0;         // "interp_form"       : lane | wave — k_scene_interpolants with or without the one-owner-per-wave path (default: profiles/r16a_scene_interpolants.md)
     int rasterTile = 0;         // "raster_tile"       : 32 | 64 texels per side of k_raster_fill's tile (default 32, profiles/r14a_shadow_raster.md)
 };
 
@@ -292,6 +293,25 @@ static constexpr size_t kSceneBoxBytes = 8, kSceneRecordBytes = 48, kSceneCounte
 int scene_depth_tile(int rasterTile, int samples);      // pixels per side of k_scene_fill's tile: the option where the LDS budget allows it (not 64 at 4x), else 32
 hipError_t launch_scene_setup(hipStream_t s, const SceneDepthJob* jobs, int numJobs, uint32_t blocks, const SceneDepthArgs& a, uint32_t* counter, void* boxes, void* records);
 hipError_t launch_scene_fill(hipStream_t s, const SceneDepthArgs& a, int tile, const uint32_t* counter, const void* boxes, const void* records);
+
+// The lit draw's interpolants from meshes (vqhip_scene_interpolants, raster_attr.hip; docs/DESIGN_DETAILS.md §7.18). The draw table travels through constant-ring
+// slots into the work buffer (one k_table_copy launch per slot): the resolve looks up any draw from any pixel, so the table needs a home that outlives the slots.
+// Work buffer: SurfaceJob[number of draws with numIndices > 0], nothing else.
+struct alignas(16) SurfaceJob {      // one vqhip_scene_surface_draw
+    const uint8_t* vertices; const void* indices; const VQ_matrix* wvp; const VQ_matrix* world; const VQ_matrix* normal; const VQ_matrix* wvpPrev;
+    uint32_t strideBytes, numVertices, numTris, numInstances;
+    int32_t indexBits, materialIndex;
+    uint32_t firstQ;                 // sequence number of (instance 0, triangle 0): the instanced triangles of the draws before
+};
+static_assert(sizeof(SurfaceJob) == 80, "SurfaceJob is five uint4");
+struct SceneInterpArgs {
+    const uint32_t* owner; void* ip[3]; void* sv[2];      // sv: both or neither
+    uint32_t ownerPitch, pitch, svPitch;                  // pixels per row
+    int32_t width, height, numJobs;
+    uint32_t totalTris;                                   // q at or beyond it owns nothing
+};
+hipError_t launch_table_copy(hipStream_t s, const void* src, void* dst, uint32_t numUint4);
+hipError_t launch_scene_interpolants(hipStream_t s, const SceneInterpArgs& a, const SurfaceJob* table, bool waveForm);   // waveForm: waves with one owner fetch it once
 
 // launchers (each returns the hipError_t of the launch)
 hipError_t launch_forward_lighting(hipStream_t s, const ShadeArgs& a, bool hasEnv, bool hasCasters, int outFmt, const Options& opt);

@@ -1,0 +1,83 @@
+"""Host-side producers of what vqhip_scene_interpolants consumes beside shadow_scene's: procedural meshes in the engine's full 44-byte vertex (position 3,
+normal 3, tangent 3, uv 2 -> float32 [V, 11]) and the four matrix blocks of PerObjectLightingData per instance. numpy only; shadow_scene is imported unchanged.
+
+Like shadow_scene this is an INPUT producer: the meshes are written for this project, the matrices are formed in binary64 and rounded once. Conventions are the
+engine's: left-handed, row vectors, front faces clockwise seen from outside."""
+import numpy as np
+
+from . import shadow_scene as S
+
+F = np.float32
+VERTEX_FLOATS = S.VERTEX_FLOATS_ENGINE
+
+# per face of the box: (normal, tangent = the direction uv.x grows in, bitangent = the direction uv.y grows in); normal = tangent x bitangent, left-handed
+_FACES = (((0, 0, -1), (1, 0, 0), (0, 1, 0)), ((0, 0, 1), (-1, 0, 0), (0, 1, 0)), ((-1, 0, 0), (0, 0, -1), (0, 1, 0)),
+          ((1, 0, 0), (0, 0, 1), (0, 1, 0)), ((0, 1, 0), (1, 0, 0), (0, 0, 1)), ((0, -1, 0), (1, 0, 0), (0, 0, -1)))
+
+
+def box(half=(1.0, 1.0, 1.0)):
+    """An axis-aligned box centred at the origin with per-face normals, tangents and uvs: 24 vertices, 12 triangles, clockwise seen from outside. uv runs over
+    [0, 1]^2 on every face. Returns (vertices float32 [24, 11], indices int64 [36])."""
+    h = np.asarray(half, dtype=np.float64)
+    verts, idx = [], []
+    for n, t, b in _FACES:
+        n, t, b = (np.asarray(v, dtype=np.float64) for v in (n, t, b))
+        base = len(verts)
+        for (u, v) in ((0, 0), (0, 1), (1, 1), (1, 0)):
+            p = (n + (2 * u - 1) * t + (2 * v - 1) * b) * h
+            verts.append(np.concatenate([p, n, t, (u, v)]))
+        idx += [base, base + 1, base + 2, base, base + 2, base + 3]
+    return np.array(verts, dtype=F), np.array(idx, dtype=np.int64)
+
+
+def room(half=(1.0, 1.0, 1.0)):
+    """The box seen from inside: every triangle reversed, normals pointing inwards (tangents and uvs kept)."""
+    v, idx = box(half)
+    v = v.copy()
+    v[:, 3:6] = -v[:, 3:6]
+    return v, idx.reshape(-1, 3)[:, ::-1].reshape(-1).copy()
+
+
+def uv_sphere(radius=1.0, slices=24, stacks=22):
+    """shadow_scene.uv_sphere's vertices and triangles with normal = position / radius, tangent = the direction of growing longitude ((1, 0, 0) at the poles)
+    and uv = (longitude / 2 pi, colatitude / pi). The seam shares its vertices: uv.x wraps inside the last column of triangles."""
+    p, idx = S.uv_sphere(radius, slices, stacks)
+    p64 = p.astype(np.float64)
+    n = p64 / radius
+    ph = np.arctan2(p64[:, 2], p64[:, 0]) % (2.0 * np.pi)
+    th = np.arccos(np.clip(n[:, 1], -1.0, 1.0))
+    t = np.stack([-np.sin(ph), np.zeros_like(ph), np.cos(ph)], axis=1)
+    pole = (np.abs(p64[:, 0]) + np.abs(p64[:, 2])) == 0.0
+    t[pole] = (1.0, 0.0, 0.0)
+    uv = np.stack([ph / (2.0 * np.pi), th / np.pi], axis=1)
+    return np.concatenate([p64, n, t, uv], axis=1).astype(F), idx
+
+
+def grid(n, size=2.0, jitter=0.0, seed=0, height=0.0):
+    """shadow_scene.grid with normal +y, tangent +x and uv = the position in the grid's square, [0, 1]^2."""
+    p, idx = S.grid(n, size, jitter, seed, height)
+    v = np.zeros((p.shape[0], VERTEX_FLOATS), dtype=F)
+    v[:, :3] = p
+    v[:, 4] = 1.0
+    v[:, 6] = 1.0
+    v[:, 9] = (p[:, 0].astype(np.float64) / size + 0.5).astype(F)
+    v[:, 10] = (p[:, 2].astype(np.float64) / size + 0.5).astype(F)
+    return v, idx
+
+
+def rotation_of(world):
+    """Transform::RotationMatrix of a world matrix built as scaling @ rotation @ translation (positive scales): the upper 3 x 3 with unit rows."""
+    world = np.asarray(world, dtype=np.float64)
+    m = np.eye(4)
+    r = world[:3, :3]
+    m[:3, :3] = r / np.sqrt((r * r).sum(axis=1, keepdims=True))
+    return m
+
+
+def instance_matrices_full(worlds, view_proj, prev_view_proj, prev_worlds=None):
+    """(matWorldViewProj, matWorld, matNormal, matWorldViewProjPrev), each float32 [n, 4, 4] in VQ_matrix memory order: PerObjectLightingData of the instances
+    `worlds` under this frame's and the previous frame's view-projection. matNormal is the rotation (Batching.cpp:281); prev_worlds defaults to worlds."""
+    worlds = np.asarray(worlds, dtype=np.float64).reshape(-1, 4, 4)
+    prev = worlds if prev_worlds is None else np.asarray(prev_worlds, dtype=np.float64).reshape(-1, 4, 4)
+    c = lambda m: np.ascontiguousarray(np.asarray(m).astype(F))      # noqa: E731
+    return c(worlds @ view_proj), c(worlds), c(np.stack([rotation_of(w) for w in worlds])), c(prev @ prev_view_proj)
