@@ -350,7 +350,8 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * VQ_CacaoConstants, vqhip_cacao (+ _work_bytes, _plane_offset_bytes); vqhip_adaptive_cacao (+ _work_bytes, _plane_offset_bytes) and three plane ids;
                                * vqhip_shadow_depth (+ _work_bytes), vqhip_shadow_mesh / _draw / _view, VQHIP_CULL_*, option raster_tile;
                                * vqhip_scene_depth (+ _work_bytes), vqhip_scene_depth_draw / _targets;
-                               * vqhip_scene_interpolants (+ _work_bytes), vqhip_scene_surface_draw, vqhip_scene_interpolant_targets, option interp_form */
+                               * vqhip_scene_interpolants (+ _work_bytes), vqhip_scene_surface_draw, vqhip_scene_interpolant_targets, option interp_form;
+                               * vqhip_scene_masked_depth, vqhip_shadow_masked_depth (+ _work_bytes), vqhip_scene_masked_depth_draw, vqhip_shadow_masked_draw / _view */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -1089,7 +1090,7 @@ VQHIP_API int vqhip_adaptive_cacao(vqhip_ctx* ctx, void* stream, const float* de
  * (R1 vertex stage, R2 clipping against w >= 2^-24 and the four side planes — no z planes: DepthClipEnable is FALSE —, R3 viewport and 16.8 snap, R4 top-left
  * coverage in int64, R5 z/w and R6 LINEAR_DEPTH interpolation); tests/shadow_raster_ref.py states it in numpy. R2, R5 and R6 are UNPINNED against a D3D12
  * device (docs/WARP_CALIBRATION.md §5).
- * Out of scope: the ENABLE_ALPHA_MASK variant, the tessellation and heightmap variants (the null heightmap's + 0.0f is kept), wireframe.
+ * The ENABLE_ALPHA_MASK variant is vqhip_shadow_masked_depth (below). Out of scope: the tessellation and heightmap variants (the null heightmap's + 0.0f is kept), wireframe.
  * Three kernels on `stream` (plus one setup launch per further ~700 draws): counters, triangle setup, tile fill. No allocation, no memset node; the call clears
  * each map itself (uncovered texels read 1.0; a view with numDraws == 0 yields all 1.0). View and draw descriptors are host memory, consumed before the call
  * returns; meshes and matrices are device memory, read when the kernels run. The maps of one call must not overlap each other, the work buffer or the inputs. */
@@ -1132,7 +1133,7 @@ VQHIP_API int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shado
  * report. docs/DESIGN_DETAILS.md §7.17 is the normative statement (V1 vertex stage = R1, V2 clipping against seven planes, V3 viewport, V4 sample positions, V5
  * per-sample z/w and the depth test as one 64-bit minimum); tests/scene_depth_ref.py states it in numpy. V2's z planes (a guard band is as legal), V4's sample
  * positions and V5's interpolation precision are UNPINNED against a D3D12 device (docs/WARP_CALIBRATION.md §5).
- * Out of scope: the ENABLE_ALPHA_MASK variant, the tessellation and heightmap variants (the null heightmap's + 0.0f is kept), wireframe, the pass's normals target
+ * The ENABLE_ALPHA_MASK variant is vqhip_scene_masked_depth (below). Out of scope: the tessellation and heightmap variants (the null heightmap's + 0.0f is kept), wireframe, the pass's normals target
  * (vqhip_scene_normals_from_materials writes it from interpolants). The interpolant planes are vqhip_scene_interpolants' (below), from this call's owner planes.
  * Outputs (pitches in pixels, coverage_pitch in bytes, 0 = dense = width; every pointer but depth may be NULL):
  *   depth           samples 1: float [height][pitch] — the `depth` of vqhip_depth_hierarchy; samples 4: float [height][pitch][4], 16-byte aligned — the depth_ms of
@@ -1201,7 +1202,8 @@ VQHIP_API int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_
  * The table is staged through the context's constant ring (one table-copy launch per ring slot of 556 draws), then ONE kernel (a wave whose 64 pixels share
  * one owner fetches it once; option interp_form lane switches that path off, same bits). No allocation, no memset node, no
  * readback. Draw descriptors are host memory, consumed before the call returns; meshes and matrices are device memory, read when the kernel runs. Not modelled:
- * the heightmap (the null heightmap's float3 add is kept), tessellation, alpha mask. vqhip_gbuffer_from_materials still takes its uv LOD from neighbouring pixels
+ * the heightmap (the null heightmap's float3 add is kept), tessellation. The alpha mask needs nothing here: vqhip_scene_masked_depth keeps discarded fragments out of
+ * the owner plane, and the shading entry points repeat the discard. vqhip_gbuffer_from_materials still takes its uv LOD from neighbouring pixels
  * of the planes, so at primitive edges it differs from a helper-lane derivative. */
 typedef struct vqhip_scene_surface_draw {   /* one DrawIndexedInstanced of the lit pass */
     vqhip_shadow_mesh mesh;                 /* the engine's vertex: position @0, normal @12, tangent @24, uv @36; strideBytes >= 44, a multiple of 4 */
@@ -1233,6 +1235,68 @@ VQHIP_API size_t vqhip_scene_interpolants_work_bytes(int numDraws);
  * or 2^29 or more instanced triangles in one call (the limits of vqhip_scene_depth). */
 VQHIP_API int vqhip_scene_interpolants(vqhip_ctx* ctx, void* stream, const vqhip_scene_surface_draw* draws, int numDraws, int width, int height,
         const uint32_t* owner, int owner_pitch_px, const vqhip_scene_interpolant_targets* out, void* work, size_t workBytes);
+
+/* ---- Alpha-tested geometry in the depth pre-pass and the shadow maps: the "_AlphaMasked" PSO permutations of both passes (PipelineStateObjects.cpp:1617, 1683,
+ * 1731, 1787; drawn by SceneRendering.cpp:1008-1030, 1318-1337), i.e. DepthPrePass.hlsl:155-161 and ShadowDepthPass.hlsl:136-140 compiled with ENABLE_ALPHA_MASK.
+ * vqhip_scene_masked_depth and vqhip_shadow_masked_depth are SUPERSETS of vqhip_scene_depth and vqhip_shadow_depth: outputs, clears, q numbering, limits and
+ * refusal rules are theirs, opaque and masked draws mix freely in one call and share one q sequence (vqhip_scene_interpolants consumes the owner planes
+ * unchanged), and a call without a masked draw launches the very kernels of the opaque entry point. docs/DESIGN_DETAILS.md §7.19 is the normative statement;
+ * tests/masked_depth_ref.py states it in numpy:
+ *   M1  the pixel shader runs once per (primitive, pixel) at the pixel centre — at 4x without `centroid`: a pixel with any covered sample evaluates at its centre
+ *       even when the centre lies outside the triangle (extrapolation, as §7.18) — and a discard removes all of that primitive's samples in the pixel. Shadow
+ *       maps: pixel = texel.
+ *   M2  the uv at the pixel centre is §7.18 I2 / I3: binary64 weights from the UNCLIPPED triangle's binary32 clip-space (x, y, w), one rounding to binary32; the
+ *       decision depends on (q, pixel) only, never on the fan piece of a clipped triangle that covers the sample.
+ *   M3  scene depth: uv * uvScaleOffset.xy + uvScaleOffset.zw as vqhip_gbuffer_from_materials evaluates it; Sample(AnisoSampler) = that call's isotropic trilinear
+ *       WRAP fetch (bias 0); the derivatives come from the 2 x 2 quad aligned to even pixel coordinates, whose other lanes are HELPER LANES: the same primitive
+ *       evaluated by M2 at (i ^ 1, j) and (i, j ^ 1), covered or not, inside the viewport or not. Discard iff HasDiffuseMap(textureConfig) && a < 0.01f.
+ *   M4  shadow: the raw vertex uv (texScaleBias feeds only the heightmap), SampleLevel(.., 0) = the bilinear WRAP fetch of level 0, discard iff a < 0.01f. There
+ *       is NO HasDiffuseMap test in that shader: a masked draw whose diffuse SRV is null (texDiffuseAlpha->texels == NULL) samples 0 and LOSES EVERY FRAGMENT.
+ *       In scene depth a NULL texels with the diffuse bit set discards everything as well; with the bit clear nothing is discarded.
+ *   M5  coverage, top-left rule, depth interpolation, saturate, the < 1.0 rejection and the 64-bit minimum are unchanged: a discarded fragment never reaches the minimum.
+ * M2's precision and M3's derivative form are UNPINNED against a D3D12 device (docs/WARP_CALIBRATION.md §5).
+ * A masked draw's mesh is the engine's vertex: uv at byte 36, strideBytes >= 44. Textures are vqhip_texture2d: RGBA8_UNORM mip chains in device memory; the
+ * descriptors (materials, texDiffuseAlpha) are HOST memory, consumed before the call returns.
+ * (The names put `masked` before `depth` so that the prefixes vqhip_scene_depth* / vqhip_shadow_depth* keep denoting the opaque pair alone.)
+ * Out of scope: the heightmap and tessellation variants, the separate texAlphaMask map (t3: bound, not read by these shaders), the ObjectID and Outline passes'
+ * masked permutations.
+ * Work: the opaque call's layout is the prefix; behind it a device table of the draws' textures (48 bytes per draw, staged through the constant ring like
+ * vqhip_scene_interpolants' table: one table-copy launch per ring slot) and one 64-byte side record per masked instanced triangle (the unclipped clip-space
+ * x, y, w and the uv of its three vertices, the draw's table slot). Kernels with a masked draw: counter(s), table copy, setup, fill. No allocation, no memset
+ * node, no readback. */
+typedef struct vqhip_scene_masked_depth_draw {
+    vqhip_scene_depth_draw draw;
+    const vqhip_material*  material;   /* HOST, or NULL. Masked iff non-NULL and (texDiffuse.reserved & VQHIP_MATERIAL_ALPHA_MASKED). Read: data.uvScaleOffset, data.textureConfig, texDiffuse */
+} vqhip_scene_masked_depth_draw;
+typedef struct vqhip_shadow_masked_draw {
+    vqhip_shadow_draw draw;
+    const vqhip_texture2d* texDiffuseAlpha;   /* HOST, or NULL = the opaque PSO. Non-NULL = the masked PSO, whatever `reserved` holds; texels NULL = null SRV (M4) */
+} vqhip_shadow_masked_draw;
+typedef struct vqhip_shadow_masked_view {      /* vqhip_shadow_view with draws of the type above */
+    float*  depth;  size_t pitchBytes;  int32_t dim;
+    int32_t linearDepth;
+    VQ_float3 cameraPosition;  float farPlane;
+    const vqhip_shadow_masked_draw* draws;  int32_t numDraws;
+} vqhip_shadow_masked_view;
+VQHIP_STATIC_ASSERT(sizeof(vqhip_scene_masked_depth_draw) == 56 && offsetof(vqhip_scene_masked_depth_draw, material) == 48, "vqhip_scene_masked_depth_draw layout");
+VQHIP_STATIC_ASSERT(sizeof(vqhip_shadow_masked_draw) == 64 && offsetof(vqhip_shadow_masked_draw, texDiffuseAlpha) == 56, "vqhip_shadow_masked_draw layout");
+VQHIP_STATIC_ASSERT(sizeof(vqhip_shadow_masked_view) == sizeof(vqhip_shadow_view) && offsetof(vqhip_shadow_masked_view, draws) == offsetof(vqhip_shadow_view, draws),
+                    "vqhip_shadow_masked_view layout");
+/* Bytes of work: vqhip_scene_depth_work_bytes(instancedTriangles) + 48 per draw and 64 per masked instanced triangle (the triangles of the draws that are masked
+ * by the rule above), each part rounded up to 256. 0 where the opaque function returns 0, for maskedInstancedTriangles > instancedTriangles, or numDraws < 0. Host-only. */
+VQHIP_API size_t vqhip_scene_masked_depth_work_bytes(uint64_t instancedTriangles, uint64_t maskedInstancedTriangles, int numDraws);
+/* vqhip_scene_depth's refusals (with the work size above), and VQHIP_ERR_INVALID_ARG — launching nothing, leaving the outputs untouched — for a masked draw whose
+ * strideBytes is below 44, whose texDiffuse has texels and a width or height outside 1 .. 16384, mips < 1 or more than vqhip_mip_level_count(width, height), or
+ * texels that are not 4-byte aligned. */
+VQHIP_API int vqhip_scene_masked_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_masked_depth_draw* draws, int numDraws, int width, int height, int samples,
+        const vqhip_scene_depth_targets* out, void* work, size_t workBytes);
+/* numDraws: the draws of all views. Otherwise as above over vqhip_shadow_depth_work_bytes(instancedTriangles, numViews). */
+VQHIP_API size_t vqhip_shadow_masked_depth_work_bytes(uint64_t instancedTriangles, uint64_t maskedInstancedTriangles, int numViews, int numDraws);
+/* vqhip_shadow_depth's refusals (with the work size above), the masked draw's refusals of vqhip_scene_masked_depth, and VQHIP_ERR_UNSUPPORTED for more than
+ * 10 000 draws in a call that has a masked draw (the texture table and the larger draw jobs share the constant ring with the view table) or 2^32 - 1 or more
+ * masked instanced triangles in one call. */
+VQHIP_API int vqhip_shadow_masked_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_masked_view* views, int numViews, void* work, size_t workBytes);
+#define VQHIP_MASK_TEXTURE_MAX_DIM 16384
 
 #ifdef __cplusplus
 }

@@ -619,6 +619,155 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// Z pre-pass with its "_AlphaMasked" draws == RenderDepthPrePass as the engine runs it on its default content (SceneRendering.cpp:1318-1337: the masked PSO and the
+// diffuse SRV for materials with IsAlphaMasked): vqhip_scene_masked_depth (docs/DESIGN_DETAILS.md §7.19). FDrawParameters is DepthPrePass's plus what the
+// function reads of the materials: MaterialIndex[d] names draw d's entry of Materials (the host array the *_from_materials calls take), a negative index or a
+// missing list draws opaque. The pass builds the vqhip_scene_masked_depth_draw list — material = &Materials[index] — and counts the masked instanced triangles by
+// the header's rule (texDiffuse.reserved has VQHIP_MATERIAL_ALPHA_MASKED) for the work size. A frame without a masked material enqueues what DepthPrePass enqueues.
+// ---------------------------------------------------------------------------------------------------------------
+class MaskedDepthPrePass : public RenderPassBase {
+public:
+    struct FResourceParameters : public IRenderPassResourceCollection {};
+    struct FDrawParameters : public DepthPrePass::FDrawParameters {
+        const std::vector<int32_t>* MaterialIndex = nullptr;                    // per draw, the size of *Draws; < 0: no material (opaque)
+        const vqhip_material* Materials = nullptr; int NumMaterials = 0;        // HOST
+    };
+    explicit MaskedDepthPrePass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    ~MaskedDepthPrePass() override { Free(mWork); }
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { Free(mWork); mWorkBytes = 0; }
+    void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override { mWidth = Width; mHeight = Height; }
+    void OnDestroyWindowSizeDependentResources() override { mWidth = mHeight = 0; }
+    bool Reserve(uint64_t InstancedTriangles, uint64_t MaskedInstancedTriangles, int NumDraws) {
+        const size_t need = vqhip_scene_masked_depth_work_bytes(InstancedTriangles, MaskedInstancedTriangles, NumDraws);
+        if (!need) return false;
+        if (need <= mWorkBytes) return true;
+        Free(mWork); mWorkBytes = 0;
+        mWork = Alloc(need);
+        if (mWork) mWorkBytes = need;
+        return mWork != nullptr;
+    }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p || p->NumLayers < 0 || p->NumLayers > VQHIP_SCENE_DEPTH_MAX_LAYERS) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        const int numDraws = p->Draws ? (int)p->Draws->size() : 0;
+        if (p->MaterialIndex && (int)p->MaterialIndex->size() != numDraws) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        mDraws.resize((size_t)numDraws);
+        uint64_t triangles = 0, masked = 0;
+        for (int d = 0; d < numDraws; ++d) {
+            vqhip_scene_masked_depth_draw& m = mDraws[(size_t)d];
+            m.draw = (*p->Draws)[(size_t)d];
+            const int32_t index = p->MaterialIndex ? (*p->MaterialIndex)[(size_t)d] : -1;
+            if (index >= p->NumMaterials || (index >= 0 && !p->Materials)) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+            m.material = index >= 0 ? p->Materials + index : nullptr;
+            const uint64_t n = (uint64_t)(m.draw.mesh.numIndices / 3) * m.draw.numInstances;
+            triangles += n;
+            if (m.material && (m.material->texDiffuse.reserved & VQHIP_MATERIAL_ALPHA_MASKED)) masked += n;
+        }
+        mMaskedTriangles = masked;
+        if (!Reserve(triangles, masked, numDraws)) { mStatus = VQHIP_ERR_HIP; return; }
+        vqhip_scene_depth_targets t = {};
+        t.depth = p->SceneDepth; t.primitive = p->Primitive; t.layers = p->bMSAA ? p->NumLayers : 0;
+        for (int k = 0; k < t.layers; ++k) { t.coverage[k] = p->Coverage[k]; t.layerPrimitive[k] = p->LayerPrimitive[k]; }
+        mStatus = vqhip_scene_masked_depth(mCtx, p->Stream, numDraws ? mDraws.data() : nullptr, numDraws, (int)mWidth, (int)mHeight, p->bMSAA ? 4 : 1, &t, mWork, mWorkBytes);
+    }
+    const void* GetWorkBuffer() const { return mWork; }
+    size_t GetWorkBytes() const { return mWorkBytes; }
+    uint64_t LastMaskedTriangles() const { return mMaskedTriangles; }
+private:
+    void* mWork = nullptr; size_t mWorkBytes = 0;
+    unsigned mWidth = 0, mHeight = 0;
+    uint64_t mMaskedTriangles = 0;
+    std::vector<vqhip_scene_masked_depth_draw> mDraws;                          // consumed by the call before it returns; kept to spare the allocation
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// Shadow maps with their "_AlphaMasked" draws == DrawShadowViewMeshList picking the masked shadow PSO and binding the diffuse SRV for materials with
+// IsAlphaMasked (SceneRendering.cpp:1008-1030): vqhip_shadow_masked_depth (§7.19). FDrawParameters is ShadowDepthPass's plus, per view, the material index of each
+// draw (a list parallel to the view's draw list; a missing list or a negative index draws opaque) and the host material array. A draw is masked when its material's
+// texDiffuse.reserved has VQHIP_MATERIAL_ALPHA_MASKED: texDiffuseAlpha = &material.texDiffuse — whose texels may be NULL: that shader has no HasDiffuseMap test, the
+// draw then loses every fragment. Views with an empty draw list are skipped, as in ShadowDepthPass.
+// ---------------------------------------------------------------------------------------------------------------
+class MaskedShadowDepthPass : public RenderPassBase {
+public:
+    struct FResourceParameters : public IRenderPassResourceCollection {};
+    struct FDrawParameters : public ShadowDepthPass::FDrawParameters {
+        const std::vector<int32_t>* DirectionalMaterialIndex = nullptr;
+        const std::vector<int32_t>* SpotMaterialIndex[VQ_NUM_SHADOWING_LIGHTS__SPOT] = {};
+        const std::vector<int32_t>* PointMaterialIndex[VQ_NUM_SHADOWING_LIGHTS__POINT * 6] = {};
+        const vqhip_material* Materials = nullptr; int NumMaterials = 0;        // HOST
+    };
+    explicit MaskedShadowDepthPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    ~MaskedShadowDepthPass() override { Free(mWork); }
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { Free(mWork); mWorkBytes = 0; }
+    void OnCreateWindowSizeDependentResources(unsigned, unsigned, const IRenderPassResourceCollection* = nullptr) override {}   // shadow maps do not follow the window
+    void OnDestroyWindowSizeDependentResources() override {}
+    bool Reserve(uint64_t InstancedTriangles, uint64_t MaskedInstancedTriangles, int NumDraws) {
+        const size_t need = vqhip_shadow_masked_depth_work_bytes(InstancedTriangles, MaskedInstancedTriangles, VQHIP_SHADOW_MAX_VIEWS, NumDraws);
+        if (!need) return false;
+        if (need <= mWorkBytes) return true;
+        Free(mWork); mWorkBytes = 0;
+        mWork = Alloc(need);
+        if (mWork) mWorkBytes = need;
+        return mWork != nullptr;
+    }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p || p->NumSpotShadowViews > VQ_NUM_SHADOWING_LIGHTS__SPOT || p->NumPointShadowViews > VQ_NUM_SHADOWING_LIGHTS__POINT) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        constexpr int kMaxViews = 1 + VQ_NUM_SHADOWING_LIGHTS__SPOT + 6 * VQ_NUM_SHADOWING_LIGHTS__POINT;
+        vqhip_shadow_masked_view views[kMaxViews];
+        size_t first[kMaxViews];                                                 // where each view's draws start in mDraws (the vector may move while it grows)
+        int n = 0;
+        uint64_t triangles = 0, masked = 0;
+        bool ok = true;
+        mDraws.clear();
+        auto add = [&](const std::vector<vqhip_shadow_draw>* draws, const std::vector<int32_t>* index, float* map, int dim, int linear, VQ_float3 pos, float farPlane) {
+            if (!draws || draws->empty()) return;
+            if (index && index->size() != draws->size()) { ok = false; return; }
+            vqhip_shadow_masked_view& v = views[n];
+            v.depth = map; v.pitchBytes = 0; v.dim = dim; v.linearDepth = linear; v.cameraPosition = pos; v.farPlane = farPlane;
+            v.draws = nullptr; v.numDraws = (int32_t)draws->size();
+            first[n++] = mDraws.size();
+            for (size_t d = 0; d < draws->size(); ++d) {
+                vqhip_shadow_masked_draw m;
+                m.draw = (*draws)[d];
+                m.texDiffuseAlpha = nullptr;
+                const int32_t k = index ? (*index)[d] : -1;
+                if (k >= p->NumMaterials || (k >= 0 && !p->Materials)) { ok = false; return; }
+                const uint64_t t = (uint64_t)(m.draw.mesh.numIndices / 3) * m.draw.numInstances;
+                triangles += t;
+                if (k >= 0 && (p->Materials[k].texDiffuse.reserved & VQHIP_MATERIAL_ALPHA_MASKED)) { m.texDiffuseAlpha = &p->Materials[k].texDiffuse; masked += t; }
+                mDraws.push_back(m);
+            }
+        };
+        const VQ_float3 zero = { 0.0f, 0.0f, 0.0f };
+        add(p->DirectionalDraws, p->DirectionalMaterialIndex, p->ShadowMapsDirectional, p->DirectionalDim, 0, zero, 1.0f);
+        for (unsigned i = 0; i < p->NumSpotShadowViews; ++i)
+            add(p->SpotDraws[i], p->SpotMaterialIndex[i], p->ShadowMapsSpot ? p->ShadowMapsSpot + (size_t)i * p->SpotDim * p->SpotDim : nullptr, p->SpotDim, 0, zero, 1.0f);
+        for (unsigned i = 0; i < p->NumPointShadowViews; ++i)
+            for (unsigned face = 0; face < 6; ++face)
+                add(p->PointDraws[i * 6 + face], p->PointMaterialIndex[i * 6 + face],
+                    p->ShadowMapsPoint ? p->ShadowMapsPoint + (size_t)(i * 6 + face) * p->PointDim * p->PointDim : nullptr, p->PointDim, 1, p->PointPosition[i], p->PointRange[i]);
+        if (!ok) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        mNumViews = n; mMaskedTriangles = masked;
+        if (n == 0) { mStatus = VQHIP_OK; return; }                              // nothing casts a shadow this frame
+        for (int v = 0; v < n; ++v) views[v].draws = mDraws.data() + first[v];
+        if (!Reserve(triangles, masked, (int)mDraws.size())) { mStatus = VQHIP_ERR_HIP; return; }
+        mStatus = vqhip_shadow_masked_depth(mCtx, p->Stream, views, n, mWork, mWorkBytes);
+    }
+    const void* GetWorkBuffer() const { return mWork; }
+    size_t GetWorkBytes() const { return mWorkBytes; }
+    int LastViewCount() const { return mNumViews; }
+    uint64_t LastMaskedTriangles() const { return mMaskedTriangles; }
+private:
+    void* mWork = nullptr; size_t mWorkBytes = 0;
+    int mNumViews = 0;
+    uint64_t mMaskedTriangles = 0;
+    std::vector<vqhip_shadow_masked_draw> mDraws;                               // all views' draws, consumed by the call before it returns
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // The lit draw's vertex stage and interpolation == what VQRenderer::RenderSceneColor (SceneRendering.cpp:1619-1760) leaves to the rasteriser between the draw call
 // and PSMain: vqhip_scene_interpolants. FDrawParameters carries the pass's draw list (FSceneDrawData::mainViewDrawParams again, each FInstancedDrawParameters as a
 // vqhip_scene_surface_draw whose four matrix blocks are the uploaded PerObjectLightingData and whose materialIndex is the draw's material) — the SAME list, in the

@@ -269,6 +269,22 @@ class SceneInterpolantTargets(C.Structure):  # vqhip_scene_interpolant_targets
                 ("pitch", C.c_int32), ("sv_pitch", C.c_int32)]
 
 
+class SceneDepthMaskedDraw(C.Structure):  # vqhip_scene_masked_depth_draw
+    _fields_ = [("draw", SceneDepthDraw), ("material", C.POINTER(MaterialDesc))]
+
+
+class ShadowMaskedDraw(C.Structure):  # vqhip_shadow_masked_draw
+    _fields_ = [("draw", ShadowDraw), ("texDiffuseAlpha", C.POINTER(Texture2D))]
+
+
+class ShadowMaskedView(C.Structure):  # vqhip_shadow_masked_view
+    _fields_ = [("depth", C.c_void_p), ("pitchBytes", C.c_size_t), ("dim", C.c_int32), ("linearDepth", C.c_int32), ("cameraPosition", float3), ("farPlane", C.c_float),
+                ("draws", C.POINTER(ShadowMaskedDraw)), ("numDraws", C.c_int32)]
+
+
+MASK_TEXTURE_MAX_DIM = 16384                 # VQHIP_MASK_TEXTURE_MAX_DIM
+MASK_TABLE_ENTRY_BYTES = 48                  # one draw's entry of the masked rasterisers' texture table in their work buffer
+MASK_SIDE_RECORD_BYTES = 64                  # one masked instanced triangle's side record
 SURFACE_VERTEX_BYTES = 44                    # the engine's vertex: position @0, normal @12, tangent @24, uv @36
 SURFACE_JOB_BYTES = 80                       # one draw's entry of vqhip_scene_interpolants' table in its work buffer
 
@@ -303,6 +319,9 @@ _chk(SceneDepthDraw, 48, matWorldViewProj=32, numInstances=40, cullMode=44)
 _chk(SceneDepthTargets, 96, primitive=8, coverage=16, layerPrimitive=48, layers=80, pitch=84, coverage_pitch=88, reserved=92)
 _chk(SceneSurfaceDraw, 72, matWorldViewProj=32, matWorld=40, matNormal=48, matWorldViewProjPrev=56, numInstances=64, materialIndex=68)
 _chk(SceneInterpolantTargets, 48, ip1=8, ip2=16, svPositionCurr=24, svPositionPrev=32, pitch=40, sv_pitch=44)
+_chk(SceneDepthMaskedDraw, 56, material=48)
+_chk(ShadowMaskedDraw, 64, texDiffuseAlpha=56)
+_chk(ShadowMaskedView, 56, pitchBytes=8, dim=16, linearDepth=20, cameraPosition=24, farPlane=36, draws=40, numDraws=48)
 _chk(ShadowView, 56, pitchBytes=8, dim=16, linearDepth=20, cameraPosition=24, farPlane=36, draws=40, numDraws=48)
 _chk(CacaoConstants, 384, EffectRadius=48, InvSharpness=96, PassIndex=100, PatternRotScaleMatrices=112, NormalsUnpackMul=192, SSAOBufferDimensions=208,
      DepthBufferOffset=240, PerPassFullResUVOffset=248, DeinterleavedDepthBufferNormalisedOffset=312, NormalsWorldToViewspaceMatrix=320)

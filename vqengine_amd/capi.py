@@ -115,6 +115,10 @@ def load_library():
         "vqhip_scene_depth_work_bytes": (sz, [C.c_uint64]),
         "vqhip_scene_depth": (i32, [vp, vp, C.POINTER(abi.SceneDepthDraw), i32, i32, i32, i32, C.POINTER(abi.SceneDepthTargets), vp, sz]),
         "vqhip_scene_interpolants_work_bytes": (sz, [i32]),
+        "vqhip_scene_masked_depth_work_bytes": (sz, [C.c_uint64, C.c_uint64, i32]),
+        "vqhip_scene_masked_depth": (i32, [vp, vp, C.POINTER(abi.SceneDepthMaskedDraw), i32, i32, i32, i32, C.POINTER(abi.SceneDepthTargets), vp, sz]),
+        "vqhip_shadow_masked_depth_work_bytes": (sz, [C.c_uint64, C.c_uint64, i32, i32]),
+        "vqhip_shadow_masked_depth": (i32, [vp, vp, C.POINTER(abi.ShadowMaskedView), i32, vp, sz]),
         "vqhip_scene_interpolants": (i32, [vp, vp, C.POINTER(abi.SceneSurfaceDraw), i32, i32, i32, vp, i32, C.POINTER(abi.SceneInterpolantTargets), vp, sz]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
@@ -153,6 +157,7 @@ EXPORTED_SYMBOLS = [
     "vqhip_shadow_depth", "vqhip_shadow_depth_work_bytes",
     "vqhip_scene_depth", "vqhip_scene_depth_work_bytes",
     "vqhip_scene_interpolants", "vqhip_scene_interpolants_work_bytes",
+    "vqhip_scene_masked_depth", "vqhip_scene_masked_depth_work_bytes", "vqhip_shadow_masked_depth", "vqhip_shadow_masked_depth_work_bytes",
 ]
 
 
@@ -191,6 +196,26 @@ class ShadowDraw:
 
     def __init__(self, positions, indices, wvp, world=None, cull=abi.CULL_NONE):
         self.positions, self.indices, self.wvp, self.world, self.cull = positions, indices, wvp, world, cull
+
+
+class MaskedDraw(ShadowDraw):
+    """A ShadowDraw for vqhip_scene_masked_depth / vqhip_shadow_masked_depth: positions are the engine's vertex (cuda float32 [V, k >= 11], uv at floats 9, 10).
+    material: abi.MaterialDesc (host) or None, read by scene_masked_depth — masked iff texDiffuse.reserved has abi.MATERIAL_ALPHA_MASKED; texture: abi.Texture2D
+    (host descriptor of a cuda RGBA8 mip chain; texels None = null SRV) or None, read by shadow_masked_depth — masked iff not None."""
+
+    def __init__(self, positions, indices, wvp, world=None, cull=abi.CULL_NONE, material=None, texture=None):
+        super().__init__(positions, indices, wvp, world, cull)
+        self.material, self.texture = material, texture
+
+
+def scene_masked_depth_work_bytes(instanced_triangles, masked_instanced_triangles, num_draws):
+    """vqhip_scene_masked_depth_work_bytes. Host-only."""
+    return load_library().vqhip_scene_masked_depth_work_bytes(int(instanced_triangles), int(masked_instanced_triangles), int(num_draws))
+
+
+def shadow_masked_depth_work_bytes(instanced_triangles, masked_instanced_triangles, num_views, num_draws):
+    """vqhip_shadow_masked_depth_work_bytes (num_draws: the draws of all views). Host-only."""
+    return load_library().vqhip_shadow_masked_depth_work_bytes(int(instanced_triangles), int(masked_instanced_triangles), int(num_views), int(num_draws))
 
 
 class ShadowView:
@@ -600,21 +625,38 @@ class Context:
     def shadow_depth_prepared(self, views, work=None):
         """The descriptors of a shadow_depth call built once: returns (call, work) with call(stream=None) issuing vqhip_shadow_depth on the same views again
         (a frame loop, a benchmark). The tensors of `views` must stay alive and in place."""
+        return self._shadow_depth_prepared("shadow_depth", False, views, work)
+
+    def shadow_masked_depth(self, views, work=None, stream=None):
+        """vqhip_shadow_masked_depth: shadow_depth with alpha-tested draws. A draw that is a MaskedDraw with a `texture` (abi.Texture2D over a cuda RGBA8 mip chain;
+        texels None = null SRV, which loses every fragment) is drawn through the "_AlphaMasked" shadow PSO; its positions are the engine's vertex (k >= 11).
+        Any other draw is opaque. Returns work."""
+        call, work = self.shadow_masked_depth_prepared(views, work)
+        call(stream)
+        return work
+
+    def shadow_masked_depth_prepared(self, views, work=None):
+        """shadow_depth_prepared for vqhip_shadow_masked_depth"""
+        return self._shadow_depth_prepared("shadow_masked_depth", True, views, work)
+
+    def _shadow_depth_prepared(self, who_, masked, views, work):
         views = list(views)
         if not 1 <= len(views) <= abi.SHADOW_MAX_VIEWS:
-            raise ValueError(f"shadow_depth: expected 1..{abi.SHADOW_MAX_VIEWS} views, got {len(views)}")
-        cviews = (abi.ShadowView * len(views))()
+            raise ValueError(f"{who_}: expected 1..{abi.SHADOW_MAX_VIEWS} views, got {len(views)}")
+        cviews = ((abi.ShadowMaskedView if masked else abi.ShadowView) * len(views))()
+        masked_tris = num_draws = 0
         keep = []
         for i, v in enumerate(views):
             d = v.depth
             if not (d.is_cuda and d.dtype == torch.float32 and d.dim() == 2 and d.shape[0] == d.shape[1] and d.stride(1) == 1 and d.stride(0) >= d.shape[1]):
-                raise ValueError(f"shadow_depth: view {i}: depth: expected cuda float32 [dim, dim] with unit column stride, got {tuple(d.shape)} {d.dtype} strides {d.stride()}")
+                raise ValueError(f"{who_}: view {i}: depth: expected cuda float32 [dim, dim] with unit column stride, got {tuple(d.shape)} {d.dtype} strides {d.stride()}")
             if not 1 <= d.shape[0] <= abi.SHADOW_MAX_DIM:
-                raise ValueError(f"shadow_depth: view {i}: dim must be 1..{abi.SHADOW_MAX_DIM}")
-            cdraws = (abi.ShadowDraw * max(1, len(v.draws)))()
+                raise ValueError(f"{who_}: view {i}: dim must be 1..{abi.SHADOW_MAX_DIM}")
+            cdraws = ((abi.ShadowMaskedDraw if masked else abi.ShadowDraw) * max(1, len(v.draws)))()
+            num_draws += len(v.draws)
             keep.append(cdraws)
             for j, dr in enumerate(v.draws):
-                who = f"shadow_depth: view {i} draw {j}"
+                who = f"{who_}: view {i} draw {j}"
                 p, ix = dr.positions, dr.indices
                 if not (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and p.shape[1] >= 3 and p.stride(1) == 1 and p.stride(0) >= p.shape[1]):
                     raise ValueError(f"{who}: positions: expected cuda float32 [V, k >= 3] with unit column stride")
@@ -632,6 +674,17 @@ class Context:
                 if dr.cull not in (abi.CULL_NONE, abi.CULL_FRONT, abi.CULL_BACK):
                     raise ValueError(f"{who}: cull: expected abi.CULL_NONE, CULL_FRONT or CULL_BACK")
                 c = cdraws[j]
+                if masked:
+                    tex = getattr(dr, "texture", None)
+                    if tex is not None:
+                        if not isinstance(tex, abi.Texture2D):
+                            raise ValueError(f"{who}: texture: expected abi.Texture2D or None")
+                        if p.shape[1] < 11:
+                            raise ValueError(f"{who}: a masked draw needs the engine's vertex, float32 [V, k >= 11] (uv at floats 9, 10)")
+                        c.texDiffuseAlpha = C.pointer(tex)
+                        keep.append(tex)
+                        masked_tris += (ix.numel() // 3) * n
+                    c = c.draw
                 c.mesh.positions, c.mesh.strideBytes, c.mesh.numVertices = p.data_ptr(), p.stride(0) * 4, p.shape[0]
                 c.mesh.indices, c.mesh.indexBits, c.mesh.numIndices = ix.data_ptr(), bits, ix.numel()
                 c.matWorldViewProj, c.matWorld = dr.wvp.data_ptr(), (dr.world.data_ptr() if dr.world is not None else None)
@@ -640,16 +693,18 @@ class Context:
             cv.depth, cv.pitchBytes, cv.dim, cv.linearDepth = d.data_ptr(), d.stride(0) * 4, d.shape[0], int(v.linear)
             cv.cameraPosition = abi.float3(*[float(x) for x in v.camera])
             cv.farPlane, cv.numDraws = v.far, len(v.draws)
-            cv.draws = C.cast(cdraws, C.POINTER(abi.ShadowDraw))
-        need = shadow_depth_work_bytes(sum(v.instanced_triangles() for v in views), len(views))
+            cv.draws = C.cast(cdraws, C.POINTER(abi.ShadowMaskedDraw if masked else abi.ShadowDraw))
+        tris = sum(v.instanced_triangles() for v in views)
+        need = shadow_masked_depth_work_bytes(tris, masked_tris, len(views), num_draws) if masked else shadow_depth_work_bytes(tris, len(views))
         if work is None:
             work = torch.empty((need,), dtype=torch.uint8, device=self.device)
         if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.numel() >= need):
-            raise ValueError(f"shadow_depth: work: expected a contiguous cuda uint8 tensor of at least {need} bytes")
+            raise ValueError(f"{who_}: work: expected a contiguous cuda uint8 tensor of at least {need} bytes")
         keep.append(views)
 
         def call(stream=None, _keep=keep):
-            self._ck(self.lib.vqhip_shadow_depth(self._h, self._stream(stream), cviews, len(views), _ptr(work), work.numel()))
+            fn = self.lib.vqhip_shadow_masked_depth if masked else self.lib.vqhip_shadow_depth
+            self._ck(fn(self._h, self._stream(stream), cviews, len(views), _ptr(work), work.numel()))
         return call, work
 
     def scene_depth(self, draws, width, height, samples=1, primitive=False, layers=0, layer_primitive=True, out=None, work=None, stream=None):
@@ -665,14 +720,29 @@ class Context:
     def scene_depth_prepared(self, draws, width, height, samples=1, primitive=False, layers=0, layer_primitive=True, out=None, work=None):
         """The descriptors of a scene_depth call built once: returns (call, result) with call(stream=None) issuing vqhip_scene_depth on the same draws and
         targets again. The tensors must stay alive and in place."""
+        return self._scene_depth_prepared("scene_depth", False, draws, width, height, samples, primitive, layers, layer_primitive, out, work)
+
+    def scene_masked_depth(self, draws, width, height, samples=1, primitive=False, layers=0, layer_primitive=True, out=None, work=None, stream=None):
+        """vqhip_scene_masked_depth: scene_depth with alpha-tested draws. A draw that is a MaskedDraw with a `material` (abi.MaterialDesc, host; its texDiffuse over
+        a cuda RGBA8 mip chain) whose texDiffuse.reserved has abi.MATERIAL_ALPHA_MASKED is drawn through the "_AlphaMasked" pre-pass PSO; its positions are the
+        engine's vertex (k >= 11). Any other draw is opaque. Same arguments and result as scene_depth."""
+        call, res = self.scene_masked_depth_prepared(draws, width, height, samples, primitive, layers, layer_primitive, out, work)
+        call(stream)
+        return res
+
+    def scene_masked_depth_prepared(self, draws, width, height, samples=1, primitive=False, layers=0, layer_primitive=True, out=None, work=None):
+        """scene_depth_prepared for vqhip_scene_masked_depth"""
+        return self._scene_depth_prepared("scene_masked_depth", True, draws, width, height, samples, primitive, layers, layer_primitive, out, work)
+
+    def _scene_depth_prepared(self, who_, masked, draws, width, height, samples, primitive, layers, layer_primitive, out, work):
         draws, out = list(draws), dict(out or {})
         w, h = int(width), int(height)
         if samples not in (1, 4):
-            raise ValueError(f"scene_depth: samples: expected 1 or 4, got {samples}")
+            raise ValueError(f"{who_}: samples: expected 1 or 4, got {samples}")
         if not 0 <= layers <= abi.SCENE_DEPTH_MAX_LAYERS or (samples == 1 and layers):
-            raise ValueError("scene_depth: layers: expected 0..4, and 0 at samples 1")
+            raise ValueError(f"{who_}: layers: expected 0..4, and 0 at samples 1")
         if not (1 <= w <= abi.SCENE_DEPTH_MAX_DIM and 1 <= h <= abi.SCENE_DEPTH_MAX_DIM):
-            raise ValueError(f"scene_depth: width and height must be 1..{abi.SCENE_DEPTH_MAX_DIM}")
+            raise ValueError(f"{who_}: width and height must be 1..{abi.SCENE_DEPTH_MAX_DIM}")
         shape = (h, w) if samples == 1 else (h, w, 4)
 
         def plane(key, dtype, shp, t):
@@ -681,7 +751,7 @@ class Context:
             px = 1 if len(shp) == 2 else shp[2]
             if not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == tuple(shp) and t.stride(-1) == 1 and (len(shp) == 2 or t.stride(1) == px)
                     and t.stride(0) % px == 0 and t.stride(0) >= w * px):
-                raise ValueError(f"scene_depth: {key}: expected cuda {dtype} {tuple(shp)} with dense pixels, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+                raise ValueError(f"{who_}: {key}: expected cuda {dtype} {tuple(shp)} with dense pixels, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
             return t, t.stride(0) // px
         res, pitches, cov_pitches = {}, set(), set()
         res["depth"], p = plane("depth", torch.float32, shape, out.get("depth"))
@@ -704,11 +774,12 @@ class Context:
                     res["layer_primitive"].append(t)
                     pitches.add(p)
         if len(pitches) != 1 or len(cov_pitches) > 1:
-            raise ValueError("scene_depth: depth, primitive and layer_primitive share one pitch in pixels, the coverage planes one pitch in bytes")
-        cdraws = (abi.SceneDepthDraw * max(1, len(draws)))()
-        tris = 0
+            raise ValueError(f"{who_}: depth, primitive and layer_primitive share one pitch in pixels, the coverage planes one pitch in bytes")
+        cdraws = ((abi.SceneDepthMaskedDraw if masked else abi.SceneDepthDraw) * max(1, len(draws)))()
+        tris = masked_tris = 0
+        keep_mats = []
         for j, dr in enumerate(draws):
-            who = f"scene_depth: draw {j}"
+            who = f"{who_}: draw {j}"
             p, ix = dr.positions, dr.indices
             if not (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and p.shape[1] >= 3 and p.stride(1) == 1 and p.stride(0) >= p.shape[1]):
                 raise ValueError(f"{who}: positions: expected cuda float32 [V, k >= 3] with unit column stride")
@@ -723,15 +794,27 @@ class Context:
             if dr.cull not in (abi.CULL_NONE, abi.CULL_FRONT, abi.CULL_BACK):
                 raise ValueError(f"{who}: cull: expected abi.CULL_NONE, CULL_FRONT or CULL_BACK")
             c = cdraws[j]
+            if masked:
+                mat = getattr(dr, "material", None)
+                if mat is not None:
+                    if not isinstance(mat, abi.MaterialDesc):
+                        raise ValueError(f"{who}: material: expected abi.MaterialDesc or None")
+                    c.material = C.pointer(mat)
+                    keep_mats.append(mat)
+                    if mat.texDiffuse.reserved & abi.MATERIAL_ALPHA_MASKED:
+                        if p.shape[1] < 11:
+                            raise ValueError(f"{who}: a masked draw needs the engine's vertex, float32 [V, k >= 11] (uv at floats 9, 10)")
+                        masked_tris += (ix.numel() // 3) * m.shape[0]
+                c = c.draw
             c.mesh.positions, c.mesh.strideBytes, c.mesh.numVertices = p.data_ptr(), p.stride(0) * 4, p.shape[0]
             c.mesh.indices, c.mesh.indexBits, c.mesh.numIndices = ix.data_ptr(), bits, ix.numel()
             c.matWorldViewProj, c.numInstances, c.cullMode = m.data_ptr(), m.shape[0], dr.cull
             tris += (ix.numel() // 3) * m.shape[0]
-        need = scene_depth_work_bytes(tris)
+        need = scene_masked_depth_work_bytes(tris, masked_tris, len(draws)) if masked else scene_depth_work_bytes(tris)
         if work is None:
             work = torch.empty((need,), dtype=torch.uint8, device=self.device)
         if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.numel() >= need and need):
-            raise ValueError(f"scene_depth: work: expected a contiguous cuda uint8 tensor of at least {need} bytes (0: too many triangles)")
+            raise ValueError(f"{who_}: work: expected a contiguous cuda uint8 tensor of at least {need} bytes (0: too many triangles)")
         res["work"] = work
         tg = abi.SceneDepthTargets()
         tg.depth = res["depth"].data_ptr()
@@ -740,10 +823,11 @@ class Context:
             tg.coverage[k] = res["coverage"][k].data_ptr()
             tg.layerPrimitive[k] = res["layer_primitive"][k].data_ptr() if layer_primitive else None
         tg.layers, tg.pitch, tg.coverage_pitch = layers, pitches.pop(), (cov_pitches.pop() if cov_pitches else 0)
-        keep = (draws, res)
+        keep = (draws, res, keep_mats)
 
         def call(stream=None, _keep=keep):
-            self._ck(self.lib.vqhip_scene_depth(self._h, self._stream(stream), cdraws, len(draws), w, h, samples, C.byref(tg), _ptr(work), work.numel()))
+            fn = self.lib.vqhip_scene_masked_depth if masked else self.lib.vqhip_scene_depth
+            self._ck(fn(self._h, self._stream(stream), cdraws, len(draws), w, h, samples, C.byref(tg), _ptr(work), work.numel()))
         return call, res
 
     def scene_interpolants(self, draws, width, height, owner, sv=False, out=None, work=None, stream=None):

@@ -11,6 +11,7 @@
 #include <atomic>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include "vq_internal.h"
 #include "vq_devmath.h"      // vqd::sincos_ is __host__ __device__: frame-uniform trigonometry is evaluated here, once
@@ -1796,6 +1797,61 @@ constexpr size_t kRasterJobsPerSlot = kConstSlotBytes / sizeof(RasterJob);
 constexpr size_t kRasterMaxDraws = 20000;                      // at most 29 job slots of the 32-slot ring beside the view table's
 static_assert(sizeof(RasterView) * VQHIP_SHADOW_MAX_VIEWS <= kConstSlotBytes, "the view table fits one ring slot");
 static_assert((kRasterMaxDraws + kRasterJobsPerSlot - 1) / kRasterJobsPerSlot + 1 < vqhip_ctx::kSlots, "one call never meets its own view-table slot again");
+// ---- §7.19: what the masked entry points add to both rasterisers' host side ----
+constexpr size_t kMaskTexPerSlot = kConstSlotBytes / sizeof(MaskTex);
+int hostTrunc(float x) { return x != x ? 0 : (int)(x < -2147483520.0f ? -2147483520.0f : x > 2147483520.0f ? 2147483520.0f : x); }     // vq_devmath.h f2i_trunc
+const char* badMaskTexture(const vqhip_texture2d& t) {        // NULL = usable
+    if (!t.texels) return nullptr;                             // a null SRV samples 0
+    if (t.width < 1 || t.width > VQHIP_MASK_TEXTURE_MAX_DIM || t.height < 1 || t.height > VQHIP_MASK_TEXTURE_MAX_DIM) return "masked texture: width and height must be 1..16384";
+    if (t.mips < 1 || t.mips > vqhip_mip_level_count(t.width, t.height)) return "masked texture: mips must be 1..vqhip_mip_level_count(width, height)";
+    if ((uintptr_t)t.texels % 4) return "masked texture: texels must be 4-byte aligned";
+    return nullptr;
+}
+constexpr size_t kRasterMaxMaskedDraws = 10000;                // vqhip_shadow_masked_depth with a masked draw: table slots + job slots + the view table's stay inside the ring
+static_assert((kRasterMaxMaskedDraws + kMaskTexPerSlot - 1) / kMaskTexPerSlot + (kRasterMaxMaskedDraws + kConstSlotBytes / sizeof(RasterMaskedJob) - 1) / (kConstSlotBytes / sizeof(RasterMaskedJob)) + 1
+              < vqhip_ctx::kSlots, "one masked call never meets its own view-table slot again");
+// What the kernels' range guards rest on (vq_raster_mask.h loadMaskTri, the `at < sideCap` of both setup kernels: memory safety only — a guard that fired would
+// draw a masked triangle solid, so these must hold): (1) a job's firstMasked is the running sum, ACROSS ring slots, of numTris * numInstances of the jobs before it
+// whose maskSlot != 0, in the order the table was filled; (2) MaskArgs.sideCap is that sum over the whole call — sideTris in the scene call (draws that can discard),
+// maskedTris in the shadow call (draws with a texture) — and never exceeds the masked count the work size was computed from; (3) 1 + the side index fits the
+// record's 32-bit stamp: below 2^29 instanced triangles in a scene call, below 2^32 / 6 per view and 2^40 per call checked as 32 bits in a shadow call — the shadow
+// call therefore refuses 2^32 - 1 or more masked instanced triangles; (4) MaskArgs.tableCap is the number of table entries staged, and maskSlot - 1 indexes them.
+// prefix | MaskTex[numDraws] | MaskSide[masked]; false when the sizes do not fit
+bool maskLayout(size_t prefix, uint64_t instancedTriangles, uint64_t maskedTriangles, int numDraws, size_t* table, size_t* side, size_t* total) {
+    if (!prefix || numDraws < 0 || maskedTriangles > instancedTriangles) return false;
+    const uint64_t tb = prefix, sd = align256(tb + (uint64_t)(numDraws > 0 ? numDraws : 1) * sizeof(MaskTex)), t = align256(sd + maskedTriangles * sizeof(MaskSide));
+    if (t > (uint64_t)SIZE_MAX) return false;
+    *table = (size_t)tb; *side = (size_t)sd; *total = (size_t)t;
+    return true;
+}
+// the table of a masked call into the work buffer, through ring slots (one k_table_copy launch per slot), as vqhip_scene_interpolants stages its draw table
+int stageMaskTable(vqhip_ctx* ctx, hipStream_t st, const std::vector<MaskTex>& host, MaskTex* dev, const char* who) {
+    size_t done = 0;
+    while (done < host.size()) {
+        int slot;
+        if (int rc = acquireSlot(ctx, &slot)) return rc;
+        const size_t n = host.size() - done < kMaskTexPerSlot ? host.size() - done : kMaskTexPerSlot;
+        std::memcpy(ctx->hostRing + (size_t)slot * kConstSlotBytes, host.data() + done, n * sizeof(MaskTex));
+        if (int rc = commitSlot(ctx, slot, n * sizeof(MaskTex), st)) return rc;
+        hipError_t e = launch_table_copy(st, ctx->devRing + (size_t)slot * kConstSlotBytes, dev + done, (uint32_t)(n * (sizeof(MaskTex) / 16)));
+        if (e != hipSuccess) return failHip(ctx, e, (std::string(who) + " table-copy launch").c_str());
+        if (int rc = releaseSlot(ctx, slot, st)) return rc;
+        done += n;
+    }
+    return VQHIP_OK;
+}
+// the two draw types of each rasteriser behind one set of accessors (overloads: C++ linkage)
+extern "C++" {
+const vqhip_shadow_draw& baseDraw(const vqhip_shadow_draw& d) { return d; }
+const vqhip_shadow_draw& baseDraw(const vqhip_shadow_masked_draw& d) { return d.draw; }
+const vqhip_texture2d* maskTexture(const vqhip_shadow_draw&) { return nullptr; }
+const vqhip_texture2d* maskTexture(const vqhip_shadow_masked_draw& d) { return d.texDiffuseAlpha; }
+const vqhip_scene_depth_draw& baseDraw(const vqhip_scene_depth_draw& d) { return d; }
+const vqhip_scene_depth_draw& baseDraw(const vqhip_scene_masked_depth_draw& d) { return d.draw; }
+const vqhip_material* maskMaterial(const vqhip_scene_depth_draw&) { return nullptr; }
+const vqhip_material* maskMaterial(const vqhip_scene_masked_depth_draw& d) { return d.material && (d.material->texDiffuse.reserved & VQHIP_MATERIAL_ALPHA_MASKED) ? d.material : nullptr; }
+} // extern "C++"
+
 // counters | boxes[6 n] | records[6 n]; false when the sizes do not fit
 bool rasterLayout(uint64_t instancedTriangles, size_t* boxes, size_t* records, size_t* total) {
     if (instancedTriangles > ((uint64_t)1 << 40)) return false;
@@ -1813,22 +1869,27 @@ size_t vqhip_shadow_depth_work_bytes(uint64_t instancedTriangles, int numViews) 
     return t;
 }
 
-int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_view* views, int numViews, void* work, size_t workBytes) {
+// vqhip_shadow_depth (VIEW = vqhip_shadow_view) and vqhip_shadow_masked_depth (VIEW = vqhip_shadow_masked_view): one body, entered with the context guard held; `who` names the entry point in messages.
+// A call without a masked draw enqueues exactly what vqhip_shadow_depth enqueues.
+extern "C++" {
+template <class VIEW>
+int shadowDepthCall(vqhip_ctx* ctx, void* stream, const VIEW* views, int numViews, void* work, size_t workBytes, const std::string& who) {
+    constexpr bool kMaskedEntry = !std::is_same<VIEW, vqhip_shadow_view>::value;
     vqk::Range range_("RenderShadowMaps");
-    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "shadow_depth: ctx is NULL");
-    CTX_GUARD(ctx, "shadow_depth");
-    if (!views || !work) return fail(ctx, VQHIP_ERR_INVALID_ARG, "shadow_depth: NULL argument");
-    if (numViews < 1 || numViews > VQHIP_SHADOW_MAX_VIEWS) return fail(ctx, VQHIP_ERR_INVALID_ARG, "shadow_depth: numViews must be 1..64");
-    if ((uintptr_t)work % 256) return fail(ctx, VQHIP_ERR_INVALID_ARG, "shadow_depth: work must be 256-byte aligned");
+    if (!views || !work) return fail(ctx, VQHIP_ERR_INVALID_ARG, who + ": NULL argument");
+    if (numViews < 1 || numViews > VQHIP_SHADOW_MAX_VIEWS) return fail(ctx, VQHIP_ERR_INVALID_ARG, who + ": numViews must be 1..64");
+    if ((uintptr_t)work % 256) return fail(ctx, VQHIP_ERR_INVALID_ARG, who + ": work must be 256-byte aligned");
     const int tile = ctx->opt.rasterTile ? ctx->opt.rasterTile : 32;
     auto bad = [&](int v, int d, const char* m) {
-        return fail(ctx, VQHIP_ERR_INVALID_ARG, "shadow_depth: view " + std::to_string(v) + (d >= 0 ? " draw " + std::to_string(d) : std::string()) + ": " + m);
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, who + ": view " + std::to_string(v) + (d >= 0 ? " draw " + std::to_string(d) : std::string()) + ": " + m);
     };
     RasterView hv[VQHIP_SHADOW_MAX_VIEWS];
-    uint64_t totalTris = 0, fillBlocks = 0;
-    size_t numJobs = 0;
+    uint64_t totalTris = 0, fillBlocks = 0, maskedTris = 0;
+    size_t numJobs = 0, numDrawsAll = 0;
+    std::vector<MaskTex> table;                                // one entry per masked draw with indices
+    std::vector<uint32_t> slotOfJob;                           // per job (draw with indices), when the call has a masked draw: 1 + its table entry, or 0
     for (int v = 0; v < numViews; ++v) {
-        const vqhip_shadow_view& V = views[v];
+        const VIEW& V = views[v];
         if (!V.depth) return bad(v, -1, "depth is NULL");
         if (V.dim < 1 || V.dim > VQHIP_SHADOW_MAX_DIM) return bad(v, -1, "dim must be 1..8192");
         const size_t pitch = V.pitchBytes ? V.pitchBytes : (size_t)V.dim * 4;
@@ -1839,7 +1900,8 @@ int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_view* vi
         if (V.linearDepth != 0 && V.linearDepth != 1) return bad(v, -1, "linearDepth must be 0 or 1");
         uint64_t viewTris = 0;
         for (int d = 0; d < V.numDraws; ++d) {
-            const vqhip_shadow_draw& D = V.draws[d];
+            const vqhip_shadow_draw& D = baseDraw(V.draws[d]);
+            const vqhip_texture2d* tex = maskTexture(V.draws[d]);
             if (!D.mesh.positions || !D.mesh.indices || !D.matWorldViewProj) return bad(v, d, "positions, indices or matWorldViewProj is NULL");
             if (V.linearDepth && !D.matWorld) return bad(v, d, "matWorld is NULL in a linear-depth view");
             if (D.mesh.indexBits != 16 && D.mesh.indexBits != 32) return bad(v, d, "indexBits must be 16 or 32");
@@ -1849,8 +1911,24 @@ int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_view* vi
             if (D.cullMode != VQHIP_CULL_NONE && D.cullMode != VQHIP_CULL_FRONT && D.cullMode != VQHIP_CULL_BACK) return bad(v, d, "unknown cullMode");
             if ((uintptr_t)D.mesh.positions % 4 || (uintptr_t)D.matWorldViewProj % 4 || (uintptr_t)D.matWorld % 4 || (uintptr_t)D.mesh.indices % (D.mesh.indexBits / 8))
                 return bad(v, d, "positions / matrices must be 4-byte aligned, indices aligned to their size");
-            if (D.mesh.numIndices) { viewTris += (uint64_t)(D.mesh.numIndices / 3) * D.numInstances; ++numJobs; }
+            if (tex) {
+                if (D.mesh.strideBytes < 44) return bad(v, d, "a masked draw needs the engine's vertex (uv at byte 36): strideBytes below 44");
+                if (const char* m = badMaskTexture(*tex)) return bad(v, d, m);
+            }
+            if (D.mesh.numIndices) {
+                viewTris += (uint64_t)(D.mesh.numIndices / 3) * D.numInstances; ++numJobs;
+                if (kMaskedEntry) {
+                    slotOfJob.push_back(tex ? (uint32_t)table.size() + 1u : 0u);
+                    if (tex) {
+                        MaskTex t; std::memset(&t, 0, sizeof(t));
+                        t.texels = tex->texels; t.width = tex->width; t.height = tex->height; t.mips = tex->mips; t.sx = t.sy = 1.0f;
+                        table.push_back(t);
+                        maskedTris += (uint64_t)(D.mesh.numIndices / 3) * D.numInstances;
+                    }
+                }
+            }
         }
+        numDrawsAll += (size_t)V.numDraws;
         RasterView& R = hv[v];
         std::memset(&R, 0, sizeof(R));
         R.depth = V.depth; R.pitch = (uint32_t)(pitch / 4); R.dim = V.dim; R.linear = V.linearDepth;
@@ -1860,13 +1938,20 @@ int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_view* vi
         const uint64_t tiles = (uint64_t)((V.dim + tile - 1) / tile);
         fillBlocks += tiles * tiles;
         totalTris += viewTris;
-        if (viewTris * 6 > 0xffffffffull) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "shadow_depth: a view draws more than 2^32 / 6 instanced triangles");
+        if (viewTris * 6 > 0xffffffffull) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": a view draws more than 2^32 / 6 instanced triangles");
     }
-    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "shadow_depth: more than 20000 draws in one call");
-    if ((totalTris + 255) / 256 + numJobs > 0x7fffffffull) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "shadow_depth: more than 2^31 triangle lanes in one call");
-    size_t offBoxes, offRecords, need;
-    if (!rasterLayout(totalTris, &offBoxes, &offRecords, &need) || workBytes < need)
-        return fail(ctx, VQHIP_ERR_INVALID_ARG, "shadow_depth: workBytes below vqhip_shadow_depth_work_bytes(the call's instanced triangles, numViews)");
+    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": more than 20000 draws in one call");
+    if ((totalTris + 255) / 256 + numJobs > 0x7fffffffull) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": more than 2^31 triangle lanes in one call");
+    size_t offBoxes, offRecords, need, offTable = 0, offSide = 0;
+    bool fits = rasterLayout(totalTris, &offBoxes, &offRecords, &need);
+    if (fits && kMaskedEntry) fits = numDrawsAll <= 0x7fffffffu && maskLayout(need, totalTris, maskedTris, (int)numDrawsAll, &offTable, &offSide, &need);
+    if (!fits || workBytes < need)
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, who + (kMaskedEntry ? ": workBytes below vqhip_shadow_masked_depth_work_bytes(the call's instanced and masked instanced triangles, numViews, the views' draws)"
+                                                                     : ": workBytes below vqhip_shadow_depth_work_bytes(the call's instanced triangles, numViews)"));
+    const bool anyMasked = !table.empty();
+    // the view table's slot is held for the whole call: the table's and the larger jobs' slots must not lap the ring onto it
+    if (anyMasked && numJobs > kRasterMaxMaskedDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": more than 10000 draws in one call that has a masked draw");
+    if (maskedTris >= 0xffffffffull) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": 2^32 - 1 or more masked instanced triangles in one call");      // the record's 32-bit stamp
     for (int v = 0; v < numViews; ++v) {
         const size_t bytes = (size_t)(hv[v].dim - 1) * hv[v].pitch * 4 + (size_t)hv[v].dim * 4;
         if (rangesOverlap(work, need, hv[v].depth, bytes)) return bad(v, -1, "depth overlaps the work buffer");
@@ -1881,36 +1966,76 @@ int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_view* vi
     std::memcpy(ctx->hostRing + (size_t)viewSlot * kConstSlotBytes, hv, sizeof(RasterView) * numViews);
     if (int rc = commitSlot(ctx, viewSlot, sizeof(RasterView) * numViews, st)) return rc;
     const RasterView* dviews = (const RasterView*)(ctx->devRing + (size_t)viewSlot * kConstSlotBytes);
-    hipError_t e = launch_raster_begin(st, counters, numViews);
-    if (e != hipSuccess) return failHip(ctx, e, "shadow_depth counters launch");
-    // the draws, in ring slots of kRasterJobsPerSlot jobs: one setup launch per slot
-    int v = 0, d = 0;
-    size_t left = numJobs;
-    while (left) {
-        int slot;
-        if (int rc = acquireSlot(ctx, &slot)) return rc;
-        RasterJob* jobs = (RasterJob*)(ctx->hostRing + (size_t)slot * kConstSlotBytes);
-        const size_t n = left < kRasterJobsPerSlot ? left : kRasterJobsPerSlot;
-        uint64_t blocks = 0;
-        for (size_t k = 0; k < n;) {
-            if (d >= views[v].numDraws) { ++v; d = 0; continue; }
-            const vqhip_shadow_draw& D = views[v].draws[d++];
-            if (!D.mesh.numIndices) continue;
-            RasterJob& J = jobs[k++];
-            J.positions = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices; J.wvp = D.matWorldViewProj; J.world = D.matWorld;
-            J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numTris = D.mesh.numIndices / 3; J.numInstances = D.numInstances;
-            J.indexBits = D.mesh.indexBits; J.cullMode = D.cullMode; J.view = v; J.firstBlock = (uint32_t)blocks;
-            blocks += ((uint64_t)J.numTris * J.numInstances + 255) / 256;
-        }
-        if (int rc = commitSlot(ctx, slot, sizeof(RasterJob) * n, st)) return rc;
-        e = launch_raster_setup(st, (const RasterJob*)(ctx->devRing + (size_t)slot * kConstSlotBytes), (int)n, (uint32_t)blocks, dviews, counters, boxes, records);
-        if (e != hipSuccess) return failHip(ctx, e, "shadow_depth setup launch");
-        if (int rc = releaseSlot(ctx, slot, st)) return rc;
-        left -= n;
+    MaskArgs ma;
+    std::memset(&ma, 0, sizeof(ma));
+    if (anyMasked) {
+        ma.table = (const MaskTex*)((char*)work + offTable); ma.side = (MaskSide*)((char*)work + offSide); ma.sideCap = maskedTris; ma.tableCap = (uint32_t)table.size();
+        if (int rc = stageMaskTable(ctx, st, table, (MaskTex*)((char*)work + offTable), who.c_str())) return rc;
     }
-    e = launch_raster_fill(st, dviews, numViews, (uint32_t)fillBlocks, tile, counters, boxes, records);
-    if (e != hipSuccess) return failHip(ctx, e, "shadow_depth fill launch");
+    hipError_t e = launch_raster_begin(st, counters, numViews);
+    if (e != hipSuccess) return failHip(ctx, e, (who + " counters launch").c_str());
+    // the draws, in ring slots of kRasterJobsPerSlot jobs (fewer of the larger masked jobs): one setup launch per slot
+    auto setupLaunches = [&](auto jobTag) -> int {
+        using JOB = decltype(jobTag);
+        constexpr bool kMaskedJob = std::is_same<JOB, RasterMaskedJob>::value;
+        constexpr size_t perSlot = kConstSlotBytes / sizeof(JOB);
+        int v = 0, d = 0;
+        size_t left = numJobs, jobNo = 0;
+        uint64_t firstMasked = 0;
+        while (left) {
+            int slot;
+            if (int rc = acquireSlot(ctx, &slot)) return rc;
+            JOB* jobs = (JOB*)(ctx->hostRing + (size_t)slot * kConstSlotBytes);
+            const size_t n = left < perSlot ? left : perSlot;
+            uint64_t blocks = 0;
+            for (size_t k = 0; k < n;) {
+                if (d >= views[v].numDraws) { ++v; d = 0; continue; }
+                const vqhip_shadow_draw& D = baseDraw(views[v].draws[d++]);
+                if (!D.mesh.numIndices) continue;
+                JOB& J = jobs[k++];
+                J.positions = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices; J.wvp = D.matWorldViewProj; J.world = D.matWorld;
+                J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numTris = D.mesh.numIndices / 3; J.numInstances = D.numInstances;
+                J.indexBits = D.mesh.indexBits; J.cullMode = D.cullMode; J.view = v; J.firstBlock = (uint32_t)blocks;
+                blocks += ((uint64_t)J.numTris * J.numInstances + 255) / 256;
+                if constexpr (kMaskedJob) {
+                    J.maskSlot = slotOfJob[jobNo]; J.firstMasked = (uint32_t)firstMasked; J.pad[0] = J.pad[1] = 0u;
+                    if (J.maskSlot) firstMasked += (uint64_t)J.numTris * J.numInstances;
+                }
+                ++jobNo;
+            }
+            if (int rc = commitSlot(ctx, slot, sizeof(JOB) * n, st)) return rc;
+            const JOB* djobs = (const JOB*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
+            if constexpr (kMaskedJob) e = launch_raster_setup_masked(st, djobs, (int)n, (uint32_t)blocks, dviews, counters, boxes, records, ma);
+            else                      e = launch_raster_setup(st, djobs, (int)n, (uint32_t)blocks, dviews, counters, boxes, records);
+            if (e != hipSuccess) return failHip(ctx, e, (who + " setup launch").c_str());
+            if (int rc = releaseSlot(ctx, slot, st)) return rc;
+            left -= n;
+        }
+        return VQHIP_OK;
+    };
+    if (int rc = anyMasked ? setupLaunches(RasterMaskedJob{}) : setupLaunches(RasterJob{})) return rc;
+    e = anyMasked ? launch_raster_fill_masked(st, dviews, numViews, (uint32_t)fillBlocks, tile, counters, boxes, records, ma)
+                  : launch_raster_fill(st, dviews, numViews, (uint32_t)fillBlocks, tile, counters, boxes, records);
+    if (e != hipSuccess) return failHip(ctx, e, (who + " fill launch").c_str());
     return releaseSlot(ctx, viewSlot, st);
+}
+} // extern "C++"
+
+int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_view* views, int numViews, void* work, size_t workBytes) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "shadow_depth: ctx is NULL");
+    CTX_GUARD(ctx, "shadow_depth");
+    return shadowDepthCall(ctx, stream, views, numViews, work, workBytes, "shadow_depth");
+}
+
+size_t vqhip_shadow_masked_depth_work_bytes(uint64_t instancedTriangles, uint64_t maskedInstancedTriangles, int numViews, int numDraws) {
+    size_t tb, sd, t;
+    return maskLayout(vqhip_shadow_depth_work_bytes(instancedTriangles, numViews), instancedTriangles, maskedInstancedTriangles, numDraws, &tb, &sd, &t) ? t : 0;
+}
+
+int vqhip_shadow_masked_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_masked_view* views, int numViews, void* work, size_t workBytes) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "shadow_masked_depth: ctx is NULL");
+    CTX_GUARD(ctx, "shadow_masked_depth");
+    return shadowDepthCall(ctx, stream, views, numViews, work, workBytes, "shadow_masked_depth");
 }
 
 // ---- Main-view depth pre-pass (raster_view.hip; docs/DESIGN_DETAILS.md §7.17) ------------------------------------------------------------------------------------
@@ -1934,12 +2059,15 @@ size_t vqhip_scene_depth_work_bytes(uint64_t instancedTriangles) {
     return sceneDepthLayout(instancedTriangles, &b, &r, &t) ? t : 0;
 }
 
-int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_depth_draw* draws, int numDraws, int width, int height, int samples,
-                      const vqhip_scene_depth_targets* out, void* work, size_t workBytes) {
+// vqhip_scene_depth (DRAW = vqhip_scene_depth_draw) and vqhip_scene_masked_depth (DRAW = vqhip_scene_masked_depth_draw): one body, entered with the context guard held; `who` names the entry
+// point in messages. A call without a masked draw enqueues exactly what vqhip_scene_depth enqueues.
+extern "C++" {
+template <class DRAW>
+int sceneDepthCall(vqhip_ctx* ctx, void* stream, const DRAW* draws, int numDraws, int width, int height, int samples,
+                   const vqhip_scene_depth_targets* out, void* work, size_t workBytes, const std::string& who) {
+    constexpr bool kMaskedEntry = !std::is_same<DRAW, vqhip_scene_depth_draw>::value;
     vqk::Range range_("RenderDepthPrePass");
-    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "scene_depth: ctx is NULL");
-    CTX_GUARD(ctx, "scene_depth");
-    auto bad = [&](const std::string& m) { return fail(ctx, VQHIP_ERR_INVALID_ARG, "scene_depth: " + m); };
+    auto bad = [&](const std::string& m) { return fail(ctx, VQHIP_ERR_INVALID_ARG, who + ": " + m); };
     if (!out || !out->depth || !work) return bad("NULL argument (out, out->depth or work)");
     if (numDraws < 0 || (numDraws > 0 && !draws)) return bad("numDraws < 0, or draws is NULL");
     if (samples != 1 && samples != 4) return bad("samples must be 1 or 4");
@@ -1954,10 +2082,13 @@ int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_depth_draw
     if ((uintptr_t)out->depth % px || (uintptr_t)out->primitive % px) return bad("depth / primitive must be 4-byte (samples 1) or 16-byte (samples 4) aligned");
     if ((uintptr_t)work % 256) return bad("work must be 256-byte aligned");
     for (int k = 0; k < out->layers; ++k) if ((uintptr_t)out->layerPrimitive[k] % 4) return bad("layerPrimitive must be 4-byte aligned");
-    uint64_t totalTris = 0;
+    uint64_t totalTris = 0, maskedTris = 0, sideTris = 0;      // maskedTris: the header's rule (sizes the work buffer); sideTris: those that can discard
     size_t numJobs = 0;
+    std::vector<MaskTex> table;                                // one entry per draw that can discard
+    std::vector<uint32_t> slotOfJob;                           // per job (draw with indices), in a masked call: 1 + its table entry, or 0
     for (int d = 0; d < numDraws; ++d) {
-        const vqhip_scene_depth_draw& D = draws[d];
+        const vqhip_scene_depth_draw& D = baseDraw(draws[d]);
+        const vqhip_material* mat = maskMaterial(draws[d]);
         auto badDraw = [&](const char* m) { return bad("draw " + std::to_string(d) + ": " + m); };
         if (!D.mesh.positions || !D.mesh.indices || !D.matWorldViewProj) return badDraw("positions, indices or matWorldViewProj is NULL");
         if (D.mesh.indexBits != 16 && D.mesh.indexBits != 32) return badDraw("indexBits must be 16 or 32");
@@ -1967,13 +2098,37 @@ int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_depth_draw
         if (D.cullMode != VQHIP_CULL_NONE && D.cullMode != VQHIP_CULL_FRONT && D.cullMode != VQHIP_CULL_BACK) return badDraw("unknown cullMode");
         if ((uintptr_t)D.mesh.positions % 4 || (uintptr_t)D.matWorldViewProj % 4 || (uintptr_t)D.mesh.indices % (D.mesh.indexBits / 8))
             return badDraw("positions / matrices must be 4-byte aligned, indices aligned to their size");
-        if (D.mesh.numIndices) { totalTris += (uint64_t)(D.mesh.numIndices / 3) * D.numInstances; ++numJobs; }
+        if (mat) {
+            if (D.mesh.strideBytes < 44) return badDraw("a masked draw needs the engine's vertex (uv at byte 36): strideBytes below 44");
+            if (const char* m = badMaskTexture(mat->texDiffuse)) return badDraw(m);
+        }
+        if (D.mesh.numIndices) {
+            const uint64_t tris = (uint64_t)(D.mesh.numIndices / 3) * D.numInstances;
+            totalTris += tris; ++numJobs;
+            if (kMaskedEntry) {
+                // DepthPrePass.hlsl:159: discard iff HasDiffuseMap(textureConfig) && a < 0.01f — without the bit the masked PSO discards nothing: drawn as opaque
+                const bool discards = mat && (hostTrunc(mat->data.textureConfig) & 1) > 0;
+                slotOfJob.push_back(discards ? (uint32_t)table.size() + 1u : 0u);
+                if (mat) maskedTris += tris;
+                if (discards) {
+                    MaskTex t; std::memset(&t, 0, sizeof(t));
+                    t.texels = mat->texDiffuse.texels; t.width = mat->texDiffuse.width; t.height = mat->texDiffuse.height; t.mips = mat->texDiffuse.mips;
+                    t.sx = mat->data.uvScaleOffset.x; t.sy = mat->data.uvScaleOffset.y; t.ox = mat->data.uvScaleOffset.z; t.oy = mat->data.uvScaleOffset.w;
+                    table.push_back(t);
+                    sideTris += tris;
+                }
+            }
+        }
     }
-    if (totalTris >= kSceneMaxTriangles) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "scene_depth: 2^29 or more instanced triangles in one call");
-    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "scene_depth: more than 20000 draws in one call");
-    size_t offBoxes, offRecords, need;
-    if (!sceneDepthLayout(totalTris, &offBoxes, &offRecords, &need) || workBytes < need)
-        return bad("workBytes below vqhip_scene_depth_work_bytes(the call's instanced triangles)");
+    if (totalTris >= kSceneMaxTriangles) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": 2^29 or more instanced triangles in one call");
+    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": more than 20000 draws in one call");
+    size_t offBoxes, offRecords, need, offTable = 0, offSide = 0;
+    bool fits = sceneDepthLayout(totalTris, &offBoxes, &offRecords, &need);
+    if (fits && kMaskedEntry) fits = maskLayout(need, totalTris, maskedTris, numDraws, &offTable, &offSide, &need);
+    if (!fits || workBytes < need)
+        return bad(kMaskedEntry ? "workBytes below vqhip_scene_masked_depth_work_bytes(the call's instanced and masked instanced triangles, numDraws)"
+                                : "workBytes below vqhip_scene_depth_work_bytes(the call's instanced triangles)");
+    const bool anyMasked = !table.empty();
     const size_t rows = (size_t)(height - 1);
     bool overlap = rangesOverlap(work, need, out->depth, (rows * pitch + width) * px) ||
                    (out->primitive && rangesOverlap(work, need, out->primitive, (rows * pitch + width) * px));
@@ -1993,12 +2148,19 @@ int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_depth_draw
     uint32_t* counter = (uint32_t*)work;
     void* boxes = (char*)work + offBoxes;
     void* records = (char*)work + offRecords;
+    MaskArgs ma;
+    std::memset(&ma, 0, sizeof(ma));
+    if (anyMasked) {
+        ma.table = (const MaskTex*)((char*)work + offTable); ma.side = (MaskSide*)((char*)work + offSide); ma.sideCap = sideTris; ma.tableCap = (uint32_t)table.size();
+        if (int rc = stageMaskTable(ctx, st, table, (MaskTex*)((char*)work + offTable), who.c_str())) return rc;
+    }
     hipError_t e = launch_raster_begin(st, counter, 1);
-    if (e != hipSuccess) return failHip(ctx, e, "scene_depth counter launch");
+    if (e != hipSuccess) return failHip(ctx, e, (who + " counter launch").c_str());
     // the draws, in ring slots of kSceneJobsPerSlot jobs: one setup launch per slot
     int d = 0;
     size_t left = numJobs;
-    uint64_t firstQ = 0;
+    uint64_t firstQ = 0, firstMasked = 0;
+    size_t jobNo = 0;
     while (left) {
         int slot;
         if (int rc = acquireSlot(ctx, &slot)) return rc;
@@ -2006,7 +2168,7 @@ int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_depth_draw
         const size_t n = left < kSceneJobsPerSlot ? left : kSceneJobsPerSlot;
         uint64_t blocks = 0;
         for (size_t k = 0; k < n;) {
-            const vqhip_scene_depth_draw& D = draws[d++];
+            const vqhip_scene_depth_draw& D = baseDraw(draws[d++]);
             if (!D.mesh.numIndices) continue;
             SceneDepthJob& J = jobs[k++];
             J.positions = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices; J.wvp = D.matWorldViewProj;
@@ -2014,15 +2176,41 @@ int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_depth_draw
             J.indexBits = D.mesh.indexBits; J.cullMode = D.cullMode; J.firstBlock = (uint32_t)blocks; J.firstQ = (uint32_t)firstQ;
             blocks += ((uint64_t)J.numTris * J.numInstances + 255) / 256;
             firstQ += (uint64_t)J.numTris * J.numInstances;
+            J.maskSlot = anyMasked ? slotOfJob[jobNo] : 0u; J.firstMasked = (uint32_t)firstMasked;
+            if (J.maskSlot) firstMasked += (uint64_t)J.numTris * J.numInstances;
+            ++jobNo;
         }
         if (int rc = commitSlot(ctx, slot, sizeof(SceneDepthJob) * n, st)) return rc;
-        e = launch_scene_setup(st, (const SceneDepthJob*)(ctx->devRing + (size_t)slot * kConstSlotBytes), (int)n, (uint32_t)blocks, a, counter, boxes, records);
-        if (e != hipSuccess) return failHip(ctx, e, "scene_depth setup launch");
+        const SceneDepthJob* djobs = (const SceneDepthJob*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
+        e = anyMasked ? launch_scene_setup_masked(st, djobs, (int)n, (uint32_t)blocks, a, counter, boxes, records, ma)
+                      : launch_scene_setup(st, djobs, (int)n, (uint32_t)blocks, a, counter, boxes, records);
+        if (e != hipSuccess) return failHip(ctx, e, (who + " setup launch").c_str());
         if (int rc = releaseSlot(ctx, slot, st)) return rc;
         left -= n;
     }
-    e = launch_scene_fill(st, a, scene_depth_tile(ctx->opt.rasterTile, samples), counter, boxes, records);
-    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "scene_depth fill launch");
+    e = anyMasked ? launch_scene_fill_masked(st, a, scene_depth_tile(ctx->opt.rasterTile, samples), counter, boxes, records, ma)
+                  : launch_scene_fill(st, a, scene_depth_tile(ctx->opt.rasterTile, samples), counter, boxes, records);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (who + " fill launch").c_str());
+}
+} // extern "C++"
+
+int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_depth_draw* draws, int numDraws, int width, int height, int samples,
+                      const vqhip_scene_depth_targets* out, void* work, size_t workBytes) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "scene_depth: ctx is NULL");
+    CTX_GUARD(ctx, "scene_depth");
+    return sceneDepthCall(ctx, stream, draws, numDraws, width, height, samples, out, work, workBytes, "scene_depth");
+}
+
+size_t vqhip_scene_masked_depth_work_bytes(uint64_t instancedTriangles, uint64_t maskedInstancedTriangles, int numDraws) {
+    size_t tb, sd, t;
+    return maskLayout(vqhip_scene_depth_work_bytes(instancedTriangles), instancedTriangles, maskedInstancedTriangles, numDraws, &tb, &sd, &t) ? t : 0;
+}
+
+int vqhip_scene_masked_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_masked_depth_draw* draws, int numDraws, int width, int height, int samples,
+                             const vqhip_scene_depth_targets* out, void* work, size_t workBytes) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "scene_masked_depth: ctx is NULL");
+    CTX_GUARD(ctx, "scene_masked_depth");
+    return sceneDepthCall(ctx, stream, draws, numDraws, width, height, samples, out, work, workBytes, "scene_masked_depth");
 }
 
 // ---- The lit draw's interpolants from meshes (raster_attr.hip; docs/DESIGN_DETAILS.md §7.18) ----------------------------------------------------------------------

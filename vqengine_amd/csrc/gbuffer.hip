@@ -26,6 +26,7 @@
 // Arithmetic/sampling contract: DESIGN.md "G-buffer producer".
 #include "vq_shade.h"          // vq_internal.h, vq_devmath.h, vq_sampling.h + the lighting body of the fused kernel
 #include "vq_mrt.h"
+#include "vq_tex8.h"         // LevelTaps, Footprint, level_taps, make_footprint, dec8, load_taps, blend_taps: the lane-local pieces of the fetch below
 
 #include <cstdlib>
 #ifndef VQ_PSMAIN_WAVES_DEFAULT
@@ -34,74 +35,6 @@
 #endif
 namespace vqk {
 using namespace vqd;
-
-struct __attribute__((packed, aligned(4))) TexelPair { uint32_t a, b; };
-
-// One level of a footprint: texel offsets (from the chain base) of the two rows, the two columns, the 4 weights.
-struct LevelTaps { uint32_t row0, row1; int x0, x1; float w00, w10, w01, w11; };
-struct Footprint { LevelTaps l0, l1; float f; };
-
-
-template <bool POT> VQD LevelTaps level_taps(int w0, int h0, int level, float u, float v) {
-    const int W = mip_dim(w0, level), H = mip_dim(h0, level);
-    int ix, iy; float wx, wy;
-    fixed8(u * (float)W - 0.5f, &ix, &wx);
-    fixed8(v * (float)H - 0.5f, &iy, &wy);
-    LevelTaps t;
-    int y0, y1;
-    if (POT) { t.x0 = ix & (W - 1); t.x1 = (ix + 1) & (W - 1); y0 = iy & (H - 1); y1 = (iy + 1) & (H - 1); }
-    else     { t.x0 = wrapi(ix, W); t.x1 = wrapi(ix + 1, W); y0 = wrapi(iy, H); y1 = wrapi(iy + 1, H); }
-    const uint32_t base = chain_level_offset<POT>(w0, h0, level);    // vq_sampling.h: closed form for power-of-two chains
-    t.row0 = base + __umul24(y0, W);                              // dims < 2^24: full-rate v_mad_u32_u24
-    t.row1 = base + __umul24(y1, W);
-    t.w00 = (1.0f - wx) * (1.0f - wy); t.w10 = wx * (1.0f - wy); t.w01 = (1.0f - wx) * wy; t.w11 = wx * wy;   // == blend4's weights
-    return t;
-}
-
-// Texture2D.Sample / SampleBias: isotropic trilinear WRAP, LOD from the quad derivatives
-template <bool POT> VQD Footprint make_footprint(int w, int h, int mips, float2 uv, float2 ddx, float2 ddy, float bias) {
-    const float W = (float)w, H = (float)h;
-    const float dXx = ddx.x * W, dXy = ddx.y * H, dYx = ddy.x * W, dYy = ddy.y * H;
-    const float rx = fma_(dXy, dXy, dXx * dXx), ry = fma_(dYy, dYy, dYx * dYx);
-    const float lod = 0.5f * log2_(max_(rx, ry)) + bias;
-    const float maxl = (float)(mips - 1);
-    const float l = (lod > 0.0f) ? ((lod < maxl) ? lod : maxl) : 0.0f;
-    const int fl = f2i_floor(l * 256.0f + 0.5f);
-    int lo = fl >> 8;
-    Footprint fp;
-    fp.f = (float)(fl & 255) * 0.00390625f;
-    if (lo >= mips - 1) { lo = mips - 1; fp.f = 0.0f; }
-    fp.l0 = level_taps<POT>(w, h, lo, uv.x, uv.y);
-    fp.l1 = level_taps<POT>(w, h, min(lo + 1, mips - 1), uv.x, uv.y);     // unused (weight 0) when f == 0
-    return fp;
-}
-
-VQD float4 dec8(uint32_t q) { return make_float4((float)(q & 255u), (float)((q >> 8) & 255u), (float)((q >> 16) & 255u), (float)(q >> 24)); }
-
-// bilinear blend of one level in byte units (exact: 8-bit weights x 8-bit texels fit binary32); same FMA chain as blend4
-struct Taps4 { uint32_t a, b, c, d; };
-template <bool PAIRS> VQD Taps4 load_taps(const uint32_t* __restrict__ t, const LevelTaps& k) {
-    Taps4 q;
-    // 32-bit byte offsets from the wave-uniform chain pointer (a chain is < 4 GB): global_load with SGPR base + VGPR offset
-    const char* b = (const char*)t;
-    if (PAIRS) {                                                     // x1 == x0 + 1 in every lane: two 8-byte loads
-        const TexelPair p0 = *(const TexelPair*)(b + ((k.row0 + (uint32_t)k.x0) << 2)), p1 = *(const TexelPair*)(b + ((k.row1 + (uint32_t)k.x0) << 2));
-        q.a = p0.a; q.b = p0.b; q.c = p1.a; q.d = p1.b;
-    } else {
-        q.a = *(const uint32_t*)(b + ((k.row0 + (uint32_t)k.x0) << 2)); q.b = *(const uint32_t*)(b + ((k.row0 + (uint32_t)k.x1) << 2));
-        q.c = *(const uint32_t*)(b + ((k.row1 + (uint32_t)k.x0) << 2)); q.d = *(const uint32_t*)(b + ((k.row1 + (uint32_t)k.x1) << 2));
-    }
-    return q;
-}
-VQD float4 blend_taps(const Taps4& q, const LevelTaps& k) {
-    const float4 c00 = dec8(q.a), c10 = dec8(q.b), c01 = dec8(q.c), c11 = dec8(q.d);
-    float4 r;
-    r.x = fma_(k.w11, c11.x, fma_(k.w01, c01.x, fma_(k.w10, c10.x, k.w00 * c00.x)));
-    r.y = fma_(k.w11, c11.y, fma_(k.w01, c01.y, fma_(k.w10, c10.y, k.w00 * c00.y)));
-    r.z = fma_(k.w11, c11.z, fma_(k.w01, c01.z, fma_(k.w10, c10.z, k.w00 * c00.z)));
-    r.w = fma_(k.w11, c11.w, fma_(k.w01, c01.w, fma_(k.w10, c10.w, k.w00 * c00.w)));     // alpha: read by the ENABLE_ALPHA_MASK discard test (:237-240)
-    return r;
-}
 
 VQD float4 fetch(const void* texels, const Footprint& fp) {
     const uint32_t* t = (const uint32_t*)texels;

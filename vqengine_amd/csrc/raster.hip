@@ -7,8 +7,11 @@
 //                    records that touch the tile, and each wave rasterises queued records with LDS atomicMin on the bits (every value is >= +0, so unsigned
 //                    order is float order); then one coalesced store of the tile. No global atomics on the maps, no clear pass.
 // Every loop bound is dim, a record count clamped to the region's capacity, or a constant: nothing a vertex value can stretch.
+// vqhip_shadow_masked_depth (§7.19; tests/masked_depth_ref.py) launches the <.., MaskArgs> instantiations of both kernels when a draw of the call is alpha-tested: the
+// same two bodies with the "_AlphaMasked" pixel shader's discard (ShadowDepthPass.hlsl:136-140) in front of the minimum; vq_raster_mask.h holds the test.
 #include "vq_internal.h"
 #include "vq_devmath.h"
+#include "vq_raster_mask.h"
 
 namespace vqk {
 using namespace vqd;
@@ -54,13 +57,18 @@ __global__ void __launch_bounds__(64) k_raster_begin(uint32_t* counters, int num
     if ((int)threadIdx.x < numViews) counters[threadIdx.x] = 0u;
 }
 
-__global__ void __launch_bounds__(kSetupLanes) k_raster_setup(const RasterJob* __restrict__ jobs, int numJobs, const RasterView* __restrict__ views,
-                                                              uint32_t* __restrict__ counters, uint2* __restrict__ boxes, uint4* __restrict__ records) {
+// JOB = RasterMaskedJob (§7.19): a draw with a maskSlot also writes its triangle's side record (the unclipped clip-space x, y, w and the uv of the three vertices,
+// the slot) and stamps its records with 1 + the side record's index; with JOB = RasterJob this is the code it was.
+// The mask arguments are a parameter pack so that the opaque instantiation keeps the parameter list (and the code) it had: MA = {} or {MaskArgs}.
+template <class JOB, class... MA>
+__global__ void __launch_bounds__(kSetupLanes) k_raster_setup(const JOB* __restrict__ jobs, int numJobs, const RasterView* __restrict__ views,
+                                                              uint32_t* __restrict__ counters, uint2* __restrict__ boxes, uint4* __restrict__ records, MA... mask) {
+    constexpr bool MASKED = sizeof...(MA) != 0;
     __shared__ uint32_t sCount, sBase;
     // the block's job: the last one whose firstBlock is <= blockIdx.x (block-uniform binary search; numJobs bounds it)
     int lo = 0, hi = numJobs - 1;
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].firstBlock <= blockIdx.x) lo = mid; else hi = mid - 1; }
-    const RasterJob job = jobs[lo];
+    const JOB job = jobs[lo];
     const RasterView view = views[job.view];
     if (threadIdx.x == 0) sCount = 0u;
     __syncthreads();
@@ -73,6 +81,10 @@ __global__ void __launch_bounds__(kSetupLanes) k_raster_setup(const RasterJob* _
     RVert poly[kMaxPoly];
     int n = 0;
     uint32_t emitMask = 0;                       // bit k: fan triangle (0, k + 1, k + 2) is emitted
+    uint32_t maskSlot = 0u, firstMasked = 0u;
+    if constexpr (MASKED) { maskSlot = job.maskSlot; firstMasked = job.firstMasked; }
+    const bool masked = maskSlot != 0u;
+    float mc[9], muv[6];                         // MASKED: the side record's fifteen floats
     if (live) {
         const uint32_t inst = (uint32_t)(t / job.numTris), tri = (uint32_t)(t % job.numTris);
         uint32_t idx[3];
@@ -97,6 +109,7 @@ __global__ void __launch_bounds__(kSetupLanes) k_raster_setup(const RasterJob* _
                 }
                 ok = ok && finite_(c[0]) && finite_(c[1]) && finite_(c[2]) && finite_(c[3]);
                 poly[k] = v;
+                if (masked) { mc[3 * k] = c[0]; mc[3 * k + 1] = c[1]; mc[3 * k + 2] = c[3]; muv[2 * k] = p[9]; muv[2 * k + 1] = p[10]; }    // uv at byte 36 (stride >= 44: the host checks)
             }
         }
         if (ok) {
@@ -155,6 +168,19 @@ __global__ void __launch_bounds__(kSetupLanes) k_raster_setup(const RasterJob* _
     if (threadIdx.x == 0) sBase = sCount ? atomicAdd(&counters[job.view], sCount) : 0u;
     __syncthreads();
     if (!mine) return;
+    uint32_t mk = 0u;
+    if constexpr (MASKED) if (masked) {
+        const MaskArgs& m = maskArgsOf(mask...);
+        const uint64_t at = (uint64_t)firstMasked + t;              // below the call's masked instanced triangles = sideCap
+        if (at < m.sideCap) {
+            uint4* sr = (uint4*)(m.side + at);
+            sr[0] = make_uint4(__float_as_uint(mc[0]), __float_as_uint(mc[1]), __float_as_uint(mc[2]), __float_as_uint(mc[3]));
+            sr[1] = make_uint4(__float_as_uint(mc[4]), __float_as_uint(mc[5]), __float_as_uint(mc[6]), __float_as_uint(mc[7]));
+            sr[2] = make_uint4(__float_as_uint(mc[8]), __float_as_uint(muv[0]), __float_as_uint(muv[1]), __float_as_uint(muv[2]));
+            sr[3] = make_uint4(__float_as_uint(muv[3]), __float_as_uint(muv[4]), __float_as_uint(muv[5]), maskSlot - 1u);
+            mk = (uint32_t)at + 1u;
+        }
+    }
     uint64_t slot = (uint64_t)sBase + place;
     for (int k = 0; k + 2 < kMaxPoly; ++k) {
         if (!(emitMask >> k & 1u)) continue;
@@ -171,14 +197,16 @@ __global__ void __launch_bounds__(kSetupLanes) k_raster_setup(const RasterJob* _
         r[1] = make_uint4((uint32_t)sx[c], (uint32_t)sy[c], __float_as_uint(dz[a]), __float_as_uint(dz[b]));
         r[2] = make_uint4(__float_as_uint(dz[c]), __float_as_uint(poly[a].wx), __float_as_uint(poly[a].wy), __float_as_uint(poly[a].wz));
         r[3] = make_uint4(__float_as_uint(poly[b].wx), __float_as_uint(poly[b].wy), __float_as_uint(poly[b].wz), __float_as_uint(poly[c].wx));
-        r[4] = make_uint4(__float_as_uint(poly[c].wy), __float_as_uint(poly[c].wz), 0u, 0u);
+        r[4] = make_uint4(__float_as_uint(poly[c].wy), __float_as_uint(poly[c].wz), mk, 0u);
         ++slot;
     }
 }
 
-template <int T>
+// MASKED (§7.19): a covered texel of a stamped record runs the alpha test of ShadowDepthPass.hlsl:136-140 (pixel = texel) before its depth is computed
+template <int T, class... MA>
 __global__ void __launch_bounds__(kFillLanes) k_raster_fill(const RasterView* __restrict__ views, int numViews, const uint32_t* __restrict__ counters,
-                                                            const uint2* __restrict__ boxes, const uint4* __restrict__ records) {
+                                                            const uint2* __restrict__ boxes, const uint4* __restrict__ records, MA... mask) {
+    constexpr bool MASKED = sizeof...(MA) != 0;
     __shared__ uint32_t tile[T * T];
     __shared__ uint32_t queue[kFillLanes];
     __shared__ uint32_t qn;
@@ -217,6 +245,9 @@ __global__ void __launch_bounds__(kFillLanes) k_raster_fill(const RasterView* __
             const uint4 r2 = vr[(size_t)rec * 5 + 2];
             const float d2 = __uint_as_float(r2.x);
             float P0x = 0, P0y = 0, P0z = 0, P1x = 0, P1y = 0, P1z = 0, P2x = 0, P2y = 0, P2z = 0;
+            MaskTri mt;
+            bool alphaTest = false;
+            if constexpr (MASKED) alphaTest = loadMaskTri(maskArgsOf(mask...), vr[(size_t)rec * 5 + 4].z, mt);
             if (lin) {
                 const uint4 r3 = vr[(size_t)rec * 5 + 3], r4 = vr[(size_t)rec * 5 + 4];
                 P0x = __uint_as_float(r2.y); P0y = __uint_as_float(r2.z); P0z = __uint_as_float(r2.w);
@@ -238,6 +269,7 @@ __global__ void __launch_bounds__(kFillLanes) k_raster_fill(const RasterView* __
                 const int64_t E0 = edgeFn(x1, y1, x2, y2, px, py), E1 = edgeFn(x2, y2, x0, y0, px, py), E2 = edgeFn(x0, y0, x1, y1, px, py);
                 const int64_t s0 = sgn * E0, s1 = sgn * E1, s2 = sgn * E2;
                 if (!((s0 > 0 || (s0 == 0 && tl0)) && (s1 > 0 || (s1 == 0 && tl1)) && (s2 > 0 || (s2 == 0 && tl2)))) continue;
+                if constexpr (MASKED) { if (alphaTest && maskDiscardShadow(mt, i, j, view.dim)) continue; }         // LINEAR_DEPTH is computed after the discard
                 const float b1 = fdiv_((float)E1, fA), b2 = fdiv_((float)E2, fA);
                 float d;
                 if (!lin) {
@@ -273,12 +305,24 @@ hipError_t launch_raster_begin(hipStream_t s, uint32_t* counters, int numViews) 
     return hipGetLastError();
 }
 hipError_t launch_raster_setup(hipStream_t s, const RasterJob* jobs, int numJobs, uint32_t blocks, const RasterView* views, uint32_t* counters, void* boxes, void* records) {
-    hipLaunchKernelGGL(k_raster_setup, dim3(blocks), dim3(kSetupLanes), 0, s, jobs, numJobs, views, counters, (uint2*)boxes, (uint4*)records);
+    hipLaunchKernelGGL(k_raster_setup<RasterJob>, dim3(blocks), dim3(kSetupLanes), 0, s, jobs, numJobs, views, counters, (uint2*)boxes, (uint4*)records);
     return hipGetLastError();
 }
 hipError_t launch_raster_fill(hipStream_t s, const RasterView* views, int numViews, uint32_t blocks, int tile, const uint32_t* counters, const void* boxes, const void* records) {
     if (tile == 64) hipLaunchKernelGGL(k_raster_fill<64>, dim3(blocks), dim3(kFillLanes), 0, s, views, numViews, counters, (const uint2*)boxes, (const uint4*)records);
     else            hipLaunchKernelGGL(k_raster_fill<32>, dim3(blocks), dim3(kFillLanes), 0, s, views, numViews, counters, (const uint2*)boxes, (const uint4*)records);
+    return hipGetLastError();
+}
+
+hipError_t launch_raster_setup_masked(hipStream_t s, const RasterMaskedJob* jobs, int numJobs, uint32_t blocks, const RasterView* views, uint32_t* counters, void* boxes, void* records,
+                                      const MaskArgs& m) {
+    hipLaunchKernelGGL((k_raster_setup<RasterMaskedJob, MaskArgs>), dim3(blocks), dim3(kSetupLanes), 0, s, jobs, numJobs, views, counters, (uint2*)boxes, (uint4*)records, m);
+    return hipGetLastError();
+}
+hipError_t launch_raster_fill_masked(hipStream_t s, const RasterView* views, int numViews, uint32_t blocks, int tile, const uint32_t* counters, const void* boxes, const void* records,
+                                     const MaskArgs& m) {
+    if (tile == 64) hipLaunchKernelGGL((k_raster_fill<64, MaskArgs>), dim3(blocks), dim3(kFillLanes), 0, s, views, numViews, counters, (const uint2*)boxes, (const uint4*)records, m);
+    else            hipLaunchKernelGGL((k_raster_fill<32, MaskArgs>), dim3(blocks), dim3(kFillLanes), 0, s, views, numViews, counters, (const uint2*)boxes, (const uint4*)records, m);
     return hipGetLastError();
 }
 

@@ -9,8 +9,11 @@
 //                   (ds_min_u64: a minimum, so the result does not depend on the order of arrival). Then the tile is stored once: depth, primitive, and — from
 //                   the pixel's own four keys — the layer masks and the layers' primitives. No global atomics on the outputs, no clear pass.
 // Every loop bound is a viewport size, a record count clamped to capacity, or a constant: nothing a vertex value can stretch.
+// vqhip_scene_masked_depth (§7.19; tests/masked_depth_ref.py) launches the <MaskArgs> instantiations of both kernels when a draw of the call is alpha-tested: the same
+// two bodies with the "_AlphaMasked" pixel shader's discard (DepthPrePass.hlsl:155-161) in front of the minimum; vq_raster_mask.h holds the test.
 #include "vq_internal.h"
 #include "vq_devmath.h"
+#include "vq_raster_mask.h"
 
 namespace vqk {
 using namespace vqd;
@@ -57,8 +60,13 @@ template <int S> VQD int sampleY(int s) { return S == 1 ? 128 : 32 + 64 * s; }
 VQD int pixelFirst(int lo, int samples) { return (lo - (samples == 1 ? 128 : 224) + 255) >> 8; }
 VQD int pixelLast(int hi, int samples)  { return (hi - (samples == 1 ? 128 : 32)) >> 8; }
 
+// MASKED (§7.19): a draw with a maskSlot also writes its triangle's side record (the unclipped clip-space x, y, w and the uv of the three vertices, the slot) and
+// stamps its records with 1 + the side record's index; the opaque instantiation is the code it was.
+// The mask arguments are a parameter pack so that the opaque instantiation keeps the parameter list (and the code) it had: MA = {} or {MaskArgs}.
+template <class... MA>
 __global__ void __launch_bounds__(kSetupLanes) k_scene_setup(const SceneDepthJob* __restrict__ jobs, int numJobs, SceneDepthArgs a, uint32_t* __restrict__ counter,
-                                                             uint2* __restrict__ boxes, uint4* __restrict__ records) {
+                                                             uint2* __restrict__ boxes, uint4* __restrict__ records, MA... mask) {
+    constexpr bool MASKED = sizeof...(MA) != 0;
     __shared__ uint32_t sCount, sBase;
     // the block's job: the last one whose firstBlock is <= blockIdx.x (block-uniform binary search; numJobs bounds it)
     int lo = 0, hi = numJobs - 1;
@@ -73,6 +81,8 @@ __global__ void __launch_bounds__(kSetupLanes) k_scene_setup(const SceneDepthJob
     float dz[kMaxPoly];                          // z / w
     int n = 0;
     uint32_t emitMask = 0;                       // bit k: fan triangle (0, k + 1, k + 2) is emitted
+    const bool masked = MASKED && job.maskSlot != 0u;
+    float mc[9], muv[6];                         // MASKED: the side record's fifteen floats
     if (live) {
         const uint32_t inst = (uint32_t)(t / job.numTris), tri = (uint32_t)(t % job.numTris);
         uint32_t idx[3];
@@ -91,6 +101,7 @@ __global__ void __launch_bounds__(kSetupLanes) k_scene_setup(const SceneDepthJob
                 for (int j = 0; j < 4; ++j) c[j] = ((x * M.m[0][j] + y * M.m[1][j]) + z * M.m[2][j]) + 1.0f * M.m[3][j];
                 ok = ok && finite_(c[0]) && finite_(c[1]) && finite_(c[2]) && finite_(c[3]);
                 poly[k] = CVert{ c[0], c[1], c[2], c[3] };
+                if (masked) { mc[3 * k] = c[0]; mc[3 * k + 1] = c[1]; mc[3 * k + 2] = c[3]; muv[2 * k] = p[9]; muv[2 * k + 1] = p[10]; }    // uv at byte 36 (stride >= 44: the host checks)
             }
         }
         if (ok) {
@@ -150,6 +161,19 @@ __global__ void __launch_bounds__(kSetupLanes) k_scene_setup(const SceneDepthJob
     __syncthreads();
     if (!mine) return;
     const uint32_t q = job.firstQ + (uint32_t)t;                    // first(draw) + instance * numTris + tri; below 2^32 - 1 (the host refuses more)
+    uint32_t mk = 0u;
+    if constexpr (MASKED) if (masked) {
+        const MaskArgs& m = maskArgsOf(mask...);
+        const uint64_t at = (uint64_t)job.firstMasked + t;          // below the call's masked instanced triangles = sideCap
+        if (at < m.sideCap) {
+            uint4* sr = (uint4*)(m.side + at);
+            sr[0] = make_uint4(__float_as_uint(mc[0]), __float_as_uint(mc[1]), __float_as_uint(mc[2]), __float_as_uint(mc[3]));
+            sr[1] = make_uint4(__float_as_uint(mc[4]), __float_as_uint(mc[5]), __float_as_uint(mc[6]), __float_as_uint(mc[7]));
+            sr[2] = make_uint4(__float_as_uint(mc[8]), __float_as_uint(muv[0]), __float_as_uint(muv[1]), __float_as_uint(muv[2]));
+            sr[3] = make_uint4(__float_as_uint(muv[3]), __float_as_uint(muv[4]), __float_as_uint(muv[5]), job.maskSlot - 1u);
+            mk = (uint32_t)at + 1u;
+        }
+    }
     uint64_t slot = (uint64_t)sBase + place;
     for (int k = 0; k + 2 < kMaxPoly; ++k) {
         if (!(emitMask >> k & 1u)) continue;
@@ -163,14 +187,17 @@ __global__ void __launch_bounds__(kSetupLanes) k_scene_setup(const SceneDepthJob
         uint4* r = records + slot * 3;
         r[0] = make_uint4((uint32_t)sx[va], (uint32_t)sy[va], (uint32_t)sx[vb], (uint32_t)sy[vb]);
         r[1] = make_uint4((uint32_t)sx[vc], (uint32_t)sy[vc], __float_as_uint(dz[va]), __float_as_uint(dz[vb]));
-        r[2] = make_uint4(__float_as_uint(dz[vc]), q, 0u, 0u);
+        r[2] = make_uint4(__float_as_uint(dz[vc]), q, mk, 0u);
         ++slot;
     }
 }
 
-template <int T, int S>
+// MASKED (§7.19): a sample of a stamped record that passes coverage and the < 1.0 test runs the alpha test of its pixel (M1: at the pixel centre, once per
+// (primitive, pixel) — at 4x each covered sample of the pixel evaluates the same function of (side record, i, j), so the four agree) before the minimum.
+template <int T, int S, class... MA>
 __global__ void __launch_bounds__(kFillLanes) k_scene_fill(SceneDepthArgs a, const uint32_t* __restrict__ counter, const uint2* __restrict__ boxes,
-                                                           const uint4* __restrict__ records) {
+                                                           const uint4* __restrict__ records, MA... mask) {
+    constexpr bool MASKED = sizeof...(MA) != 0;
     __shared__ unsigned long long tile[T * T * S];                  // 32 KiB at (32, 4) and at (64, 1)
     __shared__ uint32_t queue[kFillLanes];
     __shared__ uint32_t qn;
@@ -200,6 +227,9 @@ __global__ void __launch_bounds__(kFillLanes) k_scene_fill(SceneDepthArgs a, con
             const int x0 = (int)r0.x, y0 = (int)r0.y, x1 = (int)r0.z, y1 = (int)r0.w, x2 = (int)r1.x, y2 = (int)r1.y;
             const float d0 = __uint_as_float(r1.z), d1 = __uint_as_float(r1.w), d2 = __uint_as_float(r2.x);
             const uint32_t q = r2.y;
+            MaskTri mt;
+            bool alphaTest = false;
+            if constexpr (MASKED) alphaTest = loadMaskTri(maskArgsOf(mask...), r2.z, mt);
             const int bx0 = max((int)(bb.x & 0xffffu), tx0), bx1 = min((int)(bb.x >> 16), tx1);
             const int by0 = max((int)(bb.y & 0xffffu), ty0), by1 = min((int)(bb.y >> 16), ty1);
             const int bw = bx1 - bx0 + 1, nsmp = bw * (by1 - by0 + 1) * S;                               // 1 .. T * T * S
@@ -219,6 +249,7 @@ __global__ void __launch_bounds__(kFillLanes) k_scene_fill(SceneDepthArgs a, con
                 const float b1 = fdiv_((float)E1, fA), b2 = fdiv_((float)E2, fA);
                 const uint32_t bits = __float_as_uint(sat01((d0 + b1 * (d1 - d0)) + b2 * (d2 - d0)));
                 if (bits >= 0x3f800000u) continue;                  // LESS against the clear value 1.0 fails: the sample and its id stay untouched
+                if constexpr (MASKED) { if (alphaTest && maskDiscardScene(mt, i, j, a.width, a.height)) continue; }     // a discarded fragment never reaches the minimum
                 atomicMin(&tile[((j - ty0) * T + (i - tx0)) * S + s], ((unsigned long long)bits << 32) | q);
             }
         }
@@ -267,7 +298,7 @@ __global__ void __launch_bounds__(kFillLanes) k_scene_fill(SceneDepthArgs a, con
 int scene_depth_tile(int rasterTile, int samples) { return rasterTile == 64 && samples == 1 ? 64 : 32; }   // 64 x 64 x 4 keys would be 128 KiB of LDS
 
 hipError_t launch_scene_setup(hipStream_t s, const SceneDepthJob* jobs, int numJobs, uint32_t blocks, const SceneDepthArgs& a, uint32_t* counter, void* boxes, void* records) {
-    hipLaunchKernelGGL(k_scene_setup, dim3(blocks), dim3(kSetupLanes), 0, s, jobs, numJobs, a, counter, (uint2*)boxes, (uint4*)records);
+    hipLaunchKernelGGL(k_scene_setup<>, dim3(blocks), dim3(kSetupLanes), 0, s, jobs, numJobs, a, counter, (uint2*)boxes, (uint4*)records);
     return hipGetLastError();
 }
 hipError_t launch_scene_fill(hipStream_t s, const SceneDepthArgs& a, int tile, const uint32_t* counter, const void* boxes, const void* records) {
@@ -275,6 +306,19 @@ hipError_t launch_scene_fill(hipStream_t s, const SceneDepthArgs& a, int tile, c
     if (a.samples == 4)  hipLaunchKernelGGL((k_scene_fill<32, 4>), dim3(blocks), dim3(kFillLanes), 0, s, a, counter, (const uint2*)boxes, (const uint4*)records);
     else if (tile == 64) hipLaunchKernelGGL((k_scene_fill<64, 1>), dim3(blocks), dim3(kFillLanes), 0, s, a, counter, (const uint2*)boxes, (const uint4*)records);
     else                 hipLaunchKernelGGL((k_scene_fill<32, 1>), dim3(blocks), dim3(kFillLanes), 0, s, a, counter, (const uint2*)boxes, (const uint4*)records);
+    return hipGetLastError();
+}
+
+hipError_t launch_scene_setup_masked(hipStream_t s, const SceneDepthJob* jobs, int numJobs, uint32_t blocks, const SceneDepthArgs& a, uint32_t* counter, void* boxes, void* records,
+                                     const MaskArgs& m) {
+    hipLaunchKernelGGL(k_scene_setup<MaskArgs>, dim3(blocks), dim3(kSetupLanes), 0, s, jobs, numJobs, a, counter, (uint2*)boxes, (uint4*)records, m);
+    return hipGetLastError();
+}
+hipError_t launch_scene_fill_masked(hipStream_t s, const SceneDepthArgs& a, int tile, const uint32_t* counter, const void* boxes, const void* records, const MaskArgs& m) {
+    const uint32_t blocks = (uint32_t)(((a.width + tile - 1) / tile) * ((a.height + tile - 1) / tile));
+    if (a.samples == 4)  hipLaunchKernelGGL((k_scene_fill<32, 4, MaskArgs>), dim3(blocks), dim3(kFillLanes), 0, s, a, counter, (const uint2*)boxes, (const uint4*)records, m);
+    else if (tile == 64) hipLaunchKernelGGL((k_scene_fill<64, 1, MaskArgs>), dim3(blocks), dim3(kFillLanes), 0, s, a, counter, (const uint2*)boxes, (const uint4*)records, m);
+    else                 hipLaunchKernelGGL((k_scene_fill<32, 1, MaskArgs>), dim3(blocks), dim3(kFillLanes), 0, s, a, counter, (const uint2*)boxes, (const uint4*)records, m);
     return hipGetLastError();
 }
 

@@ -288,11 +288,38 @@ struct alignas(16) SceneDepthJob {   // one vqhip_scene_depth_draw
     int32_t indexBits, cullMode;
     uint32_t firstBlock;             // of this k_scene_setup launch: ceil(numTris * numInstances / 256) blocks per job
     uint32_t firstQ;                 // sequence number of (instance 0, triangle 0): the instanced triangles of the draws before
+    uint32_t maskSlot, firstMasked;  // read by k_scene_setup_masked alone (the struct's tail padding before): see MaskTex below
 };
+static_assert(sizeof(SceneDepthJob) == 64, "SceneDepthJob is four uint4");
 static constexpr size_t kSceneBoxBytes = 8, kSceneRecordBytes = 48, kSceneCounterBytes = 256, kSceneFanMax = 8;
 int scene_depth_tile(int rasterTile, int samples);      // pixels per side of k_scene_fill's tile: the option where the LDS budget allows it (not 64 at 4x), else 32
 hipError_t launch_scene_setup(hipStream_t s, const SceneDepthJob* jobs, int numJobs, uint32_t blocks, const SceneDepthArgs& a, uint32_t* counter, void* boxes, void* records);
 hipError_t launch_scene_fill(hipStream_t s, const SceneDepthArgs& a, int tile, const uint32_t* counter, const void* boxes, const void* records);
+
+// Alpha-tested geometry in both rasterisers (vqhip_scene_masked_depth, vqhip_shadow_masked_depth; docs/DESIGN_DETAILS.md §7.19). A masked call appends to the
+// work buffer of the opaque call: MaskTex[number of draws] | MaskSide[masked instanced triangles], each part rounded up to 256 bytes. The table travels through constant-ring slots
+// into the work buffer (k_table_copy), as vqhip_scene_interpolants' draw table does. A job's maskSlot is 1 + its entry in the table, 0 for an opaque draw;
+// firstMasked is the number of masked instanced triangles of the jobs before it. Setup writes the side record of masked triangle firstMasked + t when the
+// triangle emits a record, and stores 1 + that number in the record's last-but-one word (0 in an opaque draw's records, as before): the fan pieces of a
+// clipped triangle share one side record, so M2's uv cannot depend on the piece.
+struct alignas(16) MaskTex {         // what the alpha test reads of a draw's material: 48 bytes
+    const void* texels; int32_t width, height, mips;
+    int32_t pad0;
+    float sx, sy, ox, oy;            // uvScaleOffset (scene depth); unused by the shadow rule
+    uint32_t pad1[2];
+};
+static_assert(sizeof(MaskTex) == 48, "MaskTex is three uint4");
+struct alignas(16) MaskSide {        // per masked triangle: the unclipped clip-space (x, y, w) and the uv of its three vertices, the draw's table entry
+    float c[9]; float uv[6]; uint32_t slot;
+};
+static_assert(sizeof(MaskSide) == 64, "MaskSide is four uint4");
+struct MaskArgs { const MaskTex* table; MaskSide* side; uint64_t sideCap; uint32_t tableCap; };
+struct alignas(16) RasterMaskedJob : RasterJob { uint32_t maskSlot, firstMasked, pad[2]; };
+static_assert(sizeof(RasterMaskedJob) == 80, "RasterMaskedJob is five uint4");
+hipError_t launch_scene_setup_masked(hipStream_t s, const SceneDepthJob* jobs, int numJobs, uint32_t blocks, const SceneDepthArgs& a, uint32_t* counter, void* boxes, void* records, const MaskArgs& m);
+hipError_t launch_scene_fill_masked(hipStream_t s, const SceneDepthArgs& a, int tile, const uint32_t* counter, const void* boxes, const void* records, const MaskArgs& m);
+hipError_t launch_raster_setup_masked(hipStream_t s, const RasterMaskedJob* jobs, int numJobs, uint32_t blocks, const RasterView* views, uint32_t* counters, void* boxes, void* records, const MaskArgs& m);
+hipError_t launch_raster_fill_masked(hipStream_t s, const RasterView* views, int numViews, uint32_t blocks, int tile, const uint32_t* counters, const void* boxes, const void* records, const MaskArgs& m);
 
 // The lit draw's interpolants from meshes (vqhip_scene_interpolants, raster_attr.hip; docs/DESIGN_DETAILS.md §7.18). The draw table travels through constant-ring
 // slots into the work buffer (one k_table_copy launch per slot): the resolve looks up any draw from any pixel, so the table needs a home that outlives the slots.

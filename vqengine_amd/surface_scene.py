@@ -81,3 +81,54 @@ def instance_matrices_full(worlds, view_proj, prev_view_proj, prev_worlds=None):
     prev = worlds if prev_worlds is None else np.asarray(prev_worlds, dtype=np.float64).reshape(-1, 4, 4)
     c = lambda m: np.ascontiguousarray(np.asarray(m).astype(F))      # noqa: E731
     return c(worlds @ view_proj), c(worlds), c(np.stack([rotation_of(w) for w in worlds])), c(prev @ prev_view_proj)
+
+
+# ---- alpha-tested geometry: what vqhip_scene_masked_depth / vqhip_shadow_masked_depth consume beside the meshes above ---------------------------------------------
+def card(half_w=1.0, half_h=1.0, uv_min=(0.0, 0.0), uv_max=(1.0, 1.0)):
+    """A leaf / fence / decal card: the box's -z face alone, in the plane z = 0 (normal -z, tangent +x), clockwise seen from -z. uv runs from uv_min (the corner
+    -x, -y) to uv_max: values outside [0, 1] and negative ones exercise WRAP. Returns (vertices float32 [4, 11], indices int64 [6])."""
+    (u0, v0), (u1, v1) = uv_min, uv_max
+    verts = [np.array([(2 * u - 1) * half_w, (2 * v - 1) * half_h, 0.0, 0, 0, -1, 1, 0, 0, u0 + u * (u1 - u0), v0 + v * (v1 - v0)], dtype=np.float64)
+             for (u, v) in ((0, 0), (0, 1), (1, 1), (1, 0))]
+    return np.array(verts, dtype=F), np.array([0, 1, 2, 0, 2, 3], dtype=np.int64)
+
+
+def alpha_checker(width, height, cell=1, rgb=(200, 180, 90)):
+    """An RGBA8 checker of `cell`-texel squares whose alpha is 0 / 255 (texel (0, 0) is transparent): uint8 [height, width, 4]"""
+    y, x = np.mgrid[0:height, 0:width]
+    img = np.empty((height, width, 4), dtype=np.uint8)
+    img[..., :3] = rgb
+    img[..., 3] = np.where(((x // cell) + (y // cell)) % 2 == 1, 255, 0)
+    return img
+
+
+def alpha_columns(width, height, period=4, opaque=(1, 2), rgb=(90, 160, 60)):
+    """An RGBA8 pattern of vertical stripes: alpha 255 in the columns whose x % period is in `opaque`, else 0. The default (T O O T) has two transparent columns
+    side by side — a bilinear fetch reads 0 between them — while every 2 x 2 block is half opaque: mip 1 is 127 everywhere. uint8 [height, width, 4]"""
+    img = np.empty((height, width, 4), dtype=np.uint8)
+    img[..., :3] = rgb
+    img[..., 3] = np.where(np.isin(np.arange(width) % period, opaque), 255, 0)[None, :]
+    return img
+
+
+def mip_chain_rgba8(level0, mips=None):
+    """The mip chain the engine uploads (VQ_DXGI_UTILS::MipImage, 4-byte branch: each channel (a + b + c + d) / 4 in integers, the last row / column of an odd
+    level repeated): (chain uint8 [texels of all levels, 4], number of levels). mips None = down to 1 x 1. A 1-texel alpha checker has mip 1 = 127 everywhere."""
+    lv = np.ascontiguousarray(level0, dtype=np.uint8)
+    h, w = lv.shape[:2]
+    full = 1
+    while max(w, h) >> full:
+        full += 1
+    n = full if mips is None else int(mips)
+    if not 1 <= n <= full:
+        raise ValueError(f"mip_chain_rgba8: mips must be 1..{full}")
+    out = [lv.reshape(-1, 4)]
+    for _ in range(1, n):
+        sh, sw = lv.shape[:2]
+        dh, dw = max(sh // 2, 1), max(sw // 2, 1)
+        y0, x0 = 2 * np.arange(dh), 2 * np.arange(dw)
+        y1, x1 = np.minimum(y0 + 1, sh - 1), np.minimum(x0 + 1, sw - 1)
+        s = lv.astype(np.uint32)
+        lv = ((s[y0][:, x0] + s[y0][:, x1] + s[y1][:, x0] + s[y1][:, x1]) // 4).astype(np.uint8)
+        out.append(lv.reshape(-1, 4))
+    return np.ascontiguousarray(np.concatenate(out, axis=0)), n
