@@ -4,6 +4,7 @@ view. Needs the GPU. The workload of a `rocprofv3 --kernel-trace --stats` run of
   --variant masked   vqhip_scene_masked_depth / vqhip_shadow_masked_depth with the cards masked
   --variant opaque   the same entry points, every material NULL: the existing kernels' instantiations
   --variant base     vqhip_scene_depth / vqhip_shadow_depth (this variant runs on a tree from before the masked entry points, too)
+  --tile 32 64       every configuration once per value of the raster_tile option (default: the option's default alone)
   --mode time        instead of the loop: each configuration timed between device events (benchlib.timing._stage_stats), one JSON line
 The descriptors are built once (Context.*_prepared): the timed call is the C entry point, not the Python that fills its structures."""
 import argparse
@@ -18,6 +19,7 @@ ap.add_argument("--variant", default="masked", choices=("masked", "opaque", "bas
 ap.add_argument("--mode", default="loop", choices=("loop", "time"))
 ap.add_argument("--steps", type=int, default=50)
 ap.add_argument("--cards", type=int, default=300)
+ap.add_argument("--tile", type=int, nargs="*", default=[None])
 ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the checkout whose vqengine_amd is measured")
 ARGS = ap.parse_args()
 sys.path.insert(0, os.path.abspath(ARGS.tree))
@@ -91,7 +93,8 @@ def main():
     prep = ctx.shadow_masked_depth_prepared if new_entry else ctx.shadow_depth_prepared
     calls["shadow_2048"] = prep([capi.ShadowView(smap, lit)])
     results = {}
-    for name, (call, res) in calls.items():
+    for name, (call, res), tile in [(n + (f"_tile{t}" if t else ""), c, t) for n, c in calls.items() for t in ARGS.tile]:
+        ctx.set_option("raster_tile", tile)
         call()
         torch.cuda.synchronize()
         if ARGS.mode == "loop":

@@ -2005,7 +2005,7 @@ int shadowDepthCall(vqhip_ctx* ctx, void* stream, const VIEW* views, int numView
             }
             if (int rc = commitSlot(ctx, slot, sizeof(JOB) * n, st)) return rc;
             const JOB* djobs = (const JOB*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
-            if constexpr (kMaskedJob) e = launch_raster_setup_masked(st, djobs, (int)n, (uint32_t)blocks, dviews, counters, boxes, records, ma);
+            if constexpr (kMaskedJob) e = launch_raster_setup(st, djobs, (int)n, (uint32_t)blocks, dviews, counters, boxes, records, ma);
             else                      e = launch_raster_setup(st, djobs, (int)n, (uint32_t)blocks, dviews, counters, boxes, records);
             if (e != hipSuccess) return failHip(ctx, e, (who + " setup launch").c_str());
             if (int rc = releaseSlot(ctx, slot, st)) return rc;
@@ -2014,7 +2014,7 @@ int shadowDepthCall(vqhip_ctx* ctx, void* stream, const VIEW* views, int numView
         return VQHIP_OK;
     };
     if (int rc = anyMasked ? setupLaunches(RasterMaskedJob{}) : setupLaunches(RasterJob{})) return rc;
-    e = anyMasked ? launch_raster_fill_masked(st, dviews, numViews, (uint32_t)fillBlocks, tile, counters, boxes, records, ma)
+    e = anyMasked ? launch_raster_fill(st, dviews, numViews, (uint32_t)fillBlocks, tile, counters, boxes, records, ma)
                   : launch_raster_fill(st, dviews, numViews, (uint32_t)fillBlocks, tile, counters, boxes, records);
     if (e != hipSuccess) return failHip(ctx, e, (who + " fill launch").c_str());
     return releaseSlot(ctx, viewSlot, st);
@@ -2182,13 +2182,13 @@ int sceneDepthCall(vqhip_ctx* ctx, void* stream, const DRAW* draws, int numDraws
         }
         if (int rc = commitSlot(ctx, slot, sizeof(SceneDepthJob) * n, st)) return rc;
         const SceneDepthJob* djobs = (const SceneDepthJob*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
-        e = anyMasked ? launch_scene_setup_masked(st, djobs, (int)n, (uint32_t)blocks, a, counter, boxes, records, ma)
+        e = anyMasked ? launch_scene_setup(st, djobs, (int)n, (uint32_t)blocks, a, counter, boxes, records, ma)
                       : launch_scene_setup(st, djobs, (int)n, (uint32_t)blocks, a, counter, boxes, records);
         if (e != hipSuccess) return failHip(ctx, e, (who + " setup launch").c_str());
         if (int rc = releaseSlot(ctx, slot, st)) return rc;
         left -= n;
     }
-    e = anyMasked ? launch_scene_fill_masked(st, a, scene_depth_tile(ctx->opt.rasterTile, samples), counter, boxes, records, ma)
+    e = anyMasked ? launch_scene_fill(st, a, scene_depth_tile(ctx->opt.rasterTile, samples), counter, boxes, records, ma)
                   : launch_scene_fill(st, a, scene_depth_tile(ctx->opt.rasterTile, samples), counter, boxes, records);
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (who + " fill launch").c_str());
 }

@@ -8,8 +8,7 @@
 //                           through the vertex stage -> weights -> 11 or 19 attributes; float4 stores, one plane at a time.
 // Every index is checked before it is used: q against the call's instanced triangles, the three indices against numVertices. Nothing an owner plane or a mesh
 // holds can move a load or a store out of bounds.
-#include "vq_internal.h"
-#include "vq_devmath.h"
+#include "vq_raster.h"
 
 namespace vqk {
 using namespace vqd;
@@ -66,12 +65,7 @@ VQD void resolveOwner(const SceneInterpArgs& a, const SurfaceJob* __restrict__ t
     const uint32_t r = q - J.firstQ, numTris = J.numTris;
     const uint32_t inst = r / numTris, tri = r % numTris;
     uint32_t idx[3];
-    bool ok = inst < J.numInstances;              // holds by construction of firstQ; checked all the same
-    for (int k = 0; k < 3; ++k) {
-        idx[k] = J.indexBits == 16 ? (uint32_t)((const uint16_t*)J.indices)[(size_t)tri * 3 + k] : ((const uint32_t*)J.indices)[(size_t)tri * 3 + k];
-        ok = ok && idx[k] < J.numVertices;
-    }
-    if (!ok) return;
+    if (!fetchTriangle(J.indices, J.indexBits, tri, J.numVertices, idx) || inst >= J.numInstances) return;      // the latter holds by construction of firstQ; checked all the same
     const VQ_matrix& wvp = J.wvp[inst];
     const VQ_matrix& world = J.world[inst];
     const VQ_matrix& nrm = J.normal[inst];
@@ -82,7 +76,7 @@ VQD void resolveOwner(const SceneInterpArgs& a, const SurfaceJob* __restrict__ t
     const Vert v1 = vertexStage<SV>((const float*)(vb + idx[1] * stride), wvp, world, nrm, prev);
     const Vert v2 = vertexStage<SV>((const float*)(vb + idx[2] * stride), wvp, world, nrm, prev);
     // I2
-    const double X = (double)(2 * i + 1) / (double)a.width - 1.0, Y = 1.0 - (double)(2 * j + 1) / (double)a.height;
+    const double X = pixelCentreX(i, a.width), Y = pixelCentreY(j, a.height);
     const double x0 = v0.a[11], y0 = v0.a[12], w0 = v0.a[14], x1 = v1.a[11], y1 = v1.a[12], w1 = v1.a[14], x2 = v2.a[11], y2 = v2.a[12], w2 = v2.a[14];
     const double k0 = det(X, Y, x1, y1, w1, x2, y2, w2), k1 = det(X, Y, x2, y2, w2, x0, y0, w0), k2 = det(X, Y, x0, y0, w0, x1, y1, w1);
     const double den = (k0 + k1) + k2;

@@ -269,8 +269,11 @@ struct alignas(16) RasterJob {       // one vqhip_shadow_draw of one view
 };
 static constexpr size_t kRasterBoxBytes = 8, kRasterRecordBytes = 80, kRasterCounterBytes = 256;
 hipError_t launch_raster_begin(hipStream_t s, uint32_t* counters, int numViews);
-hipError_t launch_raster_setup(hipStream_t s, const RasterJob* jobs, int numJobs, uint32_t blocks, const RasterView* views, uint32_t* counters, void* boxes, void* records);
-hipError_t launch_raster_fill(hipStream_t s, const RasterView* views, int numViews, uint32_t blocks, int tile, const uint32_t* counters, const void* boxes, const void* records);
+// setup and fill take the call's MaskArgs (§7.19, below) as one more argument when a draw of the call is alpha-tested: JOB = RasterJob, or RasterMaskedJob with MaskArgs
+template <class JOB, class... MA>
+hipError_t launch_raster_setup(hipStream_t s, const JOB* jobs, int numJobs, uint32_t blocks, const RasterView* views, uint32_t* counters, void* boxes, void* records, const MA&... mask);
+template <class... MA>
+hipError_t launch_raster_fill(hipStream_t s, const RasterView* views, int numViews, uint32_t blocks, int tile, const uint32_t* counters, const void* boxes, const void* records, const MA&... mask);
 
 // Main-view depth pre-pass (vqhip_scene_depth, raster_view.hip; docs/DESIGN_DETAILS.md §7.17). The draw jobs travel in constant-ring slots, the targets as kernel arguments.
 // Work buffer: one record counter (256 B), the records' pixel boxes (8 B each), the records (48 B each: three snapped vertices, three z/w, q); recCap = 8 x the
@@ -288,13 +291,16 @@ struct alignas(16) SceneDepthJob {   // one vqhip_scene_depth_draw
     int32_t indexBits, cullMode;
     uint32_t firstBlock;             // of this k_scene_setup launch: ceil(numTris * numInstances / 256) blocks per job
     uint32_t firstQ;                 // sequence number of (instance 0, triangle 0): the instanced triangles of the draws before
-    uint32_t maskSlot, firstMasked;  // read by k_scene_setup_masked alone (the struct's tail padding before): see MaskTex below
+    uint32_t maskSlot, firstMasked;  // read by k_scene_setup<MaskArgs> alone (the struct's tail padding before): see MaskTex below
 };
 static_assert(sizeof(SceneDepthJob) == 64, "SceneDepthJob is four uint4");
 static constexpr size_t kSceneBoxBytes = 8, kSceneRecordBytes = 48, kSceneCounterBytes = 256, kSceneFanMax = 8;
 int scene_depth_tile(int rasterTile, int samples);      // pixels per side of k_scene_fill's tile: the option where the LDS budget allows it (not 64 at 4x), else 32
-hipError_t launch_scene_setup(hipStream_t s, const SceneDepthJob* jobs, int numJobs, uint32_t blocks, const SceneDepthArgs& a, uint32_t* counter, void* boxes, void* records);
-hipError_t launch_scene_fill(hipStream_t s, const SceneDepthArgs& a, int tile, const uint32_t* counter, const void* boxes, const void* records);
+// as the shadow rasteriser's: with the call's MaskArgs when a draw of the call is alpha-tested, without it otherwise
+template <class... MA>
+hipError_t launch_scene_setup(hipStream_t s, const SceneDepthJob* jobs, int numJobs, uint32_t blocks, const SceneDepthArgs& a, uint32_t* counter, void* boxes, void* records, const MA&... mask);
+template <class... MA>
+hipError_t launch_scene_fill(hipStream_t s, const SceneDepthArgs& a, int tile, const uint32_t* counter, const void* boxes, const void* records, const MA&... mask);
 
 // Alpha-tested geometry in both rasterisers (vqhip_scene_masked_depth, vqhip_shadow_masked_depth; docs/DESIGN_DETAILS.md §7.19). A masked call appends to the
 // work buffer of the opaque call: MaskTex[number of draws] | MaskSide[masked instanced triangles], each part rounded up to 256 bytes. The table travels through constant-ring slots
@@ -316,10 +322,6 @@ static_assert(sizeof(MaskSide) == 64, "MaskSide is four uint4");
 struct MaskArgs { const MaskTex* table; MaskSide* side; uint64_t sideCap; uint32_t tableCap; };
 struct alignas(16) RasterMaskedJob : RasterJob { uint32_t maskSlot, firstMasked, pad[2]; };
 static_assert(sizeof(RasterMaskedJob) == 80, "RasterMaskedJob is five uint4");
-hipError_t launch_scene_setup_masked(hipStream_t s, const SceneDepthJob* jobs, int numJobs, uint32_t blocks, const SceneDepthArgs& a, uint32_t* counter, void* boxes, void* records, const MaskArgs& m);
-hipError_t launch_scene_fill_masked(hipStream_t s, const SceneDepthArgs& a, int tile, const uint32_t* counter, const void* boxes, const void* records, const MaskArgs& m);
-hipError_t launch_raster_setup_masked(hipStream_t s, const RasterMaskedJob* jobs, int numJobs, uint32_t blocks, const RasterView* views, uint32_t* counters, void* boxes, void* records, const MaskArgs& m);
-hipError_t launch_raster_fill_masked(hipStream_t s, const RasterView* views, int numViews, uint32_t blocks, int tile, const uint32_t* counters, const void* boxes, const void* records, const MaskArgs& m);
 
 // The lit draw's interpolants from meshes (vqhip_scene_interpolants, raster_attr.hip; docs/DESIGN_DETAILS.md §7.18). The draw table travels through constant-ring
 // slots into the work buffer (one k_table_copy launch per slot): the resolve looks up any draw from any pixel, so the table needs a home that outlives the slots.

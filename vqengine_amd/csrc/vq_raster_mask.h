@@ -4,7 +4,7 @@
 //   M3  scene depth: uv * uvScaleOffset, derivatives from helper lanes (the same primitive at (i ^ 1, j) and (i, j ^ 1)), the trilinear WRAP fetch of gbuffer.hip
 //   M4  shadow: the raw uv, the bilinear WRAP fetch of level 0
 #pragma once
-#include "vq_internal.h"
+#include "vq_raster.h"
 #include "vq_tex8.h"
 
 namespace vqk {
@@ -39,10 +39,6 @@ VQD bool loadMaskTri(const MaskArgs& m, uint32_t mk, MaskTri& t) {
     return true;
 }
 
-// I2's pixel centre on one axis: (2 i + 1) / W - 1 and 1 - (2 j + 1) / H, each operation rounded once; i, j may lie outside the viewport
-VQD double maskCentreX(int i, int W) { return (double)(2 * i + 1) / (double)W - 1.0; }
-VQD double maskCentreY(int j, int H) { return 1.0 - (double)(2 * j + 1) / (double)H; }
-
 // M2: the primitive's uv at the pixel centre (X, Y), which may lie outside the primitive (extrapolation)
 VQD float2 maskUvAt(const MaskTri& t, double X, double Y) {
     const double k0 = (X * t.P[0] - Y * t.Q[0]) + t.R[0], k1 = (X * t.P[1] - Y * t.Q[1]) + t.R[1], k2 = (X * t.P[2] - Y * t.Q[2]) + t.R[2];
@@ -56,8 +52,8 @@ VQD float2 maskUvAt(const MaskTri& t, double X, double Y) {
 VQD bool maskDiscardScene(const MaskTri& t, int i, int j, int W, int H) {
     const MaskTex& x = t.tex;
     if (!x.texels) return true;                                       // null SRV: samples 0
-    const double X = maskCentreX(i, W), Y = maskCentreY(j, H);        // the quotients of the own centre serve both helper lanes
-    const float2 o = maskUvAt(t, X, Y), h = maskUvAt(t, maskCentreX(i ^ 1, W), Y), v = maskUvAt(t, X, maskCentreY(j ^ 1, H));
+    const double X = pixelCentreX(i, W), Y = pixelCentreY(j, H);        // the quotients of the own centre serve both helper lanes
+    const float2 o = maskUvAt(t, X, Y), h = maskUvAt(t, pixelCentreX(i ^ 1, W), Y), v = maskUvAt(t, X, pixelCentreY(j ^ 1, H));
     const float2 uv = make_float2(o.x * x.sx + x.ox, o.y * x.sy + x.oy);                          // as produce_record (gbuffer.hip) evaluates it
     const float hu = h.x * x.sx + x.ox, hv = h.y * x.sy + x.oy, vu = v.x * x.sx + x.ox, vv = v.y * x.sy + x.oy;
     const float2 ddx = (i & 1) ? make_float2(uv.x - hu, uv.y - hv) : make_float2(hu - uv.x, hv - uv.y);
@@ -72,7 +68,7 @@ VQD bool maskDiscardScene(const MaskTri& t, int i, int j, int W, int H) {
 VQD bool maskDiscardShadow(const MaskTri& t, int i, int j, int dim) {
     const MaskTex& x = t.tex;
     if (!x.texels) return true;
-    const float2 uv = maskUvAt(t, maskCentreX(i, dim), maskCentreY(j, dim));
+    const float2 uv = maskUvAt(t, pixelCentreX(i, dim), pixelCentreY(j, dim));
     return fetch_lane_alpha_level0(x.texels, x.width, x.height, uv.x, uv.y) < 0.01f;
 }
 
