@@ -529,7 +529,7 @@ int vqhip_forward_lighting_msaa(vqhip_ctx* ctx, void* stream, const vqhip_gbuffe
     a.edgeCount = (uint32_t*)ctx->edge; a.edgeList = (uint32_t*)ctx->edge + 1;
     a.width = W; a.height = H; a.layers = gb->layers; a.covPitch = covPitch; a.bgPitch = background_pitch_px; a.outPitch = out_row_pitch_px;
     HIP_TRY(ctx, hipMemsetAsync(ctx->edge, 0, 4, st));
-    hipError_t e = launch_forward_lighting_msaa(st, a, env != nullptr, casters, outFmt, ctx->arithDxc, ctx->nCUs);
+    hipError_t e = launch_forward_lighting_msaa(st, a, env != nullptr, casters, outFmt, ctx->arithDxc, ctx->nCUs, ctx->opt);
     if (e != hipSuccess) return failHip(ctx, e, "forward_lighting_msaa launch");
     HIP_TRY(ctx, hipEventRecord(ctx->edgeFree, st));
     ctx->edgeUsed = true;
@@ -692,6 +692,7 @@ int vqhip_set_option(vqhip_ctx* ctx, const char* key, const char* value) {
     if (k == "shade_wg") return num(&o.shadeWg, { 0, 64, 128, 256 });
     if (k == "psmain_waves") return num(&o.psmainWaves, { 0, 4, 5, 6 });
     if (k == "blur_y_wgs") return num(&o.blurYWgs, {});
+    if (k == "msaa_edge_wgs") return num(&o.msaaEdgeWgs, {});
     if (k == "post_form") return pick(&o.postForm, { "two", "chain" });
     if (k == "post_strips") return num(&o.postStrips, {});
     if (k == "lut_form") return pick(&o.lutForm, { "general" });

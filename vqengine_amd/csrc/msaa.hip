@@ -140,33 +140,45 @@ __global__ __launch_bounds__(256, VQ_SHADE_WAVES) void k_msaa_edges(MsaaArgs a) 
 }
 
 template <bool E, bool C, int FMT, int AR>
-hipError_t launch_pair(hipStream_t s, const MsaaArgs& a, dim3 grid, int wg, int nCUs) {
+hipError_t launch_pair(hipStream_t s, const MsaaArgs& a, dim3 grid, int wg, int nCUs, int edgeWgs) {
     hipLaunchKernelGGL((k_msaa_shade<E, C, FMT, AR>), grid, dim3(wg), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    // k_msaa_edges fills every CU once: as many 256-lane workgroups per CU as its register budget admits (queried once per instantiation)
+    // k_msaa_edges fills every CU once: as many 256-lane workgroups per CU as its register budget admits (queried once per instantiation).
+    // Option "msaa_edge_wgs" overrides the number of workgroups (tests: the grid-stride step with a list longer than the grid); edgeWgs comes
+    // clamped from launch_forward_lighting_msaa.
     static const int perCU = [] {
         int n = 0;
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_msaa_edges<E, C, FMT, AR>, 256, 0) == hipSuccess && n > 0 ? n : 2;
     }();
-    hipLaunchKernelGGL((k_msaa_edges<E, C, FMT, AR>), dim3(perCU * nCUs), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_msaa_edges<E, C, FMT, AR>), dim3(edgeWgs > 0 ? edgeWgs : perCU * nCUs), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 template <bool E, bool C>
-hipError_t launch_fmt(hipStream_t s, const MsaaArgs& a, int outFmt, int arithDxc, dim3 grid, int wg, int nCUs) {
-    if (outFmt == VQHIP_FMT_RGBA32F) return arithDxc ? launch_pair<E, C, 0, 1>(s, a, grid, wg, nCUs) : launch_pair<E, C, 0, 0>(s, a, grid, wg, nCUs);
-    return arithDxc ? launch_pair<E, C, 1, 1>(s, a, grid, wg, nCUs) : launch_pair<E, C, 1, 0>(s, a, grid, wg, nCUs);
+hipError_t launch_fmt(hipStream_t s, const MsaaArgs& a, int outFmt, int arithDxc, dim3 grid, int wg, int nCUs, int edgeWgs) {
+    if (outFmt == VQHIP_FMT_RGBA32F) return arithDxc ? launch_pair<E, C, 0, 1>(s, a, grid, wg, nCUs, edgeWgs) : launch_pair<E, C, 0, 0>(s, a, grid, wg, nCUs, edgeWgs);
+    return arithDxc ? launch_pair<E, C, 1, 1>(s, a, grid, wg, nCUs, edgeWgs) : launch_pair<E, C, 1, 0>(s, a, grid, wg, nCUs, edgeWgs);
 }
 
 } // namespace
 
 namespace vqk {
-hipError_t launch_forward_lighting_msaa(hipStream_t s, const MsaaArgs& a, bool hasEnv, bool hasCasters, int outFmt, int arithDxc, int nCUs) {
-    // k_msaa_shade: the workgroup shape of k_forward_lighting's default (shade.hip); k_msaa_edges walks the list whatever its length
-    const int wg = (size_t)a.width * a.height < ((size_t)4 << 20) ? 64 : 256;
+hipError_t launch_forward_lighting_msaa(hipStream_t s, const MsaaArgs& a, bool hasEnv, bool hasCasters, int outFmt, int arithDxc, int nCUs, const Options& opt) {
+    // k_msaa_shade: the workgroup shape of k_forward_lighting's default (shade.hip), option "shade_wg" overrides it here as there; k_msaa_edges walks the
+    // list whatever its length
+    int wg = (size_t)a.width * a.height < ((size_t)4 << 20) ? 64 : 256;
+    if (opt.shadeWg == 64 || opt.shadeWg == 128 || opt.shadeWg == 256) wg = opt.shadeWg;
     const dim3 grid((a.width + wg - 1) / wg, a.height);
     if (nCUs <= 0) nCUs = 256;
-    if (hasEnv) return hasCasters ? launch_fmt<true, true>(s, a, outFmt, arithDxc, grid, wg, nCUs) : launch_fmt<true, false>(s, a, outFmt, arithDxc, grid, wg, nCUs);
-    return hasCasters ? launch_fmt<false, true>(s, a, outFmt, arithDxc, grid, wg, nCUs) : launch_fmt<false, false>(s, a, outFmt, arithDxc, grid, wg, nCUs);
+    // "msaa_edge_wgs": never more workgroups than one lane per pixel needs (the list holds at most width * height entries), nor than 65 536 — the
+    // kernel's stride gridDim.x * 256 is a 32-bit product, and a stride that wrapped to 0 would never leave the loop
+    int edgeWgs = 0;
+    if (opt.msaaEdgeWgs > 0) {
+        const size_t perPixel = ((size_t)a.width * a.height + 255) / 256;
+        const size_t cap = perPixel < 65536 ? perPixel : 65536;
+        edgeWgs = (size_t)opt.msaaEdgeWgs < cap ? opt.msaaEdgeWgs : (int)cap;
+    }
+    if (hasEnv) return hasCasters ? launch_fmt<true, true>(s, a, outFmt, arithDxc, grid, wg, nCUs, edgeWgs) : launch_fmt<true, false>(s, a, outFmt, arithDxc, grid, wg, nCUs, edgeWgs);
+    return hasCasters ? launch_fmt<false, true>(s, a, outFmt, arithDxc, grid, wg, nCUs, edgeWgs) : launch_fmt<false, false>(s, a, outFmt, arithDxc, grid, wg, nCUs, edgeWgs);
 }
 } // namespace vqk

@@ -20,9 +20,10 @@ struct Range {
 // Tuning / A-B options of one context (vqhip_set_option, include/vqhip.h). Read by the launchers from the context the call came through — never
 // from the process environment: getenv racing a host setenv is undefined behaviour in glibc and the engine is heavily threaded. 0 / "" = the default.
 struct Options {
-    int shadeWg = 0;            // "shade_wg"          : 64 | 128 | 256 lanes per workgroup of the shade kernel (default: by frame size)
+    int shadeWg = 0;            // "shade_wg"          : 64 | 128 | 256 lanes per workgroup of the shade kernels k_forward_lighting and k_msaa_shade (default: by frame size)
     int psmainWaves = 0;        // "psmain_waves"      : 4 | 5 | 6 waves per SIMD of the fused PSMain kernel
     int blurYWgs = 0;           // "blur_y_wgs"        : workgroups of k_blur_y_tonemap_lut
+    int msaaEdgeWgs = 0;        // "msaa_edge_wgs"     : 256-lane workgroups of the persistent k_msaa_edges (default: as many as fill every CU once; clamped at launch)
     int postForm = 0;           // "post_form"         : 1 "two" = blur X, then blur Y + tonemap (two kernels) whatever the frame; 2 "chain" = k_post_chain whatever the size
                                 //                       (default: k_post_chain for RGBA16F -> RGBA8 frames of >= 2^20 pixels with a per-channel display curve, else two kernels)
     int postStrips = 0;         // "post_strips"       : row strips per column strip of k_post_chain (default: CUs / column strips — one workgroup per CU)
@@ -214,7 +215,7 @@ struct MsaaArgs {
     uint32_t* edgeCount; uint32_t* edgeList;
     int width, height, layers, covPitch, bgPitch, outPitch;
 };
-hipError_t launch_forward_lighting_msaa(hipStream_t s, const MsaaArgs& a, bool hasEnv, bool hasCasters, int outFmt, int arithDxc, int nCUs);
+hipError_t launch_forward_lighting_msaa(hipStream_t s, const MsaaArgs& a, bool hasEnv, bool hasCasters, int outFmt, int arithDxc, int nCUs, const Options& opt);
 
 // 4x MSAA surface resolve + depth hierarchy (vqhip_msaa_resolve_surfaces / vqhip_depth_hierarchy, depth.hip). Output pointers NULL = that output is not live.
 struct SurfLayer { const uint8_t* cov; const void* normals; const float4* gb1; int nPitch, rPitch; };
