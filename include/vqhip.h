@@ -1207,7 +1207,8 @@ VQHIP_API int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_
  * readback. Draw descriptors are host memory, consumed before the call returns; meshes and matrices are device memory, read when the kernel runs. Not modelled:
  * the heightmap (the null heightmap's float3 add is kept), tessellation. The alpha mask needs nothing here: vqhip_scene_masked_depth keeps discarded fragments out of
  * the owner plane, and the shading entry points repeat the discard. vqhip_gbuffer_from_materials still takes its uv LOD from neighbouring pixels
- * of the planes, so at primitive edges it differs from a helper-lane derivative. */
+ * of the planes, so at primitive edges it differs from a helper-lane derivative. vqhip_scene_quad_interpolants and the _quad producers (below, after the
+ * masked-depth section) carry the helper lanes' uv from this resolve to the producers and close that gap. */
 typedef struct vqhip_scene_surface_draw {   /* one DrawIndexedInstanced of the lit pass */
     vqhip_shadow_mesh mesh;                 /* the engine's vertex: position @0, normal @12, tangent @24, uv @36; strideBytes >= 44, a multiple of 4 */
     const VQ_matrix* matWorldViewProj;      /* device, [numInstances]: PerObjectLightingData */
@@ -1300,6 +1301,49 @@ VQHIP_API size_t vqhip_shadow_masked_depth_work_bytes(uint64_t instancedTriangle
  * masked instanced triangles in one call. */
 VQHIP_API int vqhip_shadow_masked_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_masked_view* views, int numViews, void* work, size_t workBytes);
 #define VQHIP_MASK_TEXTURE_MAX_DIM 16384
+
+/* ---- Helper-lane uv derivatives for the lit draw (docs/DESIGN_DETAILS.md §7.20; tests/quad_interp_ref.py states it in numpy). D3D takes the implicit derivatives
+ * of Texture2D.Sample from the 2 x 2 quad aligned to even pixel coordinates, and the quad's other lanes run the OWN primitive as helper lanes — covered or not,
+ * inside the viewport or not. vqhip_scene_masked_depth already evaluates its discard that way (M3); the producers of vqhip_interpolants planes read the planes'
+ * neighbours instead, which belong to whatever owns those pixels. The calls below carry the helper lanes' uv from the resolve to the producers, so that the
+ * pre-pass and the lit draw take the same derivative — and the same alpha-test decision — for every (primitive, pixel).
+ *   Q1  vqhip_scene_quad_interpolants = vqhip_scene_interpolants (the five planes hold exactly what that call writes; its work size, limits and refusals) + one
+ *       float4 plane quadUV [height][quad_pitch]: for an owned pixel (i, j) (I0's rule) quadUV = (u_h, v_h, u_v, v_v), the owner triangle's vertex uv at the centres
+ *       of pixels (i ^ 1, j) and (i, j ^ 1) by §7.18 I2 / I3 (weights and quotients afresh in binary64 at that centre, one rounding, NaN = 0x7FC00000). i ^ 1 may
+ *       equal width and j ^ 1 height; the triangle need not cover the partner; at 4x the own centre may already lie outside it. A pixel with no owner holds
+ *       (0, 0, 0, 0). Both interp_form values give the same bits.
+ *   Q2  the _quad producers = their siblings with ddx = own - helper_h on odd i, helper_h - own on even i (ddy alike with j and helper_v), where helper =
+ *       uv_helper * uvScaleOffset.xy + uvScaleOffset.zw rounded as the own uv' is. No material comparison and no image-bounds test: a helper lane always belongs
+ *       to the own primitive. Footprint, LOD, taps, normalMapMipBias, the discard and its -1 into ip2.w, SSAO and both arithmetic readings are the siblings'.
+ *       quadUV: 16-byte aligned, quad_pitch_px pixels per row (0 = in->row_pitch_px), smaller than 4 GiB.
+ * The derivative form is the UNPINNED M3 form (docs/WARP_CALIBRATION.md §5). vqhip_gbuffer_from_materials and its siblings keep the neighbour rule for callers
+ * who bring planes from a rasteriser of their own. */
+typedef struct vqhip_scene_quad_targets {
+    vqhip_scene_interpolant_targets planes;   /* as for vqhip_scene_interpolants */
+    void*   quadUV;                            /* float4 [height][quad_pitch], 16-byte aligned, required */
+    int32_t quad_pitch;                        /* pixels per row, 0 = width */
+    int32_t pad_;
+} vqhip_scene_quad_targets;
+VQHIP_STATIC_ASSERT(sizeof(vqhip_scene_quad_targets) == 64 && offsetof(vqhip_scene_quad_targets, quadUV) == 48 && offsetof(vqhip_scene_quad_targets, quad_pitch) == 56,
+                    "vqhip_scene_quad_targets layout");
+/* work: vqhip_scene_interpolants_work_bytes(numDraws). vqhip_scene_interpolants' refusals, and VQHIP_ERR_INVALID_ARG — launching nothing, leaving the outputs
+ * untouched — for quadUV NULL or not 16-byte aligned, quad_pitch negative or below width, quadUV overlapping the owner plane, the work buffer or another output. */
+VQHIP_API int vqhip_scene_quad_interpolants(vqhip_ctx* ctx, void* stream, const vqhip_scene_surface_draw* draws, int numDraws, int width, int height,
+        const uint32_t* owner, int owner_pitch_px, const vqhip_scene_quad_targets* out, void* work, size_t workBytes);
+/* The siblings' refusals, and VQHIP_ERR_INVALID_ARG for quadUV NULL or not 16-byte aligned, quad_pitch_px negative or below in->width, quadUV overlapping an
+ * output (ip2 included: its w receives the discard's -1); VQHIP_ERR_UNSUPPORTED for a quadUV plane of 4 GiB or more. */
+VQHIP_API int vqhip_gbuffer_from_materials_quad(vqhip_ctx* ctx, void* stream,
+        const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
+        float fAmbientLightingFactor, const vqhip_ssao* ssao, const vqhip_gbuffer* out, const void* quadUV, int quad_pitch_px);
+/* targets: as for vqhip_forward_lighting_from_materials_mrt; NULL = no extra targets */
+VQHIP_API int vqhip_forward_lighting_from_materials_quad(vqhip_ctx* ctx, void* stream,
+        const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials, const vqhip_ssao* ssao,
+        const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
+        const VQ_PointLight* extraPoint, int numExtraPoint, const vqhip_envmap* env, const vqhip_shadowmaps* sm,
+        void* out, int out_row_pitch_px, vqhip_format outFmt, const vqhip_psmain_targets* targets, const void* quadUV, int quad_pitch_px);
+VQHIP_API int vqhip_scene_normals_from_materials_quad(vqhip_ctx* ctx, void* stream,
+        const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
+        void* out, vqhip_format outFmt, int out_row_pitch_px, const void* quadUV, int quad_pitch_px);
 
 #ifdef __cplusplus
 }

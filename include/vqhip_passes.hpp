@@ -819,6 +819,118 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// The same resolve with the helper lanes' uv (docs/DESIGN_DETAILS.md §7.20): vqhip_scene_quad_interpolants. The inputs are SceneInterpolantsPass's; QuadUV is one
+// more float4 plane of the window's size, which QuadLitDrawPass below reads so that Texture2D.Sample takes the derivatives D3D's helper lanes give — the ones
+// MaskedDepthPrePass already used for its discard. The pass owns the work buffer and remembers the plane of its last successful call.
+// ---------------------------------------------------------------------------------------------------------------
+class QuadInterpolantsPass : public RenderPassBase {
+public:
+    struct FResourceParameters : public IRenderPassResourceCollection {};
+    struct FDrawParameters : public SceneInterpolantsPass::FDrawParameters {
+        void* QuadUV = nullptr;                                                 // float4 [H][QuadPitch], required
+        int QuadPitch = 0;                                                      // pixels per row, 0 = W
+    };
+    explicit QuadInterpolantsPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    ~QuadInterpolantsPass() override { Free(mWork); }
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { Free(mWork); mWorkBytes = 0; mQuadUV = nullptr; mQuadPitch = 0; }
+    void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override { mWidth = Width; mHeight = Height; }
+    void OnDestroyWindowSizeDependentResources() override { mWidth = mHeight = 0; mQuadUV = nullptr; mQuadPitch = 0; }
+    bool Reserve(int NumDraws) {
+        const size_t need = vqhip_scene_interpolants_work_bytes(NumDraws);
+        if (!need) return false;
+        if (need <= mWorkBytes) return true;
+        Free(mWork); mWorkBytes = 0;
+        mWork = Alloc(need);
+        if (mWork) mWorkBytes = need;
+        return mWork != nullptr;
+    }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        mQuadUV = nullptr; mQuadPitch = 0;
+        if (!p) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        const int numDraws = p->Draws ? (int)p->Draws->size() : 0;
+        if (!Reserve(numDraws)) { mStatus = VQHIP_ERR_HIP; return; }
+        vqhip_scene_quad_targets t = {};
+        t.planes.ip0 = p->Ip0; t.planes.ip1 = p->Ip1; t.planes.ip2 = p->Ip2; t.planes.svPositionCurr = p->SvPositionCurr; t.planes.svPositionPrev = p->SvPositionPrev;
+        t.quadUV = p->QuadUV; t.quad_pitch = p->QuadPitch;
+        mStatus = vqhip_scene_quad_interpolants(mCtx, p->Stream, numDraws ? p->Draws->data() : nullptr, numDraws, (int)mWidth, (int)mHeight, p->Owner, p->OwnerPitch, &t,
+                                                mWork, mWorkBytes);
+        if (mStatus == VQHIP_OK) { mQuadUV = p->QuadUV; mQuadPitch = p->QuadPitch ? p->QuadPitch : (int)mWidth; }
+    }
+    const void* GetWorkBuffer() const { return mWork; }
+    size_t GetWorkBytes() const { return mWorkBytes; }
+    const void* GetQuadUV() const { return mQuadUV; }            // nullptr until a call succeeded
+    int GetQuadPitch() const { return mQuadPitch; }              // pixels per row
+private:
+    void* mWork = nullptr; size_t mWorkBytes = 0;
+    const void* mQuadUV = nullptr; int mQuadPitch = 0;
+    unsigned mWidth = 0, mHeight = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// The lit draw over planes QuadInterpolantsPass wrote == PSMain with D3D's helper-lane derivatives (§7.20 Q2). One parameter block, three uses, each a _quad
+// producer: pGBufferOut given -> vqhip_gbuffer_from_materials_quad into the caller's planes (one 4x layer; vqhip_forward_lighting_msaa shades them);
+// pSceneNormalsOut given -> vqhip_scene_normals_from_materials_quad (the Z pre-pass's colour target); neither -> vqhip_forward_lighting_from_materials_quad
+// into the pass's own scene colour (RGBA16F), with the draw's other render targets when asked for. The quad-uv plane is taken from the resolve pass.
+// ---------------------------------------------------------------------------------------------------------------
+class QuadLitDrawPass : public RenderPassBase {
+public:
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        const QuadInterpolantsPass* pQuadInterpolants = nullptr;  // the resolve whose last call wrote *pInterpolants and the quad-uv plane
+        const vqhip_interpolants* pInterpolants = nullptr;
+        const vqhip_material* pMaterials = nullptr;
+        int NumMaterials = 0;
+        const vqhip_ssao* pScreenSpaceAO = nullptr;
+        const VQ_PerFrameData* pPerFrame = nullptr;
+        const VQ_PerViewLightingData* pPerView = nullptr;
+        const VQ_PointLight* pExtraPointLights = nullptr;
+        int NumExtraPointLights = 0;
+        const vqhip_envmap* pEnvironmentMap = nullptr;
+        const vqhip_shadowmaps* pShadowMaps = nullptr;
+        const vqhip_psmain_targets* pTargets = nullptr;          // the fused draw's other render targets, or nullptr
+        const vqhip_gbuffer* pGBufferOut = nullptr;              // one 4x layer's record planes instead of the lit frame
+        void* pSceneNormalsOut = nullptr;                        // Tex_SceneNormals (R10G10B10A2_UNORM, tightly packed) instead of the lit frame
+    };
+    explicit QuadLitDrawPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    ~QuadLitDrawPass() override { Free(mSceneColor); }
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { OnDestroyWindowSizeDependentResources(); }
+    void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override {
+        Free(mSceneColor);
+        mWidth = Width; mHeight = Height;
+        mSceneColor = Alloc((size_t)Width * Height * 8);
+    }
+    void OnDestroyWindowSizeDependentResources() override { Free(mSceneColor); mWidth = mHeight = 0; }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p || !p->pInterpolants || !p->pQuadInterpolants || !p->pQuadInterpolants->GetQuadUV() || (p->pGBufferOut && p->pSceneNormalsOut)) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        const void* quadUV = p->pQuadInterpolants->GetQuadUV();
+        const int quadPitch = p->pQuadInterpolants->GetQuadPitch();
+        if (p->pSceneNormalsOut) {
+            mStatus = vqhip_scene_normals_from_materials_quad(mCtx, p->Stream, p->pInterpolants, p->pMaterials, p->NumMaterials, p->pSceneNormalsOut,
+                                                              VQHIP_FMT_R10G10B10A2_UNORM, 0, quadUV, quadPitch);
+            return;
+        }
+        if (!p->pPerFrame) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        if (p->pGBufferOut) {
+            mStatus = vqhip_gbuffer_from_materials_quad(mCtx, p->Stream, p->pInterpolants, p->pMaterials, p->NumMaterials, p->pPerFrame->fAmbientLightingFactor,
+                                                        p->pScreenSpaceAO, p->pGBufferOut, quadUV, quadPitch);
+            return;
+        }
+        if (!mSceneColor) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        mStatus = vqhip_forward_lighting_from_materials_quad(mCtx, p->Stream, p->pInterpolants, p->pMaterials, p->NumMaterials, p->pScreenSpaceAO, p->pPerFrame, p->pPerView,
+                                                             p->pExtraPointLights, p->NumExtraPointLights, p->pEnvironmentMap, p->pShadowMaps, mSceneColor, (int)mWidth,
+                                                             VQHIP_FMT_RGBA16F, p->pTargets, quadUV, quadPitch);
+    }
+    void* GetSceneColor() const { return mSceneColor; }          // RGBA16F, width * height
+private:
+    void* mSceneColor = nullptr;
+    unsigned mWidth = 0, mHeight = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // Reflection denoiser, pass 1 == the "FFX DNSR Reproject" dispatch of ScreenSpaceReflectionsPass::RecordCommands: vqhip_ssr_reproject. Buffer roles as
 // ScreenSpaceReflections.cpp:1177-1198 binds them for frame index i: reads the surfaces of this frame and their history copies, TexRadiance[i] (what the march
 // wrote), TexRadiance[1 - i] (last frame's resolved radiance), the motion vectors, TexVariance[1 - i] and TexSampleCount[1 - i]; writes TexReprojectedRadiance,

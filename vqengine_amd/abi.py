@@ -269,6 +269,10 @@ class SceneInterpolantTargets(C.Structure):  # vqhip_scene_interpolant_targets
                 ("pitch", C.c_int32), ("sv_pitch", C.c_int32)]
 
 
+class SceneQuadTargets(C.Structure):  # vqhip_scene_quad_targets
+    _fields_ = [("planes", SceneInterpolantTargets), ("quadUV", C.c_void_p), ("quad_pitch", C.c_int32), ("pad_", C.c_int32)]
+
+
 class SceneDepthMaskedDraw(C.Structure):  # vqhip_scene_masked_depth_draw
     _fields_ = [("draw", SceneDepthDraw), ("material", C.POINTER(MaterialDesc))]
 
@@ -319,6 +323,7 @@ _chk(SceneDepthDraw, 48, matWorldViewProj=32, numInstances=40, cullMode=44)
 _chk(SceneDepthTargets, 96, primitive=8, coverage=16, layerPrimitive=48, layers=80, pitch=84, coverage_pitch=88, reserved=92)
 _chk(SceneSurfaceDraw, 72, matWorldViewProj=32, matWorld=40, matNormal=48, matWorldViewProjPrev=56, numInstances=64, materialIndex=68)
 _chk(SceneInterpolantTargets, 48, ip1=8, ip2=16, svPositionCurr=24, svPositionPrev=32, pitch=40, sv_pitch=44)
+_chk(SceneQuadTargets, 64, quadUV=48, quad_pitch=56, pad_=60)
 _chk(SceneDepthMaskedDraw, 56, material=48)
 _chk(ShadowMaskedDraw, 64, texDiffuseAlpha=56)
 _chk(ShadowMaskedView, 56, pitchBytes=8, dim=16, linearDepth=20, cameraPosition=24, farPlane=36, draws=40, numDraws=48)

@@ -120,6 +120,13 @@ def load_library():
         "vqhip_shadow_masked_depth_work_bytes": (sz, [C.c_uint64, C.c_uint64, i32, i32]),
         "vqhip_shadow_masked_depth": (i32, [vp, vp, C.POINTER(abi.ShadowMaskedView), i32, vp, sz]),
         "vqhip_scene_interpolants": (i32, [vp, vp, C.POINTER(abi.SceneSurfaceDraw), i32, i32, i32, vp, i32, C.POINTER(abi.SceneInterpolantTargets), vp, sz]),
+        "vqhip_scene_quad_interpolants": (i32, [vp, vp, C.POINTER(abi.SceneSurfaceDraw), i32, i32, i32, vp, i32, C.POINTER(abi.SceneQuadTargets), vp, sz]),
+        "vqhip_gbuffer_from_materials_quad": (i32, [vp, vp, C.POINTER(abi.Interpolants), C.POINTER(abi.MaterialDesc), i32, f32,
+                                                    C.POINTER(abi.SSAO), C.POINTER(abi.GBuffer), vp, i32]),
+        "vqhip_forward_lighting_from_materials_quad": (i32, [vp, vp, C.POINTER(abi.Interpolants), C.POINTER(abi.MaterialDesc), i32, C.POINTER(abi.SSAO),
+                                                             C.POINTER(abi.PerFrameData), C.POINTER(abi.PerViewLightingData), vp, i32,
+                                                             C.POINTER(abi.EnvMap), C.POINTER(abi.ShadowMaps), vp, i32, i32, C.POINTER(abi.PsmainTargets), vp, i32]),
+        "vqhip_scene_normals_from_materials_quad": (i32, [vp, vp, C.POINTER(abi.Interpolants), C.POINTER(abi.MaterialDesc), i32, vp, i32, i32, vp, i32]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -158,6 +165,7 @@ EXPORTED_SYMBOLS = [
     "vqhip_scene_depth", "vqhip_scene_depth_work_bytes",
     "vqhip_scene_interpolants", "vqhip_scene_interpolants_work_bytes",
     "vqhip_scene_masked_depth", "vqhip_scene_masked_depth_work_bytes", "vqhip_shadow_masked_depth", "vqhip_shadow_masked_depth_work_bytes",
+    "vqhip_scene_quad_interpolants", "vqhip_gbuffer_from_materials_quad", "vqhip_forward_lighting_from_materials_quad", "vqhip_scene_normals_from_materials_quad",
 ]
 
 
@@ -842,27 +850,41 @@ class Context:
     def scene_interpolants_prepared(self, draws, width, height, owner, sv=False, out=None, work=None):
         """The descriptors of a scene_interpolants call built once: returns (call, result) with call(stream=None) issuing vqhip_scene_interpolants on the same
         draws, owner plane and targets again. The tensors must stay alive and in place."""
+        return self._scene_interpolants_prepared("scene_interpolants", False, draws, width, height, owner, sv, out, work)
+
+    def scene_quad_interpolants(self, draws, width, height, owner, sv=False, out=None, work=None, stream=None):
+        """vqhip_scene_quad_interpolants (docs/DESIGN_DETAILS.md §7.20): scene_interpolants plus the plane `quad_uv`, cuda float32 [H, W, 4] = the owner primitive's
+        vertex uv at the helper lanes (i ^ 1, j) and (i, j ^ 1), for the _quad producers. out may hold a preallocated `quad_uv` (its row stride is its pitch)."""
+        call, res = self.scene_quad_interpolants_prepared(draws, width, height, owner, sv, out, work)
+        call(stream)
+        return res
+
+    def scene_quad_interpolants_prepared(self, draws, width, height, owner, sv=False, out=None, work=None):
+        """scene_interpolants_prepared for vqhip_scene_quad_interpolants"""
+        return self._scene_interpolants_prepared("scene_quad_interpolants", True, draws, width, height, owner, sv, out, work)
+
+    def _scene_interpolants_prepared(self, who_, quad, draws, width, height, owner, sv, out, work):
         draws, out = list(draws), dict(out or {})
         w, h = int(width), int(height)
         if not (1 <= w <= abi.SCENE_DEPTH_MAX_DIM and 1 <= h <= abi.SCENE_DEPTH_MAX_DIM):
-            raise ValueError(f"scene_interpolants: width and height must be 1..{abi.SCENE_DEPTH_MAX_DIM}")
+            raise ValueError(f"{who_}: width and height must be 1..{abi.SCENE_DEPTH_MAX_DIM}")
         if not (owner.is_cuda and owner.dtype == torch.int32 and tuple(owner.shape) == (h, w) and owner.stride(1) == 1 and owner.stride(0) >= w):
-            raise ValueError(f"scene_interpolants: owner: expected cuda int32 {(h, w)} with unit column stride, got {tuple(owner.shape)} {owner.dtype} strides {owner.stride()}")
+            raise ValueError(f"{who_}: owner: expected cuda int32 {(h, w)} with unit column stride, got {tuple(owner.shape)} {owner.dtype} strides {owner.stride()}")
         res, pitches = {}, {}
-        for key in ("ip0", "ip1", "ip2") + (("sv_curr", "sv_prev") if sv else ()):
+        for key in ("ip0", "ip1", "ip2") + (("sv_curr", "sv_prev") if sv else ()) + (("quad_uv",) if quad else ()):
             t = out.get(key)
             if t is None:
                 t = torch.empty((h, w, 4), dtype=torch.float32, device=self.device)
             if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.stride(2) == 1 and t.stride(1) == 4 and t.stride(0) % 4 == 0
                     and t.stride(0) >= 4 * w):
-                raise ValueError(f"scene_interpolants: {key}: expected cuda float32 {(h, w, 4)} with dense pixels, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+                raise ValueError(f"{who_}: {key}: expected cuda float32 {(h, w, 4)} with dense pixels, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
             res[key] = t
             pitches.setdefault(key[:2], set()).add(t.stride(0) // 4)
         if any(len(p) != 1 for p in pitches.values()):
-            raise ValueError("scene_interpolants: ip0, ip1 and ip2 share one pitch in pixels, sv_curr and sv_prev another")
+            raise ValueError(f"{who_}: ip0, ip1 and ip2 share one pitch in pixels, sv_curr and sv_prev another")
         cdraws = (abi.SceneSurfaceDraw * max(1, len(draws)))()
         for j, dr in enumerate(draws):
-            who = f"scene_interpolants: draw {j}"
+            who = f"{who_}: draw {j}"
             p, ix = dr.vertices, dr.indices
             if not (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and p.shape[1] >= 11 and p.stride(1) == 1 and p.stride(0) >= p.shape[1]):
                 raise ValueError(f"{who}: vertices: expected cuda float32 [V, k >= 11] with unit column stride")
@@ -890,7 +912,7 @@ class Context:
         if work is None:
             work = torch.empty((need,), dtype=torch.uint8, device=self.device)
         if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.numel() >= need):
-            raise ValueError(f"scene_interpolants: work: expected a contiguous cuda uint8 tensor of at least {need} bytes")
+            raise ValueError(f"{who_}: work: expected a contiguous cuda uint8 tensor of at least {need} bytes")
         res["work"] = work
         tg = abi.SceneInterpolantTargets()
         tg.ip0, tg.ip1, tg.ip2 = res["ip0"].data_ptr(), res["ip1"].data_ptr(), res["ip2"].data_ptr()
@@ -898,10 +920,14 @@ class Context:
         if sv:
             tg.svPositionCurr, tg.svPositionPrev, tg.sv_pitch = res["sv_curr"].data_ptr(), res["sv_prev"].data_ptr(), pitches["sv"].pop()
         keep = (draws, res, owner)
+        fn, arg = self.lib.vqhip_scene_interpolants, tg
+        if quad:
+            arg = abi.SceneQuadTargets()
+            arg.planes, arg.quadUV, arg.quad_pitch = tg, res["quad_uv"].data_ptr(), pitches["qu"].pop()
+            fn = self.lib.vqhip_scene_quad_interpolants
 
         def call(stream=None, _keep=keep):
-            self._ck(self.lib.vqhip_scene_interpolants(self._h, self._stream(stream), cdraws, len(draws), w, h, _ptr(owner), owner.stride(0), C.byref(tg),
-                                                       _ptr(work), work.numel()))
+            self._ck(fn(self._h, self._stream(stream), cdraws, len(draws), w, h, _ptr(owner), owner.stride(0), C.byref(arg), _ptr(work), work.numel()))
         return call, res
 
     def msaa_resolve_surfaces(self, depth_ms, coverage=None, normals=None, normals_fmt=abi.FMT_R10G10B10A2_UNORM, roughness=None, background=None,
@@ -1068,7 +1094,33 @@ class Context:
         self._ck(self.lib.vqhip_mip_chain_box_rgba8(self._h, self._stream(stream), _ptr(chain), w, h, n))
         return chain, n
 
-    def gbuffer_from_materials(self, ip, materials, ambient, ssao=None, out=None, stream=None):
+    def _quad_plane(self, quad_uv, h, w, who):
+        """(pointer, pitch in pixels) of a quad_uv plane for the _quad producers: cuda float32 [H, W, 4] with dense pixels; the row stride is the pitch"""
+        t = quad_uv
+        if not (t is not None and t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.stride(2) == 1 and t.stride(1) == 4
+                and t.stride(0) % 4 == 0 and t.stride(0) >= 4 * w):
+            raise ValueError(f"{who}: quad_uv: expected cuda float32 {(h, w, 4)} with dense pixels (the quad_uv plane of scene_quad_interpolants)")
+        return C.c_void_p(t.data_ptr()), t.stride(0) // 4
+
+    def gbuffer_from_materials_quad(self, ip, materials, ambient, quad_uv, ssao=None, out=None, stream=None):
+        """vqhip_gbuffer_from_materials_quad (docs/DESIGN_DETAILS.md §7.20): gbuffer_from_materials with the uv derivatives taken from the helper lanes in
+        `quad_uv` (scene_quad_interpolants' plane) instead of the planes' neighbours"""
+        return self.gbuffer_from_materials(ip, materials, ambient, ssao, out, stream, _quad=quad_uv)
+
+    def scene_normals_from_materials_quad(self, ip, materials, quad_uv, out_fmt=abi.FMT_R10G10B10A2_UNORM, out=None, stream=None):
+        """vqhip_scene_normals_from_materials_quad: scene_normals_from_materials with helper-lane derivatives"""
+        return self.scene_normals_from_materials(ip, materials, out_fmt, out, stream, _quad=quad_uv)
+
+    def forward_lighting_from_materials_quad(self, ip, materials, per_frame, per_view, quad_uv, albedo_fmt=None, motion_fmt=None, sv_curr=None, sv_prev=None, **kw):
+        """vqhip_forward_lighting_from_materials_quad: forward_lighting_from_materials with helper-lane derivatives. With albedo_fmt or motion_fmt the draw's
+        other render targets are written too and (out, albedo_metallic, motion_vectors) is returned, as by forward_lighting_from_materials_mrt; else `out`."""
+        if albedo_fmt is None and motion_fmt is None:
+            return self.forward_lighting_from_materials(ip, materials, per_frame, per_view, _quad=quad_uv, **kw)
+        h, w = ip[0].shape[0], ip[0].shape[1]
+        t, albedo, motion = self._psmain_targets(h, w, albedo_fmt, motion_fmt, sv_curr, sv_prev, stream=kw.get("stream"))
+        return self.forward_lighting_from_materials(ip, materials, per_frame, per_view, _targets=t, _quad=quad_uv, **kw), albedo, motion
+
+    def gbuffer_from_materials(self, ip, materials, ambient, ssao=None, out=None, stream=None, _quad=None):
         """ip: 3 float32 cuda tensors [H,W,4] (vqhip_interpolants planes); materials: ctypes array of abi.MaterialDesc whose
         texture pointers are device pointers; ssao: uint8 cuda [H,W] or None. Returns the 4 G-buffer planes."""
         for i, t in enumerate(ip):
@@ -1086,11 +1138,12 @@ class Context:
                 raise ValueError("ssao: expected contiguous cuda uint8 [H,W]")
             s = abi.SSAO(ssao.data_ptr(), ssao.shape[1], ssao.shape[0])
         n = len(materials) if materials is not None else 0
-        self._ck(self.lib.vqhip_gbuffer_from_materials(self._h, self._stream(stream), C.byref(inter), materials if n else None, n,
-                                                       float(ambient), C.byref(s) if s is not None else None, C.byref(gbuf)))
+        args = (self._h, self._stream(stream), C.byref(inter), materials if n else None, n, float(ambient), C.byref(s) if s is not None else None, C.byref(gbuf))
+        self._ck(self.lib.vqhip_gbuffer_from_materials(*args) if _quad is None
+                 else self.lib.vqhip_gbuffer_from_materials_quad(*args, *self._quad_plane(_quad, h, w, "gbuffer_from_materials_quad")))
         return out
 
-    def scene_normals_from_materials(self, ip, materials, out_fmt=abi.FMT_R10G10B10A2_UNORM, out=None, stream=None):
+    def scene_normals_from_materials(self, ip, materials, out_fmt=abi.FMT_R10G10B10A2_UNORM, out=None, stream=None, _quad=None):
         """The Z pre-pass's colour target (DepthPrePass.hlsl:PSMain): Tex_SceneNormals as int32 [H,W] (R10G10B10A2_UNORM bits; torch has no uint32) or
         float32 [H,W,4]. ip / materials as for gbuffer_from_materials (ip2 is not modified)."""
         for i, t in enumerate(ip):
@@ -1101,7 +1154,9 @@ class Context:
                    else empty_image(h, w, FMT_RGBA32F, self.device))
         inter = abi.Interpolants(ip[0].data_ptr(), ip[1].data_ptr(), ip[2].data_ptr(), w, h, w)
         n = len(materials) if materials is not None else 0
-        self._ck(self.lib.vqhip_scene_normals_from_materials(self._h, self._stream(stream), C.byref(inter), materials if n else None, n, _ptr(out), out_fmt, w))
+        args = (self._h, self._stream(stream), C.byref(inter), materials if n else None, n, _ptr(out), out_fmt, w)
+        self._ck(self.lib.vqhip_scene_normals_from_materials(*args) if _quad is None
+                 else self.lib.vqhip_scene_normals_from_materials_quad(*args, *self._quad_plane(_quad, h, w, "scene_normals_from_materials_quad")))
         return out
 
     def forward_lighting_from_materials_mrt(self, ip, materials, per_frame, per_view, albedo_fmt=FMT_RGBA16F, motion_fmt=None, sv_curr=None, sv_prev=None,
@@ -1112,7 +1167,7 @@ class Context:
         return self.forward_lighting_from_materials(ip, materials, per_frame, per_view, _targets=t, **kw), albedo, motion
 
     def forward_lighting_from_materials(self, ip, materials, per_frame, per_view, ssao=None, out=None, out_fmt=FMT_RGBA16F, extra_point=None,
-                                        env=None, shadow=None, stream=None, _targets=None):
+                                        env=None, shadow=None, stream=None, _targets=None, _quad=None):
         """PSMain in one kernel: gbuffer_from_materials(ip, materials, per_frame.fAmbientLightingFactor, ssao) + forward_lighting, the G-buffer
         record never leaving registers. Same bits as the two calls."""
         for i, t in enumerate(ip):
@@ -1134,6 +1189,10 @@ class Context:
         args = (self._h, self._stream(stream), C.byref(inter), materials if n else None, n, C.byref(s) if s is not None else None,
                 C.byref(per_frame), C.byref(per_view), extra_ptr, n_extra, C.byref(env) if env is not None else None,
                 C.byref(shadow) if shadow is not None else None, _ptr(out), out.shape[1], out_fmt)
+        if _quad is not None:
+            self._ck(self.lib.vqhip_forward_lighting_from_materials_quad(*args, C.byref(_targets) if _targets is not None else None,
+                                                                         *self._quad_plane(_quad, h, w, "forward_lighting_from_materials_quad")))
+            return out
         self._ck(self.lib.vqhip_forward_lighting_from_materials(*args) if _targets is None
                  else self.lib.vqhip_forward_lighting_from_materials_mrt(*args, C.byref(_targets)))
         return out

@@ -947,18 +947,41 @@ static size_t fillGbufConstants(vqhip_ctx* ctx, int slot, const vqhip_material* 
     return offsetof(GbufConstants, mats) + (size_t)numMaterials * sizeof(vqhip_material);
 }
 
-int vqhip_gbuffer_from_materials(vqhip_ctx* ctx, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
-                                 float fAmbientLightingFactor, const vqhip_ssao* ssao, const vqhip_gbuffer* out) {
+// The quad-uv plane of the _quad producers (docs/DESIGN_DETAILS.md §7.20 Q2), validated after validateProducer: *bytes = the extent the kernel reads
+static int validateQuadPlane(vqhip_ctx* ctx, const std::string& w, const vqhip_interpolants* in, const void* quadUV, int quad_pitch_px, QuadPlane* qp, size_t* bytes) {
+    if (!quadUV) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quadUV is NULL");
+    if ((uintptr_t)quadUV % 16) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quadUV is not 16-byte aligned");
+    if (quad_pitch_px < 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": negative quad_pitch_px");
+    const int pitch = quad_pitch_px ? quad_pitch_px : in->row_pitch_px;
+    if (pitch < in->width) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quad_pitch_px below the width");
+    if ((uint64_t)pitch * in->height * 16u >= (1ull << 32) || pitch >= (1 << 24))
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": a plane must be smaller than 4 GiB (32-bit offsets in the kernel)");
+    qp->uv = const_cast<void*>(quadUV); qp->pitch = (uint32_t)pitch;
+    *bytes = ((size_t)(in->height - 1) * pitch + in->width) * 16;
+    return VQHIP_OK;
+}
+// the extent of an output plane of `px` bytes per pixel
+static size_t planeBytes(const vqhip_interpolants* in, int pitch, size_t px) { return ((size_t)(in->height - 1) * pitch + in->width) * px; }
+
+// vqhip_gbuffer_from_materials (quad == false) and its _quad form: one body, the launch differs
+static int gbufferFromMaterials(vqhip_ctx* ctx, const std::string& w, bool quad, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
+                                float fAmbientLightingFactor, const vqhip_ssao* ssao, const vqhip_gbuffer* out, const void* quadUV, int quad_pitch_px) {
     vqk::Range range_("Geometry");                       // :1723 (surface assembly half of the lit draws)
-    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "gbuffer_from_materials: ctx is NULL");
-    CTX_GUARD(ctx, "gbuffer_from_materials");
-    if (!out || !out->gb0 || !out->gb1 || !out->gb2 || !out->gb3) return fail(ctx, VQHIP_ERR_INVALID_ARG, "gbuffer_from_materials: NULL plane");
-    int rc = validateProducer(ctx, "gbuffer_from_materials", in, materials, numMaterials, ssao);
+    if (!out || !out->gb0 || !out->gb1 || !out->gb2 || !out->gb3) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": NULL plane");
+    int rc = validateProducer(ctx, w.c_str(), in, materials, numMaterials, ssao);
     if (rc) return rc;
     if (out->width != in->width || out->height != in->height || out->row_pitch_px < in->width)
-        return fail(ctx, VQHIP_ERR_INVALID_ARG, "gbuffer_from_materials: bad dimensions / pitch");
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": bad dimensions / pitch");
     if ((uint64_t)out->row_pitch_px * out->height * 16u >= (1ull << 32) || out->row_pitch_px >= (1 << 24))
-        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "gbuffer_from_materials: a plane must be smaller than 4 GiB (32-bit offsets in the kernel)");
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": a plane must be smaller than 4 GiB (32-bit offsets in the kernel)");
+    QuadPlane qp = { nullptr, 0 };
+    if (quad) {
+        size_t qb;
+        if ((rc = validateQuadPlane(ctx, w, in, quadUV, quad_pitch_px, &qp, &qb)) != VQHIP_OK) return rc;
+        const void* const outs[5] = { out->gb0, out->gb1, out->gb2, out->gb3, in->ip2 };     // ip2.w receives the discard's -1
+        for (int k = 0; k < 5; ++k)
+            if (rangesOverlap(quadUV, qb, outs[k], planeBytes(in, k < 4 ? out->row_pitch_px : in->row_pitch_px, 16))) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quadUV overlaps an output");
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     int slot;
@@ -972,24 +995,40 @@ int vqhip_gbuffer_from_materials(vqhip_ctx* ctx, void* stream, const vqhip_inter
     a.gb0 = (float4*)out->gb0; a.gb1 = (float4*)out->gb1; a.gb2 = (float4*)out->gb2; a.gb3 = (float4*)out->gb3;
     a.gc = (const GbufConstants*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
     a.width = in->width; a.height = in->height; a.pitch = in->row_pitch_px; a.outPitch = out->row_pitch_px;
-    hipError_t e = launch_gbuffer_from_materials(st, a);
-    if (e != hipSuccess) return failHip(ctx, e, "gbuffer_from_materials launch");
+    hipError_t e = quad ? launch_gbuffer_from_materials_quad(st, a, qp) : launch_gbuffer_from_materials(st, a);
+    if (e != hipSuccess) return failHip(ctx, e, (w + " launch").c_str());
     return releaseSlot(ctx, slot, st);
+}
+int vqhip_gbuffer_from_materials(vqhip_ctx* ctx, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
+                                 float fAmbientLightingFactor, const vqhip_ssao* ssao, const vqhip_gbuffer* out) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "gbuffer_from_materials: ctx is NULL");
+    CTX_GUARD(ctx, "gbuffer_from_materials");
+    return gbufferFromMaterials(ctx, "gbuffer_from_materials", false, stream, in, materials, numMaterials, fAmbientLightingFactor, ssao, out, nullptr, 0);
+}
+int vqhip_gbuffer_from_materials_quad(vqhip_ctx* ctx, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
+                                      float fAmbientLightingFactor, const vqhip_ssao* ssao, const vqhip_gbuffer* out, const void* quadUV, int quad_pitch_px) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "gbuffer_from_materials_quad: ctx is NULL");
+    CTX_GUARD(ctx, "gbuffer_from_materials_quad");
+    return gbufferFromMaterials(ctx, "gbuffer_from_materials_quad", true, stream, in, materials, numMaterials, fAmbientLightingFactor, ssao, out, quadUV, quad_pitch_px);
 }
 
 // The colour target of the Z pre-pass (DepthPrePass.hlsl:PSMain :153-171; VQRenderer::RenderDepthPrePass, SceneRendering.cpp:1264-1360): Tex_SceneNormals.
-int vqhip_scene_normals_from_materials(vqhip_ctx* ctx, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
-                                       void* out, vqhip_format outFmt, int out_row_pitch_px) {
+static int sceneNormalsFromMaterials(vqhip_ctx* ctx, const std::string& w, bool quad, void* stream, const vqhip_interpolants* in, const vqhip_material* materials,
+                                     int numMaterials, void* out, vqhip_format outFmt, int out_row_pitch_px, const void* quadUV, int quad_pitch_px) {
     vqk::Range range_("RenderDepthPrePass");             // SceneRendering.cpp:1273
-    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "scene_normals_from_materials: ctx is NULL");
-    CTX_GUARD(ctx, "scene_normals_from_materials");
-    if (!out) return fail(ctx, VQHIP_ERR_INVALID_ARG, "scene_normals_from_materials: out is NULL");
+    if (!out) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": out is NULL");
     if (outFmt != VQHIP_FMT_R10G10B10A2_UNORM && outFmt != VQHIP_FMT_RGBA32F)
-        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "scene_normals_from_materials: outFmt must be R10G10B10A2_UNORM or RGBA32F");
-    int rc = validateProducer(ctx, "scene_normals_from_materials", in, materials, numMaterials, nullptr);
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": outFmt must be R10G10B10A2_UNORM or RGBA32F");
+    int rc = validateProducer(ctx, w.c_str(), in, materials, numMaterials, nullptr);
     if (rc) return rc;
     const int pitch = out_row_pitch_px ? out_row_pitch_px : in->width;
-    if (pitch < in->width) return fail(ctx, VQHIP_ERR_INVALID_ARG, "scene_normals_from_materials: bad output pitch");
+    if (pitch < in->width) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": bad output pitch");
+    QuadPlane qp = { nullptr, 0 };
+    if (quad) {
+        size_t qb;
+        if ((rc = validateQuadPlane(ctx, w, in, quadUV, quad_pitch_px, &qp, &qb)) != VQHIP_OK) return rc;
+        if (rangesOverlap(quadUV, qb, out, planeBytes(in, pitch, outFmt == VQHIP_FMT_RGBA32F ? 16 : 4))) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quadUV overlaps an output");
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     int slot;
@@ -1003,9 +1042,21 @@ int vqhip_scene_normals_from_materials(vqhip_ctx* ctx, void* stream, const vqhip
     a.gb0 = a.gb1 = a.gb2 = a.gb3 = nullptr;
     a.gc = (const GbufConstants*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
     a.width = in->width; a.height = in->height; a.pitch = in->row_pitch_px; a.outPitch = pitch;
-    hipError_t e = launch_scene_normals_from_materials(st, a, out, outFmt);
-    if (e != hipSuccess) return failHip(ctx, e, "scene_normals_from_materials launch");
+    hipError_t e = quad ? launch_scene_normals_from_materials_quad(st, a, out, outFmt, qp) : launch_scene_normals_from_materials(st, a, out, outFmt);
+    if (e != hipSuccess) return failHip(ctx, e, (w + " launch").c_str());
     return releaseSlot(ctx, slot, st);
+}
+int vqhip_scene_normals_from_materials(vqhip_ctx* ctx, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
+                                       void* out, vqhip_format outFmt, int out_row_pitch_px) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "scene_normals_from_materials: ctx is NULL");
+    CTX_GUARD(ctx, "scene_normals_from_materials");
+    return sceneNormalsFromMaterials(ctx, "scene_normals_from_materials", false, stream, in, materials, numMaterials, out, outFmt, out_row_pitch_px, nullptr, 0);
+}
+int vqhip_scene_normals_from_materials_quad(vqhip_ctx* ctx, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
+                                            void* out, vqhip_format outFmt, int out_row_pitch_px, const void* quadUV, int quad_pitch_px) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "scene_normals_from_materials_quad: ctx is NULL");
+    CTX_GUARD(ctx, "scene_normals_from_materials_quad");
+    return sceneNormalsFromMaterials(ctx, "scene_normals_from_materials_quad", true, stream, in, materials, numMaterials, out, outFmt, out_row_pitch_px, quadUV, quad_pitch_px);
 }
 
 // PSMain as the engine runs it (ForwardLighting.hlsl:226-380, the lit draws of RenderSceneColor, SceneRendering.cpp:1619-1760): interpolants +
@@ -1020,22 +1071,30 @@ int vqhip_forward_lighting_from_materials(vqhip_ctx* ctx, void* stream, const vq
                                                      out, out_row_pitch_px, outFmt, nullptr);
 }
 
-int vqhip_forward_lighting_from_materials_mrt(vqhip_ctx* ctx, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
+static int forwardFromMaterials(vqhip_ctx* ctx, const std::string& w, bool quad, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
         const vqhip_ssao* ssao, const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
         const VQ_PointLight* extraPoint, int numExtraPoint, const vqhip_envmap* env, const vqhip_shadowmaps* sm,
-        void* out, int out_row_pitch_px, vqhip_format outFmt, const vqhip_psmain_targets* targets) {
+        void* out, int out_row_pitch_px, vqhip_format outFmt, const vqhip_psmain_targets* targets, const void* quadUV, int quad_pitch_px) {
     vqk::Range range_("RenderSceneColor");
-    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "forward_lighting_from_materials: ctx is NULL");
-    CTX_GUARD(ctx, "forward_lighting_from_materials");
-    if (!out) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_from_materials: out is NULL");
-    int rc = validateProducer(ctx, "forward_lighting_from_materials", in, materials, numMaterials, ssao);
+    if (!out) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": out is NULL");
+    int rc = validateProducer(ctx, w.c_str(), in, materials, numMaterials, ssao);
     if (rc) return rc;
-    if (out_row_pitch_px < in->width) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_from_materials: bad output pitch");
+    if (out_row_pitch_px < in->width) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": bad output pitch");
     bool casters = false;
-    rc = validateLighting(ctx, "forward_lighting_from_materials", perFrame, perView, extraPoint, numExtraPoint, env, sm, outFmt, &casters);
+    rc = validateLighting(ctx, w.c_str(), perFrame, perView, extraPoint, numExtraPoint, env, sm, outFmt, &casters);
     if (rc) return rc;
     MrtArgs mrt;
-    if ((rc = fillMrt(ctx, "forward_lighting_from_materials", targets, in->width, &mrt)) != VQHIP_OK) return rc;
+    if ((rc = fillMrt(ctx, w.c_str(), targets, in->width, &mrt)) != VQHIP_OK) return rc;
+    QuadPlane qp = { nullptr, 0 };
+    if (quad) {
+        size_t qb;
+        if ((rc = validateQuadPlane(ctx, w, in, quadUV, quad_pitch_px, &qp, &qb)) != VQHIP_OK) return rc;
+        const bool over = rangesOverlap(quadUV, qb, out, planeBytes(in, out_row_pitch_px, outFmt == VQHIP_FMT_RGBA32F ? 16 : 8)) ||
+                          rangesOverlap(quadUV, qb, in->ip2, planeBytes(in, in->row_pitch_px, 16)) ||      // ip2.w receives the discard's -1
+                          rangesOverlap(quadUV, qb, mrt.albedo, planeBytes(in, mrt.albedoPitch, mrt.albedoF32 ? 16 : 8)) ||
+                          rangesOverlap(quadUV, qb, mrt.motion, planeBytes(in, mrt.motionPitch, mrt.motionF32 ? 8 : 4));
+        if (over) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quadUV overlaps an output");
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     int slotG, slotF;
@@ -1048,11 +1107,30 @@ int vqhip_forward_lighting_from_materials_mrt(vqhip_ctx* ctx, void* stream, cons
     a.gb0 = a.gb1 = a.gb2 = a.gb3 = nullptr;
     a.gc = (const GbufConstants*)(ctx->devRing + (size_t)slotG * kConstSlotBytes);
     a.width = in->width; a.height = in->height; a.pitch = in->row_pitch_px; a.outPitch = 0;
-    hipError_t e = launch_forward_from_materials(st, a, (const FrameConstants*)(ctx->devRing + (size_t)slotF * kConstSlotBytes), env != nullptr, casters,
-                                                 out, out_row_pitch_px, outFmt, ctx->arithDxc, ctx->opt, mrt);
-    if (e != hipSuccess) return failHip(ctx, e, "forward_lighting_from_materials launch");
+    const FrameConstants* fc = (const FrameConstants*)(ctx->devRing + (size_t)slotF * kConstSlotBytes);
+    hipError_t e = quad ? launch_forward_from_materials_quad(st, a, fc, env != nullptr, casters, out, out_row_pitch_px, outFmt, ctx->arithDxc, ctx->opt, mrt, qp)
+                        : launch_forward_from_materials(st, a, fc, env != nullptr, casters, out, out_row_pitch_px, outFmt, ctx->arithDxc, ctx->opt, mrt);
+    if (e != hipSuccess) return failHip(ctx, e, (w + " launch").c_str());
     if ((rc = releaseSlot(ctx, slotG, st)) != VQHIP_OK) return rc;
     return releaseSlot(ctx, slotF, st);
+}
+int vqhip_forward_lighting_from_materials_mrt(vqhip_ctx* ctx, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
+        const vqhip_ssao* ssao, const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
+        const VQ_PointLight* extraPoint, int numExtraPoint, const vqhip_envmap* env, const vqhip_shadowmaps* sm,
+        void* out, int out_row_pitch_px, vqhip_format outFmt, const vqhip_psmain_targets* targets) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "forward_lighting_from_materials: ctx is NULL");
+    CTX_GUARD(ctx, "forward_lighting_from_materials");
+    return forwardFromMaterials(ctx, "forward_lighting_from_materials", false, stream, in, materials, numMaterials, ssao, perFrame, perView, extraPoint, numExtraPoint, env, sm,
+                                out, out_row_pitch_px, outFmt, targets, nullptr, 0);
+}
+int vqhip_forward_lighting_from_materials_quad(vqhip_ctx* ctx, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
+        const vqhip_ssao* ssao, const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
+        const VQ_PointLight* extraPoint, int numExtraPoint, const vqhip_envmap* env, const vqhip_shadowmaps* sm,
+        void* out, int out_row_pitch_px, vqhip_format outFmt, const vqhip_psmain_targets* targets, const void* quadUV, int quad_pitch_px) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "forward_lighting_from_materials_quad: ctx is NULL");
+    CTX_GUARD(ctx, "forward_lighting_from_materials_quad");
+    return forwardFromMaterials(ctx, "forward_lighting_from_materials_quad", true, stream, in, materials, numMaterials, ssao, perFrame, perView, extraPoint, numExtraPoint, env, sm,
+                                out, out_row_pitch_px, outFmt, targets, quadUV, quad_pitch_px);
 }
 
 // ---- skydome ------------------------------------------------------------------------
@@ -2226,13 +2304,14 @@ size_t vqhip_scene_interpolants_work_bytes(int numDraws) {
     return align256((size_t)(numDraws > 0 ? numDraws : 1) * sizeof(SurfaceJob));
 }
 
-int vqhip_scene_interpolants(vqhip_ctx* ctx, void* stream, const vqhip_scene_surface_draw* draws, int numDraws, int width, int height,
-                             const uint32_t* owner, int owner_pitch_px, const vqhip_scene_interpolant_targets* out, void* work, size_t workBytes) {
+// vqhip_scene_interpolants (quadOut == NULL) and vqhip_scene_quad_interpolants (§7.20 Q1): one body, the launch differs
+static int sceneInterpolants(vqhip_ctx* ctx, const std::string& w, void* stream, const vqhip_scene_surface_draw* draws, int numDraws, int width, int height,
+                             const uint32_t* owner, int owner_pitch_px, const vqhip_scene_interpolant_targets* out, const vqhip_scene_quad_targets* quadOut,
+                             void* work, size_t workBytes) {
     vqk::Range range_("RenderSceneColor");
-    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "scene_interpolants: ctx is NULL");
-    CTX_GUARD(ctx, "scene_interpolants");
-    auto bad = [&](const std::string& m) { return fail(ctx, VQHIP_ERR_INVALID_ARG, "scene_interpolants: " + m); };
+    auto bad = [&](const std::string& m) { return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": " + m); };
     if (!out || !out->ip0 || !out->ip1 || !out->ip2 || !owner || !work) return bad("NULL argument (out, ip0, ip1, ip2, owner or work)");
+    if (quadOut && !quadOut->quadUV) return bad("quadUV is NULL");
     if (numDraws < 0 || (numDraws > 0 && !draws)) return bad("numDraws < 0, or draws is NULL");
     if (!out->svPositionCurr != !out->svPositionPrev) return bad("svPositionCurr and svPositionPrev: both or neither");
     const bool sv = out->svPositionCurr != nullptr;
@@ -2240,9 +2319,11 @@ int vqhip_scene_interpolants(vqhip_ctx* ctx, void* stream, const vqhip_scene_sur
     if (out->pitch < 0 || out->sv_pitch < 0 || owner_pitch_px < 0) return bad("negative pitch");
     const size_t pitch = out->pitch ? (size_t)out->pitch : (size_t)width, svPitch = out->sv_pitch ? (size_t)out->sv_pitch : (size_t)width;
     const size_t ownerPitch = owner_pitch_px ? (size_t)owner_pitch_px : (size_t)width;
-    if (pitch < (size_t)width || svPitch < (size_t)width || ownerPitch < (size_t)width) return bad("a pitch below width");
-    void* const planes[5] = { out->ip0, out->ip1, out->ip2, out->svPositionCurr, out->svPositionPrev };
-    for (int k = 0; k < 5; ++k) if ((uintptr_t)planes[k] % 16) return bad("a target is not 16-byte aligned");
+    if (quadOut && quadOut->quad_pitch < 0) return bad("negative pitch");
+    const size_t quadPitch = quadOut && quadOut->quad_pitch ? (size_t)quadOut->quad_pitch : (size_t)width;
+    if (pitch < (size_t)width || svPitch < (size_t)width || ownerPitch < (size_t)width || quadPitch < (size_t)width) return bad("a pitch below width");
+    void* const planes[6] = { out->ip0, out->ip1, out->ip2, out->svPositionCurr, out->svPositionPrev, quadOut ? quadOut->quadUV : nullptr };
+    for (int k = 0; k < 6; ++k) if ((uintptr_t)planes[k] % 16) return bad("a target is not 16-byte aligned");
     if ((uintptr_t)owner % 4) return bad("owner must be 4-byte aligned");
     if ((uintptr_t)work % 256) return bad("work must be 256-byte aligned");
     uint64_t totalTris = 0;
@@ -2263,17 +2344,19 @@ int vqhip_scene_interpolants(vqhip_ctx* ctx, void* stream, const vqhip_scene_sur
             return badDraw("positions / matrices must be 4-byte aligned, indices aligned to their size");
         if (D.mesh.numIndices) { totalTris += (uint64_t)(D.mesh.numIndices / 3) * D.numInstances; ++numJobs; }
     }
-    if (totalTris >= kSceneMaxTriangles) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "scene_interpolants: 2^29 or more instanced triangles in one call");
-    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "scene_interpolants: more than 20000 draws in one call");
+    if (totalTris >= kSceneMaxTriangles) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": 2^29 or more instanced triangles in one call");
+    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": more than 20000 draws in one call");
     const size_t need = vqhip_scene_interpolants_work_bytes(numDraws);
     if (workBytes < need) return bad("workBytes below vqhip_scene_interpolants_work_bytes(numDraws)");
     const size_t rows = (size_t)(height - 1);
     const size_t ownerBytes = (rows * ownerPitch + width) * 4;
-    for (int k = 0; k < 5; ++k) {
+    const size_t quadBytes = (rows * quadPitch + width) * 16;
+    for (int k = 0; k < 6; ++k) {
         if (!planes[k]) continue;
-        const size_t bytes = (rows * (k < 3 ? pitch : svPitch) + width) * 16;
+        const size_t bytes = k == 5 ? quadBytes : (rows * (k < 3 ? pitch : svPitch) + width) * 16;
         if (rangesOverlap(work, need, planes[k], bytes)) return bad("an output overlaps the work buffer");
         if (rangesOverlap(owner, ownerBytes, planes[k], bytes)) return bad("an output overlaps the owner plane");
+        if (k < 5 && rangesOverlap(planes[5], quadBytes, planes[k], bytes)) return bad("quadUV overlaps another output");
     }
 
     SceneInterpArgs a;
@@ -2306,12 +2389,27 @@ int vqhip_scene_interpolants(vqhip_ctx* ctx, void* stream, const vqhip_scene_sur
         }
         if (int rc = commitSlot(ctx, slot, sizeof(SurfaceJob) * n, st)) return rc;
         hipError_t e = launch_table_copy(st, ctx->devRing + (size_t)slot * kConstSlotBytes, table + done, (uint32_t)(n * (sizeof(SurfaceJob) / 16)));
-        if (e != hipSuccess) return failHip(ctx, e, "scene_interpolants table-copy launch");
+        if (e != hipSuccess) return failHip(ctx, e, (w + " table-copy launch").c_str());
         if (int rc = releaseSlot(ctx, slot, st)) return rc;
         left -= n; done += n;
     }
-    hipError_t e = launch_scene_interpolants(st, a, table, ctx->opt.interpForm != 1);        // default: the wave form
-    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "scene_interpolants launch");
+    const bool waveForm = ctx->opt.interpForm != 1;                                           // default: the wave form
+    const QuadPlane qp = { planes[5], (uint32_t)quadPitch };
+    hipError_t e = quadOut ? launch_scene_quad_interpolants(st, a, table, waveForm, qp) : launch_scene_interpolants(st, a, table, waveForm);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (w + " launch").c_str());
+}
+int vqhip_scene_interpolants(vqhip_ctx* ctx, void* stream, const vqhip_scene_surface_draw* draws, int numDraws, int width, int height,
+                             const uint32_t* owner, int owner_pitch_px, const vqhip_scene_interpolant_targets* out, void* work, size_t workBytes) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "scene_interpolants: ctx is NULL");
+    CTX_GUARD(ctx, "scene_interpolants");
+    return sceneInterpolants(ctx, "scene_interpolants", stream, draws, numDraws, width, height, owner, owner_pitch_px, out, nullptr, work, workBytes);
+}
+int vqhip_scene_quad_interpolants(vqhip_ctx* ctx, void* stream, const vqhip_scene_surface_draw* draws, int numDraws, int width, int height,
+                                  const uint32_t* owner, int owner_pitch_px, const vqhip_scene_quad_targets* out, void* work, size_t workBytes) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "scene_quad_interpolants: ctx is NULL");
+    CTX_GUARD(ctx, "scene_quad_interpolants");
+    if (!out) return fail(ctx, VQHIP_ERR_INVALID_ARG, "scene_quad_interpolants: NULL argument (out, ip0, ip1, ip2, owner or work)");
+    return sceneInterpolants(ctx, "scene_quad_interpolants", stream, draws, numDraws, width, height, owner, owner_pitch_px, &out->planes, out, work, workBytes);
 }
 
 } // extern "C"

@@ -92,27 +92,42 @@ struct MaterialSampler {
 // the diffuse map is fetched for the alpha test of the "_AlphaMasked" permutation alone, the normal map WITHOUT normalMapMipBias (:164 is Sample), the
 // coverage plane is left as it is (the lighting pass repeats the discard itself, ForwardLighting.hlsl:237-240).
 struct Record { float4 g0, g1, g2, g3; bool covered; };    // covered: a fragment of some material survived to the end of PSMain at this pixel
-template <bool PREPASS = false>
-VQD Record produce_record(const GbufArgs& a, int x, int y, bool inside, int lane) {
+// QA: empty, or the one QuadPlane of the _quad entry points (docs/DESIGN_DETAILS.md §7.20 Q2): the derivatives then come from the pixel's own helper lanes — the
+// owner primitive's uv at (x ^ 1, y) and (x, y ^ 1), written by vqhip_scene_quad_interpolants — instead of the quad partners in the planes. A helper lane always
+// belongs to the own primitive: no material comparison, no image-bounds test.
+VQD const QuadPlane& quadPlaneOf(const QuadPlane& p) { return p; }
+template <bool PREPASS = false, class... QA>
+VQD Record produce_record(const GbufArgs& a, int x, int y, bool inside, int lane, const QA&... quadPlane) {
+    constexpr bool QUAD = sizeof...(QA) != 0;
     const GbufConstants* __restrict__ gc = a.gc;
     Record rec;
     rec.g0 = rec.g1 = rec.g2 = rec.g3 = make_float4(0, 0, 0, 0);
     rec.covered = false;
     const uint32_t o = (__umul24(y, a.pitch) + (uint32_t)x) << 4;      // 32-bit byte offsets: planes are < 4 GB (checked by the C ABI)
 
-    float4 i0 = make_float4(0, 0, 0, 0), i1 = i0, i2 = i0;
+    float4 i0 = make_float4(0, 0, 0, 0), i1 = i0, i2 = i0, qd = i0;
     int idx = -1;
     if (inside) {
         // the interpolant planes are a stream (48 B per pixel, read once per kernel): non-temporal, so that they do not evict the material maps / LUT / cubes from the XCD L2s
         typedef float v4f __attribute__((ext_vector_type(4)));
         auto nt = [](const void* p) { const v4f v = __builtin_nontemporal_load((const v4f*)p); return make_float4(v.x, v.y, v.z, v.w); };
         i0 = nt((const char*)a.ip0 + o); i1 = nt((const char*)a.ip1 + o); i2 = nt((const char*)a.ip2 + o);
+        if constexpr (QUAD) {                                          // the same stream discipline, 16 B more per pixel (the plane is < 4 GB: checked by the C ABI)
+            const QuadPlane& qp = quadPlaneOf(quadPlane...);
+            qd = nt((const char*)qp.uv + ((__umul24(y, qp.pitch) + (uint32_t)x) << 4));
+        }
         idx = __float_as_int(i2.w);
         if (idx >= gc->numMaterials) idx = -1;
     }
-    // quad neighbours (raw uv + material index): lane^1 horizontal, lane^2 vertical
-    const float hu = __shfl_xor(i0.w, 1), hv = __shfl_xor(i1.w, 1); const int hidx = __shfl_xor(idx, 1);
-    const float vu = __shfl_xor(i0.w, 2), vv = __shfl_xor(i1.w, 2); const int vidx = __shfl_xor(idx, 2);
+    float hu, hv, vu, vv; int hidx, vidx;
+    if constexpr (QUAD) {
+        // helper lanes (raw uv of the own primitive at the quad partners' centres): x ^ 1 horizontal, y ^ 1 vertical
+        hu = qd.x; hv = qd.y; vu = qd.z; vv = qd.w; hidx = vidx = 0;
+    } else {
+        // quad neighbours (raw uv + material index): lane^1 horizontal, lane^2 vertical
+        hu = __shfl_xor(i0.w, 1); hv = __shfl_xor(i1.w, 1); hidx = __shfl_xor(idx, 1);
+        vu = __shfl_xor(i0.w, 2); vv = __shfl_xor(i1.w, 2); vidx = __shfl_xor(idx, 2);
+    }
 
     // idx < 0 (no geometry): the record stays all-zero
 
@@ -129,11 +144,11 @@ VQD Record produce_record(const GbufArgs& a, int x, int y, bool inside, int lane
             MaterialSampler ms;
             ms.uv = make_float2(i0.w * sx + ox, i1.w * sy + oy);                            // ForwardLighting.hlsl:226
             ms.ddx = make_float2(0, 0); ms.ddy = make_float2(0, 0);
-            if (hidx == mi) {
+            if (QUAD || hidx == mi) {                                                       // lane & 1 == x & 1, lane & 2 <=> y & 1 (strip_pixel)
                 const float nu = hu * sx + ox, nv = hv * sy + oy;
                 ms.ddx = (lane & 1) ? make_float2(ms.uv.x - nu, ms.uv.y - nv) : make_float2(nu - ms.uv.x, nv - ms.uv.y);
             }
-            if (vidx == mi) {
+            if (QUAD || vidx == mi) {
                 const float nu = vu * sx + ox, nv = vv * sy + oy;
                 ms.ddy = (lane & 2) ? make_float2(ms.uv.x - nu, ms.uv.y - nv) : make_float2(nu - ms.uv.x, nv - ms.uv.y);
             }
@@ -229,11 +244,12 @@ VQD void strip_pixel(int& x, int& y, int& lane) {
     y = blockIdx.y * 2 + ((lane >> 1) & 1);
 }
 
-__global__ __launch_bounds__(256, 4) void k_gbuffer_from_materials(GbufArgs a) {      // 4 waves per SIMD = 128 VGPRs (5 spilled): 17 % faster than the 137 the compiler takes uncapped (profiles/r4p_gbuffer_waves.jsonl)
+template <class... QA>
+__global__ __launch_bounds__(256, 4) void k_gbuffer_from_materials(GbufArgs a, QA... quadPlane) {      // 4 waves per SIMD = 128 VGPRs (1 spilled with the present compiler, 5 when this was measured): 17 % faster than the 137 the compiler takes uncapped (profiles/r4p_gbuffer_waves.jsonl)
     int x, y, lane;
     strip_pixel(x, y, lane);
     const bool inside = (x < a.width) & (y < a.height);
-    const Record r = produce_record<false>(a, x, y, inside, lane);
+    const Record r = produce_record<false>(a, x, y, inside, lane, quadPlane...);
     if (!inside) return;
     const uint32_t q = (__umul24(y, a.outPitch) + (uint32_t)x) << 4;
     *(float4*)((char*)a.gb0 + q) = r.g0; *(float4*)((char*)a.gb1 + q) = r.g1; *(float4*)((char*)a.gb2 + q) = r.g2; *(float4*)((char*)a.gb3 + q) = r.g3;
@@ -241,12 +257,12 @@ __global__ __launch_bounds__(256, 4) void k_gbuffer_from_materials(GbufArgs a) {
 
 // The Z pre-pass's colour target (DepthPrePass.hlsl:PSMain; VQRenderer::RenderDepthPrePass, SceneRendering.cpp:1264-1360): Tex_SceneNormals, R10G10B10A2_UNORM
 // (float -> UNORM n: trunc(saturate(c) * (2^n - 1) + 0.5)) or the unquantised float4; pixels nothing is drawn on keep the clear value 0 (:1289-1300).
-template <int OUTFMT>
-__global__ __launch_bounds__(256) void k_scene_normals_from_materials(GbufArgs a, void* out) {
+template <int OUTFMT, class... QA>
+__global__ __launch_bounds__(256) void k_scene_normals_from_materials(GbufArgs a, void* out, QA... quadPlane) {
     int x, y, lane;
     strip_pixel(x, y, lane);
     const bool inside = (x < a.width) & (y < a.height);
-    const float4 n = produce_record<true>(a, x, y, inside, lane).g1;
+    const float4 n = produce_record<true>(a, x, y, inside, lane, quadPlane...).g1;
     if (!inside) return;
     const size_t q = (size_t)y * a.outPitch + x;
     if (OUTFMT == VQHIP_FMT_RGBA32F) { ((float4*)out)[q] = n; return; }
@@ -257,12 +273,12 @@ __global__ __launch_bounds__(256) void k_scene_normals_from_materials(GbufArgs a
 // PSMain as the engine has it (ForwardLighting.hlsl:226-380): the producer and the lighting body (vq_shade.h) in ONE kernel — the 64-byte record
 // stays in registers instead of making a 128 B/pixel round trip through HBM. Bit-identical to vqhip_gbuffer_from_materials followed by
 // vqhip_forward_lighting (the record is the same fp32 values either way; pixels without geometry shade the all-zero record like the two calls do).
-template <bool HAS_ENV, bool HAS_CASTERS, int OUTFMT, int WAVES, int AR>
-__global__ __launch_bounds__(256, WAVES) void k_forward_from_materials(GbufArgs a, const FrameConstants* fc, void* out, int outPitch, MrtArgs mrt) {
+template <bool HAS_ENV, bool HAS_CASTERS, int OUTFMT, int WAVES, int AR, class... QA>
+__global__ __launch_bounds__(256, WAVES) void k_forward_from_materials(GbufArgs a, const FrameConstants* fc, void* out, int outPitch, MrtArgs mrt, QA... quadPlane) {
     int x, y, lane;
     strip_pixel(x, y, lane);
     const bool inside = (x < a.width) & (y < a.height);
-    const Record r = produce_record<false>(a, x, y, inside, lane);
+    const Record r = produce_record<false>(a, x, y, inside, lane, quadPlane...);
     if (!inside) return;
     // SV_TARGET1 / the motion vectors exist only where a fragment reaches :382-389: pixels without geometry and alpha-mask discards keep the targets' clear
     // values, as under the rasteriser (the colour target is still written for them: the all-zero record shaded, like the two calls do)
@@ -272,34 +288,48 @@ __global__ __launch_bounds__(256, WAVES) void k_forward_from_materials(GbufArgs 
 }
 
 
-hipError_t launch_gbuffer_from_materials(hipStream_t s, const GbufArgs& a) {
+// QA: empty (the entry points of §7.1 / §7.8) or the QuadPlane of their _quad forms (§7.20): one body for both, the kernels differ in the pack alone
+template <class... QA>
+static hipError_t launchGbuffer(hipStream_t s, const GbufArgs& a, const QA&... quad) {
     dim3 grid((a.width + 127) / 128, (a.height + 1) / 2);
-    hipLaunchKernelGGL(k_gbuffer_from_materials, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_gbuffer_from_materials<QA...>, grid, dim3(256), 0, s, a, quad...);
     return hipGetLastError();
 }
+hipError_t launch_gbuffer_from_materials(hipStream_t s, const GbufArgs& a) { return launchGbuffer(s, a); }
+hipError_t launch_gbuffer_from_materials_quad(hipStream_t s, const GbufArgs& a, const QuadPlane& quad) { return launchGbuffer(s, a, quad); }
 
-hipError_t launch_scene_normals_from_materials(hipStream_t s, const GbufArgs& a, void* out, int outFmt) {
+template <class... QA>
+static hipError_t launchSceneNormals(hipStream_t s, const GbufArgs& a, void* out, int outFmt, const QA&... quad) {
     dim3 grid((a.width + 127) / 128, (a.height + 1) / 2);
-    if (outFmt == VQHIP_FMT_RGBA32F) hipLaunchKernelGGL(k_scene_normals_from_materials<VQHIP_FMT_RGBA32F>, grid, dim3(256), 0, s, a, out);
-    else                             hipLaunchKernelGGL(k_scene_normals_from_materials<VQHIP_FMT_R10G10B10A2_UNORM>, grid, dim3(256), 0, s, a, out);
+    if (outFmt == VQHIP_FMT_RGBA32F) hipLaunchKernelGGL((k_scene_normals_from_materials<VQHIP_FMT_RGBA32F, QA...>), grid, dim3(256), 0, s, a, out, quad...);
+    else                             hipLaunchKernelGGL((k_scene_normals_from_materials<VQHIP_FMT_R10G10B10A2_UNORM, QA...>), grid, dim3(256), 0, s, a, out, quad...);
     return hipGetLastError();
 }
+hipError_t launch_scene_normals_from_materials(hipStream_t s, const GbufArgs& a, void* out, int outFmt) { return launchSceneNormals(s, a, out, outFmt); }
+hipError_t launch_scene_normals_from_materials_quad(hipStream_t s, const GbufArgs& a, void* out, int outFmt, const QuadPlane& quad) { return launchSceneNormals(s, a, out, outFmt, quad); }
 
-hipError_t launch_forward_from_materials(hipStream_t s, const GbufArgs& a, const FrameConstants* fc, bool hasEnv, bool hasCasters, void* out, int outPitch, int outFmt, int arithDxc, const Options& opt, const MrtArgs& mrt) {
+template <class... QA>
+static hipError_t launchForward(hipStream_t s, const GbufArgs& a, const FrameConstants* fc, bool hasEnv, bool hasCasters, void* out, int outPitch, int outFmt, int arithDxc, const Options& opt, const MrtArgs& mrt, const QA&... quad) {
     dim3 grid((a.width + 127) / 128, (a.height + 1) / 2);
     // register budget of the fused kernel: the producer half peaks at ~120 VGPRs (4 waves per SIMD), the lighting half needs 67; VQHIP_PSMAIN_WAVES = 5 / 6
     // caps the kernel at 96 / 80 VGPRs (the producer half then spills a little, the 64-light loop runs at higher occupancy)
     const int wv = opt.psmainWaves ? opt.psmainWaves : VQ_PSMAIN_WAVES_DEFAULT;      // option "psmain_waves"
-#define FFM(E, C, F) do { if (arithDxc) hipLaunchKernelGGL((k_forward_from_materials<E, C, F, VQ_PSMAIN_WAVES_DEFAULT, 1>), grid, dim3(256), 0, s, a, fc, out, outPitch, mrt); /* DXC reading: one occupancy form */ \
-                          else if (wv >= 6) hipLaunchKernelGGL((k_forward_from_materials<E, C, F, 6, 0>), grid, dim3(256), 0, s, a, fc, out, outPitch, mrt); \
-                          else if (wv == 5) hipLaunchKernelGGL((k_forward_from_materials<E, C, F, 5, 0>), grid, dim3(256), 0, s, a, fc, out, outPitch, mrt); \
-                          else hipLaunchKernelGGL((k_forward_from_materials<E, C, F, 4, 0>), grid, dim3(256), 0, s, a, fc, out, outPitch, mrt); } while (0)
+#define FFM(E, C, F) do { if (arithDxc) hipLaunchKernelGGL((k_forward_from_materials<E, C, F, VQ_PSMAIN_WAVES_DEFAULT, 1, QA...>), grid, dim3(256), 0, s, a, fc, out, outPitch, mrt, quad...); /* DXC reading: one occupancy form */ \
+                          else if (wv >= 6) hipLaunchKernelGGL((k_forward_from_materials<E, C, F, 6, 0, QA...>), grid, dim3(256), 0, s, a, fc, out, outPitch, mrt, quad...); \
+                          else if (wv == 5) hipLaunchKernelGGL((k_forward_from_materials<E, C, F, 5, 0, QA...>), grid, dim3(256), 0, s, a, fc, out, outPitch, mrt, quad...); \
+                          else hipLaunchKernelGGL((k_forward_from_materials<E, C, F, 4, 0, QA...>), grid, dim3(256), 0, s, a, fc, out, outPitch, mrt, quad...); } while (0)
 #define FFM2(E, C) do { if (outFmt == VQHIP_FMT_RGBA32F) FFM(E, C, 0); else FFM(E, C, 1); } while (0)
     if (hasEnv) { if (hasCasters) FFM2(true, true); else FFM2(true, false); }
     else        { if (hasCasters) FFM2(false, true); else FFM2(false, false); }
 #undef FFM2
 #undef FFM
     return hipGetLastError();
+}
+hipError_t launch_forward_from_materials(hipStream_t s, const GbufArgs& a, const FrameConstants* fc, bool hasEnv, bool hasCasters, void* out, int outPitch, int outFmt, int arithDxc, const Options& opt, const MrtArgs& mrt) {
+    return launchForward(s, a, fc, hasEnv, hasCasters, out, outPitch, outFmt, arithDxc, opt, mrt);
+}
+hipError_t launch_forward_from_materials_quad(hipStream_t s, const GbufArgs& a, const FrameConstants* fc, bool hasEnv, bool hasCasters, void* out, int outPitch, int outFmt, int arithDxc, const Options& opt, const MrtArgs& mrt, const QuadPlane& quad) {
+    return launchForward(s, a, fc, hasEnv, hasCasters, out, outPitch, outFmt, arithDxc, opt, mrt, quad);
 }
 
 // ---- MipImage, 4-byte branch (DXGIUtils.cpp:264-285): each channel (a+b+c+d)/4, integer division ---------

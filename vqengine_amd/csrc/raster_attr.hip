@@ -8,7 +8,9 @@
 //                           through the vertex stage -> weights -> 11 or 19 attributes; float4 stores, one plane at a time.
 // Every index is checked before it is used: q against the call's instanced triangles, the three indices against numVertices. Nothing an owner plane or a mesh
 // holds can move a load or a store out of bounds.
-#include "vq_raster.h"
+// vqhip_scene_quad_interpolants (§7.20 Q1) launches the QUAD instantiations of the same kernel: one more float4 plane, the owner triangle's uv at the two helper
+// lanes' centres (i ^ 1, j) and (i, j ^ 1), evaluated by vq_raster_mask.h's maskUvAt — the statement of I2 / I3 the masked depth fill already uses for its helper lanes.
+#include "vq_raster_mask.h"
 
 namespace vqk {
 using namespace vqd;
@@ -57,8 +59,11 @@ VQD uint32_t roundBits(double d) {
 // I0 .. I3 for the owner q of pixel (i, j): the record's words into out[] (left as they are when q owns nothing). Called with the lane's own q, or — from a wave whose
 // 64 pixels share one owner — with that q as a wave-uniform value: the table entry, the indices, the vertices and the matrices then have uniform addresses and
 // travel through the scalar cache, one fetch per wave instead of one per lane. The arithmetic is the same instruction sequence either way: identical bits.
-template <bool SV>
-VQD void resolveOwner(const SceneInterpArgs& a, const SurfaceJob* __restrict__ table, uint32_t q, int i, int j, uint32_t* out) {
+// QUAD: also quad[0 .. 3] = (u_h, v_h, u_v, v_v), the owner's uv at the centres of pixels (i ^ 1, j) and (i, j ^ 1) — which may lie outside the viewport and outside
+// the triangle. The three sub-determinants of each weight depend on the triangle alone and are shared by the two centres; with -ffp-contract=off that is the
+// expression of det() bit for bit.
+template <bool SV, bool QUAD>
+VQD void resolveOwner(const SceneInterpArgs& a, const SurfaceJob* __restrict__ table, uint32_t q, int i, int j, uint32_t* out, uint32_t* quad) {
     int lo = 0, hi = a.numJobs - 1;               // the last job whose firstQ is <= q; numJobs >= 1 since totalTris > 0
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (table[mid].firstQ <= q) lo = mid; else hi = mid - 1; }
     const SurfaceJob& J = table[lo];
@@ -90,10 +95,23 @@ VQD void resolveOwner(const SceneInterpArgs& a, const SurfaceJob* __restrict__ t
         out[at] = bits;
     }
     out[11] = (uint32_t)J.materialIndex;
+    if constexpr (QUAD) {                         // after I3: of the 57 vertex scalars only the nine of (x, y, w) and the six of uv are still live
+        MaskUv t;
+        t.P[0] = y1 * w2 - w1 * y2; t.Q[0] = x1 * w2 - w1 * x2; t.R[0] = x1 * y2 - y1 * x2;
+        t.P[1] = y2 * w0 - w2 * y0; t.Q[1] = x2 * w0 - w2 * x0; t.R[1] = x2 * y0 - y2 * x0;
+        t.P[2] = y0 * w1 - w0 * y1; t.Q[2] = x0 * w1 - w0 * x1; t.R[2] = x0 * y1 - y0 * x1;
+        t.u[0] = v0.a[9]; t.v[0] = v0.a[10]; t.u[1] = v1.a[9]; t.v[1] = v1.a[10]; t.u[2] = v2.a[9]; t.v[2] = v2.a[10];
+        const float2 h = maskUvAt(t, pixelCentreX(i ^ 1, a.width), Y), v = maskUvAt(t, X, pixelCentreY(j ^ 1, a.height));
+        auto canon = [](float f) { return f != f ? kCanonicalNaN : __float_as_uint(f); };
+        quad[0] = canon(h.x); quad[1] = canon(h.y); quad[2] = canon(v.x); quad[3] = canon(v.y);
+    }
 }
 
-template <bool SV, bool WAVE>
-__global__ void __launch_bounds__(kLanes) k_scene_interpolants(SceneInterpArgs a, const SurfaceJob* __restrict__ table) {
+// QA: empty, or the one QuadPlane of vqhip_scene_quad_interpolants (the existing instantiations keep their parameter list)
+VQD const QuadPlane& quadPlaneOf(const QuadPlane& p) { return p; }
+template <bool SV, bool WAVE, class... QA>
+__global__ void __launch_bounds__(kLanes) k_scene_interpolants(SceneInterpArgs a, const SurfaceJob* __restrict__ table, QA... quadPlane) {
+    constexpr bool QUAD = sizeof...(QA) != 0;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int i = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), j = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
     if (i >= a.width || j >= a.height) return;
@@ -103,13 +121,14 @@ __global__ void __launch_bounds__(kLanes) k_scene_interpolants(SceneInterpArgs a
     for (int k = 0; k < (SV ? 20 : 12); ++k) out[k] = 0u;
     out[11] = kNoPrimitive;                       // asfloat(int32 -1)
     if constexpr (SV) { out[15] = 0x3f800000u; out[19] = 0x3f800000u; }
+    uint32_t quad[4] = { 0u, 0u, 0u, 0u };
 
     // I0: q at or beyond the call's instanced triangles (0xFFFFFFFF included: the host refuses 2^29 or more) owns nothing
     const uint32_t q0 = __builtin_amdgcn_readfirstlane(q);
     if (WAVE && __builtin_amdgcn_ballot_w64(q != q0) == 0ull) {       // the wave's live lanes share one owner
-        if (q0 < a.totalTris) resolveOwner<SV>(a, table, q0, i, j, out);
+        if (q0 < a.totalTris) resolveOwner<SV, QUAD>(a, table, q0, i, j, out, quad);
     } else if (q < a.totalTris) {
-        resolveOwner<SV>(a, table, q, i, j, out);
+        resolveOwner<SV, QUAD>(a, table, q, i, j, out, quad);
     }
     const size_t at = (size_t)j * a.pitch + i;
     ((uint4*)a.ip[0])[at] = make_uint4(out[0], out[1], out[2], out[3]);
@@ -119,6 +138,10 @@ __global__ void __launch_bounds__(kLanes) k_scene_interpolants(SceneInterpArgs a
         const size_t sat = (size_t)j * a.svPitch + i;
         ((uint4*)a.sv[0])[sat] = make_uint4(out[12], out[13], out[14], out[15]);
         ((uint4*)a.sv[1])[sat] = make_uint4(out[16], out[17], out[18], out[19]);
+    }
+    if constexpr (QUAD) {
+        const QuadPlane& qp = quadPlaneOf(quadPlane...);
+        ((uint4*)qp.uv)[(size_t)j * qp.pitch + i] = make_uint4(quad[0], quad[1], quad[2], quad[3]);
     }
 }
 
@@ -137,6 +160,18 @@ hipError_t launch_scene_interpolants(hipStream_t s, const SceneInterpArgs& a, co
     } else {
         if (waveForm) hipLaunchKernelGGL((k_scene_interpolants<false, true>), grid, dim3(kLanes), 0, s, a, table);
         else          hipLaunchKernelGGL((k_scene_interpolants<false, false>), grid, dim3(kLanes), 0, s, a, table);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_scene_quad_interpolants(hipStream_t s, const SceneInterpArgs& a, const SurfaceJob* table, bool waveForm, const QuadPlane& quad) {
+    const dim3 grid((uint32_t)((a.width + 15) / 16), (uint32_t)((a.height + 15) / 16));
+    if (a.sv[0]) {
+        if (waveForm) hipLaunchKernelGGL((k_scene_interpolants<true, true, QuadPlane>), grid, dim3(kLanes), 0, s, a, table, quad);
+        else          hipLaunchKernelGGL((k_scene_interpolants<true, false, QuadPlane>), grid, dim3(kLanes), 0, s, a, table, quad);
+    } else {
+        if (waveForm) hipLaunchKernelGGL((k_scene_interpolants<false, true, QuadPlane>), grid, dim3(kLanes), 0, s, a, table, quad);
+        else          hipLaunchKernelGGL((k_scene_interpolants<false, false, QuadPlane>), grid, dim3(kLanes), 0, s, a, table, quad);
     }
     return hipGetLastError();
 }

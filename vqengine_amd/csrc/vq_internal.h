@@ -113,6 +113,13 @@ hipError_t launch_gbuffer_from_materials(hipStream_t s, const GbufArgs& a);
 hipError_t launch_scene_normals_from_materials(hipStream_t s, const GbufArgs& a, void* out, int outFmt);   // a.gb* unused, a.outPitch = pitch of `out`
 struct FrameConstants;
 hipError_t launch_forward_from_materials(hipStream_t s, const GbufArgs& a, const FrameConstants* fc, bool hasEnv, bool hasCasters, void* out, int outPitch, int outFmt, int arithDxc, const Options& opt, const MrtArgs& mrt);
+// §7.20: the quad-uv plane, float4 [height][pitch] = the owner primitive's vertex uv at the helper lanes (i ^ 1, j) and (i, j ^ 1). Written by the QUAD instantiations of
+// k_scene_interpolants (raster_attr.hip), read by the QUAD instantiations of the surface producers (gbuffer.hip); it travels as a kernel parameter of its own, so
+// that every other instantiation keeps its parameter list.
+struct QuadPlane { void* uv; uint32_t pitch; };
+hipError_t launch_gbuffer_from_materials_quad(hipStream_t s, const GbufArgs& a, const QuadPlane& quad);
+hipError_t launch_scene_normals_from_materials_quad(hipStream_t s, const GbufArgs& a, void* out, int outFmt, const QuadPlane& quad);
+hipError_t launch_forward_from_materials_quad(hipStream_t s, const GbufArgs& a, const FrameConstants* fc, bool hasEnv, bool hasCasters, void* out, int outPitch, int outFmt, int arithDxc, const Options& opt, const MrtArgs& mrt, const QuadPlane& quad);
 hipError_t launch_mip_box_rgba8(hipStream_t s, const void* src, void* dst, int sw, int sh, int dw, int dh);
 hipError_t launch_skydome(hipStream_t s, const float4* eq0, int w0, int h0, const VQ_SkydomeParams& sp, const float4* cov, int covPitch,
                           void* color, int W, int H, int pitch, int fmt);
@@ -342,6 +349,7 @@ struct SceneInterpArgs {
 };
 hipError_t launch_table_copy(hipStream_t s, const void* src, void* dst, uint32_t numUint4);
 hipError_t launch_scene_interpolants(hipStream_t s, const SceneInterpArgs& a, const SurfaceJob* table, bool waveForm);   // waveForm: waves with one owner fetch it once
+hipError_t launch_scene_quad_interpolants(hipStream_t s, const SceneInterpArgs& a, const SurfaceJob* table, bool waveForm, const QuadPlane& quad);
 
 // launchers (each returns the hipError_t of the launch)
 hipError_t launch_forward_lighting(hipStream_t s, const ShadeArgs& a, bool hasEnv, bool hasCasters, int outFmt, const Options& opt);

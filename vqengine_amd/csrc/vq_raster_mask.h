@@ -13,9 +13,11 @@ using namespace vqd;
 VQD const MaskArgs& maskArgsOf(const MaskArgs& m) { return m; }     // the one element of a kernel's mask parameter pack
 
 // A masked record as the fill loop holds it: the three sub-determinants of each I2 weight (they depend on the triangle alone), the uv, the material's entry.
-struct MaskTri {
+struct MaskUv {                        // the part M2 reads: also what the quad resolve of raster_attr.hip (§7.20 Q1) fills for its helper lanes
     double P[3], Q[3], R[3];          // k_n = (X * P[n] - Y * Q[n]) + R[n]
     float u[3], v[3];
+};
+struct MaskTri : MaskUv {
     MaskTex tex;
 };
 
@@ -40,7 +42,7 @@ VQD bool loadMaskTri(const MaskArgs& m, uint32_t mk, MaskTri& t) {
 }
 
 // M2: the primitive's uv at the pixel centre (X, Y), which may lie outside the primitive (extrapolation)
-VQD float2 maskUvAt(const MaskTri& t, double X, double Y) {
+VQD float2 maskUvAt(const MaskUv& t, double X, double Y) {
     const double k0 = (X * t.P[0] - Y * t.Q[0]) + t.R[0], k1 = (X * t.P[1] - Y * t.Q[1]) + t.R[1], k2 = (X * t.P[2] - Y * t.Q[2]) + t.R[2];
     const double den = (k0 + k1) + k2;
     const double l1 = k1 / den, l2 = k2 / den;
