@@ -331,7 +331,8 @@ VQHIP_API int  vqhip_set_fresnel_pow(vqhip_ctx* ctx, vqhip_fresnel_pow mode);
  * (docs/WARP_CALIBRATION.md) selects whichever WARP turns out to follow. */
 /* Tuning / A-B options of a context, read by the launchers at call time (never from the process environment: getenv racing a host setenv is
  * undefined behaviour, and VQEngine records on many threads, SceneRendering.cpp:563-706). value NULL, "" or "default" restores the default. Every
- * form selected here gives the bits of the default form (tests/test_gpu_conv_forms.py, tests/test_gpu_round3.py); unknown keys / values: VQHIP_ERR_INVALID_ARG.
+ * form selected here gives the bits of the default form (tests/test_gpu_conv_forms.py, tests/test_gpu_round3.py; psmain_waves and shade_wg in every instantiation of their
+ * kernels: tests/test_gpu_psmain_variants.py); unknown keys / values: VQHIP_ERR_INVALID_ARG.
  *   shade_wg 64|128|256 · psmain_waves 4|5|6 · blur_y_wgs n · msaa_edge_wgs n · post_form two|chain · post_strips n · lut_form general ·
  *   specular_form general · diffuse_form records|texels|general · diffuse_seq_form ordered|lane · raster_tile 32|64 · interp_form lane|wave
  * (the non-default values are the general / fallback forms of the same kernels; the measured-and-rejected kernel forms of rounds 2-5 — the compact tonemap
