@@ -70,6 +70,25 @@ protected:
     vqhip_ctx* mCtx;
     static void* Alloc(size_t bytes) { void* p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }
     static void Free(void*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
+    // A device buffer a pass owns and sizes on demand (the library itself never allocates). Reserve refuses need == 0, keeps a buffer that is large enough and
+    // otherwise frees the old one before it allocates (hipFree waits for the device); the buffer only grows. Freed with the pass.
+    struct WorkBuffer {
+        void* ptr = nullptr; size_t bytes = 0;
+        WorkBuffer() = default;
+        WorkBuffer(const WorkBuffer&) = delete;
+        WorkBuffer& operator=(const WorkBuffer&) = delete;
+        ~WorkBuffer() { Release(); }
+        bool Reserve(size_t need) {
+            if (!need) return false;
+            if (need <= bytes) return true;
+            Release();
+            ptr = Alloc(need);
+            if (ptr) bytes = need;
+            return ptr != nullptr;
+        }
+        void Release() { Free(ptr); bytes = 0; }
+    };
+    template <class DRAW> static uint64_t InstancedTriangles(const DRAW& d) { return (uint64_t)(d.mesh.numIndices / 3) * d.numInstances; }
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -437,20 +456,19 @@ public:
     void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override {
         OnDestroyWindowSizeDependentResources();
         mWidth = Width; mHeight = Height;
-        mWorkBytes = vqhip_cacao_work_bytes((int)Width, (int)Height);
-        mWork = mWorkBytes ? Alloc(mWorkBytes) : nullptr;
+        mWork.Reserve(vqhip_cacao_work_bytes((int)Width, (int)Height));
     }
-    void OnDestroyWindowSizeDependentResources() override { Free(mWork); mWorkBytes = 0; mWidth = mHeight = 0; }
+    void OnDestroyWindowSizeDependentResources() override { mWork.Release(); mWidth = mHeight = 0; }
     void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
         const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
-        if (!p || !mWork) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        if (!p || !mWork.ptr) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
         mStatus = vqhip_cacao(mCtx, p->Stream, p->TexSceneDepthResolve, (size_t)mWidth * 4, p->TexSceneNormals, VQHIP_FMT_R10G10B10A2_UNORM, (size_t)mWidth * 4,
-                              &p->Constants, p->PerPassConstants, VQHIP_CACAO_QUALITY_HIGH, p->BlurPassCount, mWork, mWorkBytes, p->TexAmbientOcclusion,
+                              &p->Constants, p->PerPassConstants, VQHIP_CACAO_QUALITY_HIGH, p->BlurPassCount, mWork.ptr, mWork.bytes, p->TexAmbientOcclusion,
                               (size_t)mWidth, (int)mWidth, (int)mHeight);
     }
-    const void* GetWorkBuffer() const { return mWork; }          // vqhip_cacao_plane_offset_bytes addresses the intermediates
+    const void* GetWorkBuffer() const { return mWork.ptr; }      // vqhip_cacao_plane_offset_bytes addresses the intermediates
 private:
-    void* mWork = nullptr; size_t mWorkBytes = 0;
+    WorkBuffer mWork;
     unsigned mWidth = 0, mHeight = 0;
 };
 
@@ -471,20 +489,19 @@ public:
     void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override {
         OnDestroyWindowSizeDependentResources();
         mWidth = Width; mHeight = Height;
-        mWorkBytes = vqhip_adaptive_cacao_work_bytes((int)Width, (int)Height);
-        mWork = mWorkBytes ? Alloc(mWorkBytes) : nullptr;
+        mWork.Reserve(vqhip_adaptive_cacao_work_bytes((int)Width, (int)Height));
     }
-    void OnDestroyWindowSizeDependentResources() override { Free(mWork); mWorkBytes = 0; mWidth = mHeight = 0; }
+    void OnDestroyWindowSizeDependentResources() override { mWork.Release(); mWidth = mHeight = 0; }
     void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
         const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
-        if (!p || !mWork) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        if (!p || !mWork.ptr) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
         mStatus = vqhip_adaptive_cacao(mCtx, p->Stream, p->TexSceneDepthResolve, (size_t)mWidth * 4, p->TexSceneNormals, VQHIP_FMT_R10G10B10A2_UNORM, (size_t)mWidth * 4,
-                                       &p->Constants, p->PerPassConstants, p->BlurPassCount, mWork, mWorkBytes, p->TexAmbientOcclusion,
+                                       &p->Constants, p->PerPassConstants, p->BlurPassCount, mWork.ptr, mWork.bytes, p->TexAmbientOcclusion,
                                        (size_t)mWidth, (int)mWidth, (int)mHeight);
     }
-    const void* GetWorkBuffer() const { return mWork; }          // vqhip_adaptive_cacao_plane_offset_bytes addresses the intermediates
+    const void* GetWorkBuffer() const { return mWork.ptr; }      // vqhip_adaptive_cacao_plane_offset_bytes addresses the intermediates
 private:
-    void* mWork = nullptr; size_t mWorkBytes = 0;
+    WorkBuffer mWork;
     unsigned mWidth = 0, mHeight = 0;
 };
 
@@ -514,51 +531,51 @@ public:
         float PointRange[VQ_NUM_SHADOWING_LIGHTS__POINT] = {};                  // ... .range, the far plane (:1235)
     };
     explicit ShadowDepthPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
-    ~ShadowDepthPass() override { Free(mWork); }
     bool Initialize() override { return mCtx != nullptr; }
-    void Destroy() override { Free(mWork); mWorkBytes = 0; }
+    void Destroy() override { mWork.Release(); }
     void OnCreateWindowSizeDependentResources(unsigned, unsigned, const IRenderPassResourceCollection* = nullptr) override {}   // shadow maps do not follow the window
     void OnDestroyWindowSizeDependentResources() override {}
-    bool Reserve(uint64_t InstancedTriangles) {
-        const size_t need = vqhip_shadow_depth_work_bytes(InstancedTriangles, VQHIP_SHADOW_MAX_VIEWS);
-        if (!need) return false;
-        if (need <= mWorkBytes) return true;
-        Free(mWork); mWorkBytes = 0;
-        mWork = Alloc(need);
-        if (mWork) mWorkBytes = need;
-        return mWork != nullptr;
-    }
+    bool Reserve(uint64_t InstancedTriangles) { return mWork.Reserve(vqhip_shadow_depth_work_bytes(InstancedTriangles, VQHIP_SHADOW_MAX_VIEWS)); }
     void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
         const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
         if (!p || p->NumSpotShadowViews > VQ_NUM_SHADOWING_LIGHTS__SPOT || p->NumPointShadowViews > VQ_NUM_SHADOWING_LIGHTS__POINT) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
-        vqhip_shadow_view views[1 + VQ_NUM_SHADOWING_LIGHTS__SPOT + 6 * VQ_NUM_SHADOWING_LIGHTS__POINT];
-        int n = 0;
+        vqhip_shadow_view views[kMaxViews];
         uint64_t triangles = 0;
-        auto add = [&](const std::vector<vqhip_shadow_draw>* draws, float* map, int dim, int linear, VQ_float3 pos, float farPlane) {
-            if (!draws || draws->empty()) return;
-            vqhip_shadow_view& v = views[n++];
-            v.depth = map; v.pitchBytes = 0; v.dim = dim; v.linearDepth = linear; v.cameraPosition = pos; v.farPlane = farPlane;
-            v.draws = draws->data(); v.numDraws = (int32_t)draws->size();
-            for (const vqhip_shadow_draw& d : *draws) triangles += (uint64_t)(d.mesh.numIndices / 3) * d.numInstances;
-        };
-        const VQ_float3 zero = { 0.0f, 0.0f, 0.0f };
-        add(p->DirectionalDraws, p->ShadowMapsDirectional, p->DirectionalDim, 0, zero, 1.0f);                       // :1146-1147
-        for (unsigned i = 0; i < p->NumSpotShadowViews; ++i)
-            add(p->SpotDraws[i], p->ShadowMapsSpot ? p->ShadowMapsSpot + (size_t)i * p->SpotDim * p->SpotDim : nullptr, p->SpotDim, 0, zero, 1.0f);
-        for (unsigned i = 0; i < p->NumPointShadowViews; ++i)
-            for (unsigned face = 0; face < 6; ++face)
-                add(p->PointDraws[i * 6 + face], p->ShadowMapsPoint ? p->ShadowMapsPoint + (size_t)(i * 6 + face) * p->PointDim * p->PointDim : nullptr, p->PointDim, 1,
-                    p->PointPosition[i], p->PointRange[i]);
+        const int n = WalkViews(*p, views, [&](vqhip_shadow_view& v, const std::vector<vqhip_shadow_draw>& draws, ViewKind, unsigned) {
+            v.draws = draws.data();
+            for (const vqhip_shadow_draw& d : draws) triangles += InstancedTriangles(d);
+        });
         mNumViews = n;
         if (n == 0) { mStatus = VQHIP_OK; return; }                              // nothing casts a shadow this frame
         if (!Reserve(triangles)) { mStatus = VQHIP_ERR_HIP; return; }
-        mStatus = vqhip_shadow_depth(mCtx, p->Stream, views, n, mWork, mWorkBytes);
+        mStatus = vqhip_shadow_depth(mCtx, p->Stream, views, n, mWork.ptr, mWork.bytes);
     }
-    const void* GetWorkBuffer() const { return mWork; }
-    size_t GetWorkBytes() const { return mWorkBytes; }
+    // The frame's views in the library's order — directional, spots, point faces (LINEAR_DEPTH, the caster's position and range) — into views[0 .. n): a view
+    // whose draw list is missing or empty is skipped, a map array that is NULL stays NULL. perView(view, its draws, kind, k) sets view.draws; k is the spot's
+    // number, or light * 6 + face. Returns n. Shared with MaskedShadowDepthPass (VIEW = vqhip_shadow_masked_view).
+    static constexpr int kMaxViews = 1 + VQ_NUM_SHADOWING_LIGHTS__SPOT + 6 * VQ_NUM_SHADOWING_LIGHTS__POINT;
+    enum ViewKind { kDirectional, kSpot, kPointFace };
+    template <class VIEW, class FN>
+    static int WalkViews(const FDrawParameters& p, VIEW* views, FN&& perView) {
+        int n = 0;
+        auto add = [&](const std::vector<vqhip_shadow_draw>* draws, ViewKind kind, unsigned k, float* maps, int dim, VQ_float3 pos, float farPlane) {
+            if (!draws || draws->empty()) return;
+            VIEW& v = views[n++];
+            v.depth = maps ? maps + (size_t)k * dim * dim : nullptr; v.pitchBytes = 0; v.dim = dim; v.linearDepth = kind == kPointFace; v.cameraPosition = pos; v.farPlane = farPlane;
+            v.draws = nullptr; v.numDraws = (int32_t)draws->size();
+            perView(v, *draws, kind, k);
+        };
+        const VQ_float3 zero = { 0.0f, 0.0f, 0.0f };
+        add(p.DirectionalDraws, kDirectional, 0, p.ShadowMapsDirectional, p.DirectionalDim, zero, 1.0f);            // :1146-1147
+        for (unsigned i = 0; i < p.NumSpotShadowViews; ++i) add(p.SpotDraws[i], kSpot, i, p.ShadowMapsSpot, p.SpotDim, zero, 1.0f);
+        for (unsigned i = 0; i < p.NumPointShadowViews * 6; ++i) add(p.PointDraws[i], kPointFace, i, p.ShadowMapsPoint, p.PointDim, p.PointPosition[i / 6], p.PointRange[i / 6]);
+        return n;
+    }
+    const void* GetWorkBuffer() const { return mWork.ptr; }
+    size_t GetWorkBytes() const { return mWork.bytes; }
     int LastViewCount() const { return mNumViews; }
 private:
-    void* mWork = nullptr; size_t mWorkBytes = 0;
+    WorkBuffer mWork;
     int mNumViews = 0;
 };
 
@@ -585,36 +602,31 @@ public:
         uint32_t* LayerPrimitive[VQHIP_SCENE_DEPTH_MAX_LAYERS] = {};
     };
     explicit DepthPrePass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
-    ~DepthPrePass() override { Free(mWork); }
     bool Initialize() override { return mCtx != nullptr; }
-    void Destroy() override { Free(mWork); mWorkBytes = 0; }
+    void Destroy() override { mWork.Release(); }
     void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override { mWidth = Width; mHeight = Height; }
     void OnDestroyWindowSizeDependentResources() override { mWidth = mHeight = 0; }
-    bool Reserve(uint64_t InstancedTriangles) {
-        const size_t need = vqhip_scene_depth_work_bytes(InstancedTriangles);
-        if (!need) return false;
-        if (need <= mWorkBytes) return true;
-        Free(mWork); mWorkBytes = 0;
-        mWork = Alloc(need);
-        if (mWork) mWorkBytes = need;
-        return mWork != nullptr;
-    }
+    bool Reserve(uint64_t InstancedTriangles) { return mWork.Reserve(vqhip_scene_depth_work_bytes(InstancedTriangles)); }
     void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
         const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
         if (!p || p->NumLayers < 0 || p->NumLayers > VQHIP_SCENE_DEPTH_MAX_LAYERS) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
         uint64_t triangles = 0;
         const int numDraws = p->Draws ? (int)p->Draws->size() : 0;
-        for (int d = 0; d < numDraws; ++d) triangles += (uint64_t)((*p->Draws)[d].mesh.numIndices / 3) * (*p->Draws)[d].numInstances;
+        for (int d = 0; d < numDraws; ++d) triangles += InstancedTriangles((*p->Draws)[d]);
         if (!Reserve(triangles)) { mStatus = VQHIP_ERR_HIP; return; }
-        vqhip_scene_depth_targets t = {};
-        t.depth = p->SceneDepth; t.primitive = p->Primitive; t.layers = p->bMSAA ? p->NumLayers : 0;
-        for (int k = 0; k < t.layers; ++k) { t.coverage[k] = p->Coverage[k]; t.layerPrimitive[k] = p->LayerPrimitive[k]; }
-        mStatus = vqhip_scene_depth(mCtx, p->Stream, numDraws ? p->Draws->data() : nullptr, numDraws, (int)mWidth, (int)mHeight, p->bMSAA ? 4 : 1, &t, mWork, mWorkBytes);
+        const vqhip_scene_depth_targets t = Targets(*p);
+        mStatus = vqhip_scene_depth(mCtx, p->Stream, numDraws ? p->Draws->data() : nullptr, numDraws, (int)mWidth, (int)mHeight, p->bMSAA ? 4 : 1, &t, mWork.ptr, mWork.bytes);
     }
-    const void* GetWorkBuffer() const { return mWork; }
-    size_t GetWorkBytes() const { return mWorkBytes; }
+    static vqhip_scene_depth_targets Targets(const FDrawParameters& p) {        // shared with MaskedDepthPrePass; the layer planes exist with MSAA only
+        vqhip_scene_depth_targets t = {};
+        t.depth = p.SceneDepth; t.primitive = p.Primitive; t.layers = p.bMSAA ? p.NumLayers : 0;
+        for (int k = 0; k < t.layers; ++k) { t.coverage[k] = p.Coverage[k]; t.layerPrimitive[k] = p.LayerPrimitive[k]; }
+        return t;
+    }
+    const void* GetWorkBuffer() const { return mWork.ptr; }
+    size_t GetWorkBytes() const { return mWork.bytes; }
 private:
-    void* mWork = nullptr; size_t mWorkBytes = 0;
+    WorkBuffer mWork;
     unsigned mWidth = 0, mHeight = 0;
 };
 
@@ -633,20 +645,11 @@ public:
         const vqhip_material* Materials = nullptr; int NumMaterials = 0;        // HOST
     };
     explicit MaskedDepthPrePass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
-    ~MaskedDepthPrePass() override { Free(mWork); }
     bool Initialize() override { return mCtx != nullptr; }
-    void Destroy() override { Free(mWork); mWorkBytes = 0; }
+    void Destroy() override { mWork.Release(); }
     void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override { mWidth = Width; mHeight = Height; }
     void OnDestroyWindowSizeDependentResources() override { mWidth = mHeight = 0; }
-    bool Reserve(uint64_t InstancedTriangles, uint64_t MaskedInstancedTriangles, int NumDraws) {
-        const size_t need = vqhip_scene_masked_depth_work_bytes(InstancedTriangles, MaskedInstancedTriangles, NumDraws);
-        if (!need) return false;
-        if (need <= mWorkBytes) return true;
-        Free(mWork); mWorkBytes = 0;
-        mWork = Alloc(need);
-        if (mWork) mWorkBytes = need;
-        return mWork != nullptr;
-    }
+    bool Reserve(uint64_t InstancedTriangles, uint64_t MaskedInstancedTriangles, int NumDraws) { return mWork.Reserve(vqhip_scene_masked_depth_work_bytes(InstancedTriangles, MaskedInstancedTriangles, NumDraws)); }
     void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
         const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
         if (!p || p->NumLayers < 0 || p->NumLayers > VQHIP_SCENE_DEPTH_MAX_LAYERS) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
@@ -660,22 +663,20 @@ public:
             const int32_t index = p->MaterialIndex ? (*p->MaterialIndex)[(size_t)d] : -1;
             if (index >= p->NumMaterials || (index >= 0 && !p->Materials)) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
             m.material = index >= 0 ? p->Materials + index : nullptr;
-            const uint64_t n = (uint64_t)(m.draw.mesh.numIndices / 3) * m.draw.numInstances;
+            const uint64_t n = InstancedTriangles(m.draw);
             triangles += n;
             if (m.material && (m.material->texDiffuse.reserved & VQHIP_MATERIAL_ALPHA_MASKED)) masked += n;
         }
         mMaskedTriangles = masked;
         if (!Reserve(triangles, masked, numDraws)) { mStatus = VQHIP_ERR_HIP; return; }
-        vqhip_scene_depth_targets t = {};
-        t.depth = p->SceneDepth; t.primitive = p->Primitive; t.layers = p->bMSAA ? p->NumLayers : 0;
-        for (int k = 0; k < t.layers; ++k) { t.coverage[k] = p->Coverage[k]; t.layerPrimitive[k] = p->LayerPrimitive[k]; }
-        mStatus = vqhip_scene_masked_depth(mCtx, p->Stream, numDraws ? mDraws.data() : nullptr, numDraws, (int)mWidth, (int)mHeight, p->bMSAA ? 4 : 1, &t, mWork, mWorkBytes);
+        const vqhip_scene_depth_targets t = DepthPrePass::Targets(*p);
+        mStatus = vqhip_scene_masked_depth(mCtx, p->Stream, numDraws ? mDraws.data() : nullptr, numDraws, (int)mWidth, (int)mHeight, p->bMSAA ? 4 : 1, &t, mWork.ptr, mWork.bytes);
     }
-    const void* GetWorkBuffer() const { return mWork; }
-    size_t GetWorkBytes() const { return mWorkBytes; }
+    const void* GetWorkBuffer() const { return mWork.ptr; }
+    size_t GetWorkBytes() const { return mWork.bytes; }
     uint64_t LastMaskedTriangles() const { return mMaskedTriangles; }
 private:
-    void* mWork = nullptr; size_t mWorkBytes = 0;
+    WorkBuffer mWork;
     unsigned mWidth = 0, mHeight = 0;
     uint64_t mMaskedTriangles = 0;
     std::vector<vqhip_scene_masked_depth_draw> mDraws;                          // consumed by the call before it returns; kept to spare the allocation
@@ -698,70 +699,48 @@ public:
         const vqhip_material* Materials = nullptr; int NumMaterials = 0;        // HOST
     };
     explicit MaskedShadowDepthPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
-    ~MaskedShadowDepthPass() override { Free(mWork); }
     bool Initialize() override { return mCtx != nullptr; }
-    void Destroy() override { Free(mWork); mWorkBytes = 0; }
+    void Destroy() override { mWork.Release(); }
     void OnCreateWindowSizeDependentResources(unsigned, unsigned, const IRenderPassResourceCollection* = nullptr) override {}   // shadow maps do not follow the window
     void OnDestroyWindowSizeDependentResources() override {}
-    bool Reserve(uint64_t InstancedTriangles, uint64_t MaskedInstancedTriangles, int NumDraws) {
-        const size_t need = vqhip_shadow_masked_depth_work_bytes(InstancedTriangles, MaskedInstancedTriangles, VQHIP_SHADOW_MAX_VIEWS, NumDraws);
-        if (!need) return false;
-        if (need <= mWorkBytes) return true;
-        Free(mWork); mWorkBytes = 0;
-        mWork = Alloc(need);
-        if (mWork) mWorkBytes = need;
-        return mWork != nullptr;
-    }
+    bool Reserve(uint64_t InstancedTriangles, uint64_t MaskedInstancedTriangles, int NumDraws) { return mWork.Reserve(vqhip_shadow_masked_depth_work_bytes(InstancedTriangles, MaskedInstancedTriangles, VQHIP_SHADOW_MAX_VIEWS, NumDraws)); }
     void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
         const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
         if (!p || p->NumSpotShadowViews > VQ_NUM_SHADOWING_LIGHTS__SPOT || p->NumPointShadowViews > VQ_NUM_SHADOWING_LIGHTS__POINT) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
-        constexpr int kMaxViews = 1 + VQ_NUM_SHADOWING_LIGHTS__SPOT + 6 * VQ_NUM_SHADOWING_LIGHTS__POINT;
-        vqhip_shadow_masked_view views[kMaxViews];
-        size_t first[kMaxViews];                                                 // where each view's draws start in mDraws (the vector may move while it grows)
-        int n = 0;
+        vqhip_shadow_masked_view views[ShadowDepthPass::kMaxViews];
+        size_t first[ShadowDepthPass::kMaxViews];                                // where each view's draws start in mDraws (the vector may move while it grows)
         uint64_t triangles = 0, masked = 0;
         bool ok = true;
         mDraws.clear();
-        auto add = [&](const std::vector<vqhip_shadow_draw>* draws, const std::vector<int32_t>* index, float* map, int dim, int linear, VQ_float3 pos, float farPlane) {
-            if (!draws || draws->empty()) return;
-            if (index && index->size() != draws->size()) { ok = false; return; }
-            vqhip_shadow_masked_view& v = views[n];
-            v.depth = map; v.pitchBytes = 0; v.dim = dim; v.linearDepth = linear; v.cameraPosition = pos; v.farPlane = farPlane;
-            v.draws = nullptr; v.numDraws = (int32_t)draws->size();
-            first[n++] = mDraws.size();
-            for (size_t d = 0; d < draws->size(); ++d) {
+        const int n = ShadowDepthPass::WalkViews(*p, views, [&](vqhip_shadow_masked_view& v, const std::vector<vqhip_shadow_draw>& draws, ShadowDepthPass::ViewKind kind, unsigned slot) {
+            const std::vector<int32_t>* index = kind == ShadowDepthPass::kDirectional ? p->DirectionalMaterialIndex : kind == ShadowDepthPass::kSpot ? p->SpotMaterialIndex[slot] : p->PointMaterialIndex[slot];
+            if (index && index->size() != draws.size()) { ok = false; return; }
+            first[&v - views] = mDraws.size();
+            for (size_t d = 0; d < draws.size(); ++d) {
                 vqhip_shadow_masked_draw m;
-                m.draw = (*draws)[d];
+                m.draw = draws[d];
                 m.texDiffuseAlpha = nullptr;
                 const int32_t k = index ? (*index)[d] : -1;
                 if (k >= p->NumMaterials || (k >= 0 && !p->Materials)) { ok = false; return; }
-                const uint64_t t = (uint64_t)(m.draw.mesh.numIndices / 3) * m.draw.numInstances;
+                const uint64_t t = InstancedTriangles(m.draw);
                 triangles += t;
                 if (k >= 0 && (p->Materials[k].texDiffuse.reserved & VQHIP_MATERIAL_ALPHA_MASKED)) { m.texDiffuseAlpha = &p->Materials[k].texDiffuse; masked += t; }
                 mDraws.push_back(m);
             }
-        };
-        const VQ_float3 zero = { 0.0f, 0.0f, 0.0f };
-        add(p->DirectionalDraws, p->DirectionalMaterialIndex, p->ShadowMapsDirectional, p->DirectionalDim, 0, zero, 1.0f);
-        for (unsigned i = 0; i < p->NumSpotShadowViews; ++i)
-            add(p->SpotDraws[i], p->SpotMaterialIndex[i], p->ShadowMapsSpot ? p->ShadowMapsSpot + (size_t)i * p->SpotDim * p->SpotDim : nullptr, p->SpotDim, 0, zero, 1.0f);
-        for (unsigned i = 0; i < p->NumPointShadowViews; ++i)
-            for (unsigned face = 0; face < 6; ++face)
-                add(p->PointDraws[i * 6 + face], p->PointMaterialIndex[i * 6 + face],
-                    p->ShadowMapsPoint ? p->ShadowMapsPoint + (size_t)(i * 6 + face) * p->PointDim * p->PointDim : nullptr, p->PointDim, 1, p->PointPosition[i], p->PointRange[i]);
+        });
         if (!ok) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
         mNumViews = n; mMaskedTriangles = masked;
         if (n == 0) { mStatus = VQHIP_OK; return; }                              // nothing casts a shadow this frame
         for (int v = 0; v < n; ++v) views[v].draws = mDraws.data() + first[v];
         if (!Reserve(triangles, masked, (int)mDraws.size())) { mStatus = VQHIP_ERR_HIP; return; }
-        mStatus = vqhip_shadow_masked_depth(mCtx, p->Stream, views, n, mWork, mWorkBytes);
+        mStatus = vqhip_shadow_masked_depth(mCtx, p->Stream, views, n, mWork.ptr, mWork.bytes);
     }
-    const void* GetWorkBuffer() const { return mWork; }
-    size_t GetWorkBytes() const { return mWorkBytes; }
+    const void* GetWorkBuffer() const { return mWork.ptr; }
+    size_t GetWorkBytes() const { return mWork.bytes; }
     int LastViewCount() const { return mNumViews; }
     uint64_t LastMaskedTriangles() const { return mMaskedTriangles; }
 private:
-    void* mWork = nullptr; size_t mWorkBytes = 0;
+    WorkBuffer mWork;
     int mNumViews = 0;
     uint64_t mMaskedTriangles = 0;
     std::vector<vqhip_shadow_masked_draw> mDraws;                               // all views' draws, consumed by the call before it returns
@@ -787,20 +766,11 @@ public:
         void* SvPositionCurr = nullptr; void* SvPositionPrev = nullptr;         // both or neither
     };
     explicit SceneInterpolantsPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
-    ~SceneInterpolantsPass() override { Free(mWork); }
     bool Initialize() override { return mCtx != nullptr; }
-    void Destroy() override { Free(mWork); mWorkBytes = 0; }
+    void Destroy() override { mWork.Release(); }
     void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override { mWidth = Width; mHeight = Height; }
     void OnDestroyWindowSizeDependentResources() override { mWidth = mHeight = 0; }
-    bool Reserve(int NumDraws) {
-        const size_t need = vqhip_scene_interpolants_work_bytes(NumDraws);
-        if (!need) return false;
-        if (need <= mWorkBytes) return true;
-        Free(mWork); mWorkBytes = 0;
-        mWork = Alloc(need);
-        if (mWork) mWorkBytes = need;
-        return mWork != nullptr;
-    }
+    bool Reserve(int NumDraws) { return mWork.Reserve(vqhip_scene_interpolants_work_bytes(NumDraws)); }
     void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
         const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
         if (!p) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
@@ -809,12 +779,12 @@ public:
         vqhip_scene_interpolant_targets t = {};
         t.ip0 = p->Ip0; t.ip1 = p->Ip1; t.ip2 = p->Ip2; t.svPositionCurr = p->SvPositionCurr; t.svPositionPrev = p->SvPositionPrev;
         mStatus = vqhip_scene_interpolants(mCtx, p->Stream, numDraws ? p->Draws->data() : nullptr, numDraws, (int)mWidth, (int)mHeight, p->Owner, p->OwnerPitch, &t,
-                                           mWork, mWorkBytes);
+                                           mWork.ptr, mWork.bytes);
     }
-    const void* GetWorkBuffer() const { return mWork; }
-    size_t GetWorkBytes() const { return mWorkBytes; }
+    const void* GetWorkBuffer() const { return mWork.ptr; }
+    size_t GetWorkBytes() const { return mWork.bytes; }
 private:
-    void* mWork = nullptr; size_t mWorkBytes = 0;
+    WorkBuffer mWork;
     unsigned mWidth = 0, mHeight = 0;
 };
 
@@ -831,20 +801,11 @@ public:
         int QuadPitch = 0;                                                      // pixels per row, 0 = W
     };
     explicit QuadInterpolantsPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
-    ~QuadInterpolantsPass() override { Free(mWork); }
     bool Initialize() override { return mCtx != nullptr; }
-    void Destroy() override { Free(mWork); mWorkBytes = 0; mQuadUV = nullptr; mQuadPitch = 0; }
+    void Destroy() override { mWork.Release(); mQuadUV = nullptr; mQuadPitch = 0; }
     void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override { mWidth = Width; mHeight = Height; }
     void OnDestroyWindowSizeDependentResources() override { mWidth = mHeight = 0; mQuadUV = nullptr; mQuadPitch = 0; }
-    bool Reserve(int NumDraws) {
-        const size_t need = vqhip_scene_interpolants_work_bytes(NumDraws);
-        if (!need) return false;
-        if (need <= mWorkBytes) return true;
-        Free(mWork); mWorkBytes = 0;
-        mWork = Alloc(need);
-        if (mWork) mWorkBytes = need;
-        return mWork != nullptr;
-    }
+    bool Reserve(int NumDraws) { return mWork.Reserve(vqhip_scene_interpolants_work_bytes(NumDraws)); }
     void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
         const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
         mQuadUV = nullptr; mQuadPitch = 0;
@@ -855,15 +816,15 @@ public:
         t.planes.ip0 = p->Ip0; t.planes.ip1 = p->Ip1; t.planes.ip2 = p->Ip2; t.planes.svPositionCurr = p->SvPositionCurr; t.planes.svPositionPrev = p->SvPositionPrev;
         t.quadUV = p->QuadUV; t.quad_pitch = p->QuadPitch;
         mStatus = vqhip_scene_quad_interpolants(mCtx, p->Stream, numDraws ? p->Draws->data() : nullptr, numDraws, (int)mWidth, (int)mHeight, p->Owner, p->OwnerPitch, &t,
-                                                mWork, mWorkBytes);
+                                                mWork.ptr, mWork.bytes);
         if (mStatus == VQHIP_OK) { mQuadUV = p->QuadUV; mQuadPitch = p->QuadPitch ? p->QuadPitch : (int)mWidth; }
     }
-    const void* GetWorkBuffer() const { return mWork; }
-    size_t GetWorkBytes() const { return mWorkBytes; }
+    const void* GetWorkBuffer() const { return mWork.ptr; }
+    size_t GetWorkBytes() const { return mWork.bytes; }
     const void* GetQuadUV() const { return mQuadUV; }            // nullptr until a call succeeded
     int GetQuadPitch() const { return mQuadPitch; }              // pixels per row
 private:
-    void* mWork = nullptr; size_t mWorkBytes = 0;
+    WorkBuffer mWork;
     const void* mQuadUV = nullptr; int mQuadPitch = 0;
     unsigned mWidth = 0, mHeight = 0;
 };

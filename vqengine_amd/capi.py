@@ -169,6 +169,47 @@ EXPORTED_SYMBOLS = [
 ]
 
 
+def _check_vertices(who, name, p, k):           # this and the helpers below: what the three rasteriser bindings (_*_prepared) check and fill alike
+    if not (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and p.shape[1] >= k and p.stride(1) == 1 and p.stride(0) >= p.shape[1]):
+        raise ValueError(f"{who}: {name}: expected cuda float32 [V, k >= {k}] with unit column stride")
+
+
+def _check_indices(who, ix):                    # -> the index width in bits
+    bits = {2: 16, 4: 32}.get(ix.element_size()) if not ix.dtype.is_floating_point else None
+    if not (ix.is_cuda and ix.dim() == 1 and ix.is_contiguous() and bits and ix.numel() % 3 == 0):
+        raise ValueError(f"{who}: indices: expected a contiguous cuda 1-D 16-bit or 32-bit integer tensor whose length is a multiple of 3")
+    return bits
+
+
+def _check_matrix_blocks(who, blocks, same=""):
+    """blocks: (name, tensor, optional: may be None), the first one sets n; `same` ends the message -> n, the instance count"""
+    n = blocks[0][1].shape[0] if blocks[0][1].dim() == 3 else 0
+    for name, m, optional in blocks:
+        if not (optional if m is None else m.is_cuda and m.dtype == torch.float32 and tuple(m.shape) == (n, 4, 4) and m.is_contiguous()):
+            raise ValueError(f"{who}: {name}: expected cuda float32 [n, 4, 4] contiguous{same}")
+    return n
+
+
+def _check_instances_cull(who, n, limit, cull=abi.CULL_NONE):
+    if not 1 <= n <= limit:
+        raise ValueError(f"{who}: 1..{limit} instances, got {n}")
+    if cull not in (abi.CULL_NONE, abi.CULL_FRONT, abi.CULL_BACK):
+        raise ValueError(f"{who}: cull: expected abi.CULL_NONE, CULL_FRONT or CULL_BACK")
+
+
+def _fill_mesh(c, p, ix, bits, empty_indices=None):     # empty_indices: the address an index tensor without elements (which has none) is given
+    c.mesh.positions, c.mesh.strideBytes, c.mesh.numVertices = p.data_ptr(), p.stride(0) * 4, p.shape[0]
+    c.mesh.indices, c.mesh.indexBits, c.mesh.numIndices = ix.data_ptr() or empty_indices, bits, ix.numel()
+
+
+def _work_tensor(who, work, need, device, zero=""):     # allocated when None, else checked; zero: what need == 0 means, where it is refused
+    if work is None:
+        work = torch.empty((need,), dtype=torch.uint8, device=device)
+    if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.numel() >= need and (need or not zero)):
+        raise ValueError(f"{who}: work: expected a contiguous cuda uint8 tensor of at least {need} bytes{zero}")
+    return work
+
+
 def scene_interpolants_work_bytes(num_draws):
     """vqhip_scene_interpolants_work_bytes: the work buffer (the draw table's device home) of a vqhip_scene_interpolants call of `num_draws` draws. Host-only."""
     return load_library().vqhip_scene_interpolants_work_bytes(int(num_draws))
@@ -666,21 +707,10 @@ class Context:
             for j, dr in enumerate(v.draws):
                 who = f"{who_}: view {i} draw {j}"
                 p, ix = dr.positions, dr.indices
-                if not (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and p.shape[1] >= 3 and p.stride(1) == 1 and p.stride(0) >= p.shape[1]):
-                    raise ValueError(f"{who}: positions: expected cuda float32 [V, k >= 3] with unit column stride")
-                bits = {2: 16, 4: 32}.get(ix.element_size()) if not ix.dtype.is_floating_point else None
-                if not (ix.is_cuda and ix.dim() == 1 and ix.is_contiguous() and bits and ix.numel() % 3 == 0):
-                    raise ValueError(f"{who}: indices: expected a contiguous cuda 1-D 16-bit or 32-bit integer tensor whose length is a multiple of 3")
-                n = dr.wvp.shape[0] if dr.wvp.dim() == 3 else 0
-                for name, m in (("wvp", dr.wvp), ("world", dr.world)):
-                    if m is None and name == "world" and not v.linear:
-                        continue
-                    if m is None or not (m.is_cuda and m.dtype == torch.float32 and tuple(m.shape) == (n, 4, 4) and m.is_contiguous()):
-                        raise ValueError(f"{who}: {name}: expected cuda float32 [n, 4, 4] contiguous, n the same for wvp and world")
-                if not 1 <= n <= abi.SHADOW_MAX_INSTANCES:
-                    raise ValueError(f"{who}: 1..{abi.SHADOW_MAX_INSTANCES} instances, got {n}")
-                if dr.cull not in (abi.CULL_NONE, abi.CULL_FRONT, abi.CULL_BACK):
-                    raise ValueError(f"{who}: cull: expected abi.CULL_NONE, CULL_FRONT or CULL_BACK")
+                _check_vertices(who, "positions", p, 3)
+                bits = _check_indices(who, ix)
+                n = _check_matrix_blocks(who, (("wvp", dr.wvp, False), ("world", dr.world, not v.linear)), ", n the same for wvp and world")
+                _check_instances_cull(who, n, abi.SHADOW_MAX_INSTANCES, dr.cull)
                 c = cdraws[j]
                 if masked:
                     tex = getattr(dr, "texture", None)
@@ -693,8 +723,7 @@ class Context:
                         keep.append(tex)
                         masked_tris += (ix.numel() // 3) * n
                     c = c.draw
-                c.mesh.positions, c.mesh.strideBytes, c.mesh.numVertices = p.data_ptr(), p.stride(0) * 4, p.shape[0]
-                c.mesh.indices, c.mesh.indexBits, c.mesh.numIndices = ix.data_ptr(), bits, ix.numel()
+                _fill_mesh(c, p, ix, bits)
                 c.matWorldViewProj, c.matWorld = dr.wvp.data_ptr(), (dr.world.data_ptr() if dr.world is not None else None)
                 c.numInstances, c.cullMode = n, dr.cull
             cv = cviews[i]
@@ -704,10 +733,7 @@ class Context:
             cv.draws = C.cast(cdraws, C.POINTER(abi.ShadowMaskedDraw if masked else abi.ShadowDraw))
         tris = sum(v.instanced_triangles() for v in views)
         need = shadow_masked_depth_work_bytes(tris, masked_tris, len(views), num_draws) if masked else shadow_depth_work_bytes(tris, len(views))
-        if work is None:
-            work = torch.empty((need,), dtype=torch.uint8, device=self.device)
-        if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.numel() >= need):
-            raise ValueError(f"{who_}: work: expected a contiguous cuda uint8 tensor of at least {need} bytes")
+        work = _work_tensor(who_, work, need, self.device)
         keep.append(views)
 
         def call(stream=None, _keep=keep):
@@ -789,18 +815,10 @@ class Context:
         for j, dr in enumerate(draws):
             who = f"{who_}: draw {j}"
             p, ix = dr.positions, dr.indices
-            if not (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and p.shape[1] >= 3 and p.stride(1) == 1 and p.stride(0) >= p.shape[1]):
-                raise ValueError(f"{who}: positions: expected cuda float32 [V, k >= 3] with unit column stride")
-            bits = {2: 16, 4: 32}.get(ix.element_size()) if not ix.dtype.is_floating_point else None
-            if not (ix.is_cuda and ix.dim() == 1 and ix.is_contiguous() and bits and ix.numel() % 3 == 0):
-                raise ValueError(f"{who}: indices: expected a contiguous cuda 1-D 16-bit or 32-bit integer tensor whose length is a multiple of 3")
-            m = dr.wvp
-            if not (m.is_cuda and m.dtype == torch.float32 and m.dim() == 3 and tuple(m.shape[1:]) == (4, 4) and m.is_contiguous()):
-                raise ValueError(f"{who}: wvp: expected cuda float32 [n, 4, 4] contiguous")
-            if not 1 <= m.shape[0] <= abi.SCENE_DEPTH_MAX_INSTANCES:
-                raise ValueError(f"{who}: 1..{abi.SCENE_DEPTH_MAX_INSTANCES} instances, got {m.shape[0]}")
-            if dr.cull not in (abi.CULL_NONE, abi.CULL_FRONT, abi.CULL_BACK):
-                raise ValueError(f"{who}: cull: expected abi.CULL_NONE, CULL_FRONT or CULL_BACK")
+            _check_vertices(who, "positions", p, 3)
+            bits = _check_indices(who, ix)
+            n = _check_matrix_blocks(who, (("wvp", dr.wvp, False),))
+            _check_instances_cull(who, n, abi.SCENE_DEPTH_MAX_INSTANCES, dr.cull)
             c = cdraws[j]
             if masked:
                 mat = getattr(dr, "material", None)
@@ -812,18 +830,13 @@ class Context:
                     if mat.texDiffuse.reserved & abi.MATERIAL_ALPHA_MASKED:
                         if p.shape[1] < 11:
                             raise ValueError(f"{who}: a masked draw needs the engine's vertex, float32 [V, k >= 11] (uv at floats 9, 10)")
-                        masked_tris += (ix.numel() // 3) * m.shape[0]
+                        masked_tris += (ix.numel() // 3) * n
                 c = c.draw
-            c.mesh.positions, c.mesh.strideBytes, c.mesh.numVertices = p.data_ptr(), p.stride(0) * 4, p.shape[0]
-            c.mesh.indices, c.mesh.indexBits, c.mesh.numIndices = ix.data_ptr(), bits, ix.numel()
-            c.matWorldViewProj, c.numInstances, c.cullMode = m.data_ptr(), m.shape[0], dr.cull
-            tris += (ix.numel() // 3) * m.shape[0]
+            _fill_mesh(c, p, ix, bits)
+            c.matWorldViewProj, c.numInstances, c.cullMode = dr.wvp.data_ptr(), n, dr.cull
+            tris += (ix.numel() // 3) * n
         need = scene_masked_depth_work_bytes(tris, masked_tris, len(draws)) if masked else scene_depth_work_bytes(tris)
-        if work is None:
-            work = torch.empty((need,), dtype=torch.uint8, device=self.device)
-        if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.numel() >= need and need):
-            raise ValueError(f"{who_}: work: expected a contiguous cuda uint8 tensor of at least {need} bytes (0: too many triangles)")
-        res["work"] = work
+        res["work"] = work = _work_tensor(who_, work, need, self.device, " (0: too many triangles)")
         tg = abi.SceneDepthTargets()
         tg.depth = res["depth"].data_ptr()
         tg.primitive = res["primitive"].data_ptr() if primitive else None
@@ -886,34 +899,20 @@ class Context:
         for j, dr in enumerate(draws):
             who = f"{who_}: draw {j}"
             p, ix = dr.vertices, dr.indices
-            if not (p.is_cuda and p.dtype == torch.float32 and p.dim() == 2 and p.shape[1] >= 11 and p.stride(1) == 1 and p.stride(0) >= p.shape[1]):
-                raise ValueError(f"{who}: vertices: expected cuda float32 [V, k >= 11] with unit column stride")
-            bits = {2: 16, 4: 32}.get(ix.element_size()) if not ix.dtype.is_floating_point else None
-            if not (ix.is_cuda and ix.dim() == 1 and ix.is_contiguous() and bits and ix.numel() % 3 == 0):
-                raise ValueError(f"{who}: indices: expected a contiguous cuda 1-D 16-bit or 32-bit integer tensor whose length is a multiple of 3")
-            n = dr.wvp.shape[0] if dr.wvp.dim() == 3 else 0
-            for name, m in (("wvp", dr.wvp), ("world", dr.world), ("normal", dr.normal), ("wvp_prev", dr.wvp_prev)):
-                if m is None and name == "wvp_prev" and not sv:
-                    continue
-                if m is None or not (m.is_cuda and m.dtype == torch.float32 and tuple(m.shape) == (n, 4, 4) and m.is_contiguous()):
-                    raise ValueError(f"{who}: {name}: expected cuda float32 [n, 4, 4] contiguous, n the same for every matrix block")
-            if not 1 <= n <= abi.SCENE_DEPTH_MAX_INSTANCES:
-                raise ValueError(f"{who}: 1..{abi.SCENE_DEPTH_MAX_INSTANCES} instances, got {n}")
+            _check_vertices(who, "vertices", p, 11)
+            bits = _check_indices(who, ix)
+            n = _check_matrix_blocks(who, (("wvp", dr.wvp, False), ("world", dr.world, False), ("normal", dr.normal, False), ("wvp_prev", dr.wvp_prev, not sv)),
+                                     ", n the same for every matrix block")
+            _check_instances_cull(who, n, abi.SCENE_DEPTH_MAX_INSTANCES)
             if dr.material < 0:
                 raise ValueError(f"{who}: material: expected an index >= 0")
             c = cdraws[j]
-            c.mesh.positions, c.mesh.strideBytes, c.mesh.numVertices = p.data_ptr(), p.stride(0) * 4, p.shape[0]
             # an empty tensor has no address, and the library refuses a NULL index buffer whatever its length: an empty draw names the vertex buffer (never read)
-            c.mesh.indices, c.mesh.indexBits, c.mesh.numIndices = ix.data_ptr() or p.data_ptr(), bits, ix.numel()
+            _fill_mesh(c, p, ix, bits, empty_indices=p.data_ptr())
             c.matWorldViewProj, c.matWorld, c.matNormal = dr.wvp.data_ptr(), dr.world.data_ptr(), dr.normal.data_ptr()
             c.matWorldViewProjPrev = dr.wvp_prev.data_ptr() if dr.wvp_prev is not None else None
             c.numInstances, c.materialIndex = n, dr.material
-        need = scene_interpolants_work_bytes(len(draws))
-        if work is None:
-            work = torch.empty((need,), dtype=torch.uint8, device=self.device)
-        if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous() and work.numel() >= need):
-            raise ValueError(f"{who_}: work: expected a contiguous cuda uint8 tensor of at least {need} bytes")
-        res["work"] = work
+        res["work"] = work = _work_tensor(who_, work, scene_interpolants_work_bytes(len(draws)), self.device)
         tg = abi.SceneInterpolantTargets()
         tg.ip0, tg.ip1, tg.ip2 = res["ip0"].data_ptr(), res["ip1"].data_ptr(), res["ip2"].data_ptr()
         tg.pitch = pitches["ip"].pop()

@@ -1870,14 +1870,73 @@ int vqhip_adaptive_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "adaptive_cacao launch");
 }
 
-// ---- Shadow-map rasteriser (raster.hip; docs/DESIGN_DETAILS.md §7.16) --------------------------------------------------------------------------------------
+// ---- The rasterisers' front ends (docs/DESIGN_DETAILS.md §7.16-7.20): what the eight entry points below share -------------------------------------------------
 namespace {
-constexpr size_t kRasterJobsPerSlot = kConstSlotBytes / sizeof(RasterJob);
-constexpr size_t kRasterMaxDraws = 20000;                      // at most 29 job slots of the 32-slot ring beside the view table's
-static_assert(sizeof(RasterView) * VQHIP_SHADOW_MAX_VIEWS <= kConstSlotBytes, "the view table fits one ring slot");
-static_assert((kRasterMaxDraws + kRasterJobsPerSlot - 1) / kRasterJobsPerSlot + 1 < vqhip_ctx::kSlots, "one call never meets its own view-table slot again");
+extern "C++" {                                                 // templates and overloads: C++ linkage
+constexpr size_t kRasterMaxDraws = 20000;                      // draws with indices in one call of any rasteriser
+constexpr uint64_t kSceneMaxTriangles = (uint64_t)1 << 29;     // eight records each: the record counter is 32 bits wide; q stays far below 0xFFFFFFFF
+template <class JOB> constexpr size_t slotsFor(size_t jobs) { return (jobs + kConstSlotBytes / sizeof(JOB) - 1) / (kConstSlotBytes / sizeof(JOB)); }   // ring slots a table takes
+
+// What every rasteriser checks of a mesh draw, between its own NULL checks and its own cullMode / materialIndex / alignment / texture checks; empty = usable
+std::string badMeshDraw(const vqhip_shadow_mesh& m, uint32_t numInstances, uint32_t minStride, uint32_t maxInstances) {
+    if (m.indexBits != 16 && m.indexBits != 32) return "indexBits must be 16 or 32";
+    if (m.numIndices % 3) return "numIndices is not a multiple of 3";
+    if (m.strideBytes < minStride || m.strideBytes % 4) return "strideBytes below " + std::to_string(minStride) + " or not a multiple of 4";
+    if (numInstances < 1 || numInstances > maxInstances) return "numInstances must be 1.." + std::to_string(maxInstances);
+    return std::string();
+}
+
+// counters | boxes[fan n] | records[fan n] of a call that draws n instanced triangles; false above the rasteriser's limit or when the sizes do not fit
+struct WorkLayout { uint64_t maxTriangles, fan; size_t counterBytes, boxBytes, recordBytes; };
+constexpr WorkLayout kShadowLayout = { (uint64_t)1 << 40, 6, kRasterCounterBytes, kRasterBoxBytes, kRasterRecordBytes };
+constexpr WorkLayout kSceneLayout = { kSceneMaxTriangles - 1, kSceneFanMax, kSceneCounterBytes, kSceneBoxBytes, kSceneRecordBytes };
+bool workLayout(const WorkLayout& L, uint64_t instancedTriangles, size_t* boxes, size_t* records, size_t* total) {
+    if (instancedTriangles > L.maxTriangles) return false;
+    const uint64_t cap = instancedTriangles * L.fan;
+    const uint64_t b = L.counterBytes, r = align256(b + cap * L.boxBytes), t = align256(r + cap * L.recordBytes);
+    if (t > (uint64_t)SIZE_MAX) return false;
+    *boxes = (size_t)b; *records = (size_t)r; *total = (size_t)t;
+    return true;
+}
+
+// A host table of `count` JOBs through constant-ring slots, as many to a slot as it holds: per slot acquire, fill(job, k) for entry k = 0 .. n - 1 of the slot in
+// host ring memory, commit sizeof(JOB) * n bytes, launch(the slot's device entries, n, entries staged before) — the ONE launch that reads the slot — and release.
+// fill and launch own whatever runs across slots (the next draw, firstQ, firstMasked) or restarts in each (firstBlock: k == 0); launch returns a vqhip_status.
+template <class JOB, class FILL, class LAUNCH>
+int stageJobs(vqhip_ctx* ctx, hipStream_t st, size_t count, FILL&& fill, LAUNCH&& launch) {
+    constexpr size_t perSlot = kConstSlotBytes / sizeof(JOB);
+    static_assert(perSlot >= 1, "a ring slot holds at least one job");
+    for (size_t done = 0; done < count;) {
+        int slot;
+        if (int rc = acquireSlot(ctx, &slot)) return rc;
+        JOB* jobs = (JOB*)(ctx->hostRing + (size_t)slot * kConstSlotBytes);
+        const size_t n = count - done < perSlot ? count - done : perSlot;
+        for (size_t k = 0; k < n; ++k) fill(jobs[k], k);
+        if (int rc = commitSlot(ctx, slot, sizeof(JOB) * n, st)) return rc;
+        if (int rc = launch((const JOB*)(ctx->devRing + (size_t)slot * kConstSlotBytes), n, done)) return rc;
+        if (int rc = releaseSlot(ctx, slot, st)) return rc;
+        done += n;
+    }
+    return VQHIP_OK;
+}
+// the launch of a table that needs a home beyond its slots: k_table_copy of the slot's n entries to dst
+template <class JOB>
+int copySlotToTable(vqhip_ctx* ctx, hipStream_t st, const JOB* src, size_t n, JOB* dst, const std::string& who) {
+    hipError_t e = launch_table_copy(st, src, dst, (uint32_t)(n * (sizeof(JOB) / 16)));
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (who + " table-copy launch").c_str());
+}
+// what a setup job takes of its draw's mesh; returns the draw's instanced triangles and takes its blocks of the slot's setup launch
+template <class JOB, class DRAW>
+uint64_t meshJob(JOB& J, const DRAW& D, uint64_t& blocks) {
+    J.positions = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices; J.wvp = D.matWorldViewProj;
+    J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numTris = D.mesh.numIndices / 3; J.numInstances = D.numInstances;
+    J.indexBits = D.mesh.indexBits; J.cullMode = D.cullMode; J.firstBlock = (uint32_t)blocks;
+    const uint64_t tris = (uint64_t)J.numTris * J.numInstances;
+    blocks += (tris + 255) / 256;
+    return tris;
+}
+
 // ---- §7.19: what the masked entry points add to both rasterisers' host side ----
-constexpr size_t kMaskTexPerSlot = kConstSlotBytes / sizeof(MaskTex);
 int hostTrunc(float x) { return x != x ? 0 : (int)(x < -2147483520.0f ? -2147483520.0f : x > 2147483520.0f ? 2147483520.0f : x); }     // vq_devmath.h f2i_trunc
 const char* badMaskTexture(const vqhip_texture2d& t) {        // NULL = usable
     if (!t.texels) return nullptr;                             // a null SRV samples 0
@@ -1886,15 +1945,6 @@ const char* badMaskTexture(const vqhip_texture2d& t) {        // NULL = usable
     if ((uintptr_t)t.texels % 4) return "masked texture: texels must be 4-byte aligned";
     return nullptr;
 }
-constexpr size_t kRasterMaxMaskedDraws = 10000;                // vqhip_shadow_masked_depth with a masked draw: table slots + job slots + the view table's stay inside the ring
-static_assert((kRasterMaxMaskedDraws + kMaskTexPerSlot - 1) / kMaskTexPerSlot + (kRasterMaxMaskedDraws + kConstSlotBytes / sizeof(RasterMaskedJob) - 1) / (kConstSlotBytes / sizeof(RasterMaskedJob)) + 1
-              < vqhip_ctx::kSlots, "one masked call never meets its own view-table slot again");
-// What the kernels' range guards rest on (vq_raster_mask.h loadMaskTri, the `at < sideCap` of both setup kernels: memory safety only — a guard that fired would
-// draw a masked triangle solid, so these must hold): (1) a job's firstMasked is the running sum, ACROSS ring slots, of numTris * numInstances of the jobs before it
-// whose maskSlot != 0, in the order the table was filled; (2) MaskArgs.sideCap is that sum over the whole call — sideTris in the scene call (draws that can discard),
-// maskedTris in the shadow call (draws with a texture) — and never exceeds the masked count the work size was computed from; (3) 1 + the side index fits the
-// record's 32-bit stamp: below 2^29 instanced triangles in a scene call, below 2^32 / 6 per view and 2^40 per call checked as 32 bits in a shadow call — the shadow
-// call therefore refuses 2^32 - 1 or more masked instanced triangles; (4) MaskArgs.tableCap is the number of table entries staged, and maskSlot - 1 indexes them.
 // prefix | MaskTex[numDraws] | MaskSide[masked]; false when the sizes do not fit
 bool maskLayout(size_t prefix, uint64_t instancedTriangles, uint64_t maskedTriangles, int numDraws, size_t* table, size_t* side, size_t* total) {
     if (!prefix || numDraws < 0 || maskedTriangles > instancedTriangles) return false;
@@ -1903,24 +1953,29 @@ bool maskLayout(size_t prefix, uint64_t instancedTriangles, uint64_t maskedTrian
     *table = (size_t)tb; *side = (size_t)sd; *total = (size_t)t;
     return true;
 }
-// the table of a masked call into the work buffer, through ring slots (one k_table_copy launch per slot), as vqhip_scene_interpolants stages its draw table
-int stageMaskTable(vqhip_ctx* ctx, hipStream_t st, const std::vector<MaskTex>& host, MaskTex* dev, const char* who) {
-    size_t done = 0;
-    while (done < host.size()) {
-        int slot;
-        if (int rc = acquireSlot(ctx, &slot)) return rc;
-        const size_t n = host.size() - done < kMaskTexPerSlot ? host.size() - done : kMaskTexPerSlot;
-        std::memcpy(ctx->hostRing + (size_t)slot * kConstSlotBytes, host.data() + done, n * sizeof(MaskTex));
-        if (int rc = commitSlot(ctx, slot, n * sizeof(MaskTex), st)) return rc;
-        hipError_t e = launch_table_copy(st, ctx->devRing + (size_t)slot * kConstSlotBytes, dev + done, (uint32_t)(n * (sizeof(MaskTex) / 16)));
-        if (e != hipSuccess) return failHip(ctx, e, (std::string(who) + " table-copy launch").c_str());
-        if (int rc = releaseSlot(ctx, slot, st)) return rc;
-        done += n;
-    }
-    return VQHIP_OK;
+// What the kernels' range guards rest on (vq_raster_mask.h loadMaskTri, the `at < sideCap` of both setup kernels: memory safety only — a guard that fired would
+// draw a masked triangle solid, so these must hold): (1) a job's firstMasked is the running sum, ACROSS ring slots, of numTris * numInstances of the jobs before it
+// whose maskSlot != 0, in the order the table was filled; (2) MaskArgs.sideCap is that sum over the whole call — sideTris in the scene call (draws that can discard),
+// maskedTris in the shadow call (draws with a texture) — and never exceeds the masked count the work size was computed from; (3) 1 + the side index fits the
+// record's 32-bit stamp: below 2^29 instanced triangles in a scene call, below 2^32 / 6 per view and 2^40 per call checked as 32 bits in a shadow call — the shadow
+// call therefore refuses 2^32 - 1 or more masked instanced triangles; (4) MaskArgs.tableCap is the number of table entries staged, and maskSlot - 1 indexes them.
+template <class JOB>
+void maskJob(JOB& J, uint32_t maskSlot, uint64_t& firstMasked, uint64_t tris) {
+    J.maskSlot = maskSlot; J.firstMasked = (uint32_t)firstMasked;
+    if (maskSlot) firstMasked += tris;
 }
-// the two draw types of each rasteriser behind one set of accessors (overloads: C++ linkage)
-extern "C++" {
+// The MaskArgs of a call, all zero when no draw of it is alpha-tested; else its table goes into the work buffer, through ring slots (one k_table_copy launch per
+// slot), as vqhip_scene_interpolants stages its draw table
+int stageMask(vqhip_ctx* ctx, hipStream_t st, const std::vector<MaskTex>& table, void* work, size_t offTable, size_t offSide, uint64_t sideCap, const std::string& who, MaskArgs* ma) {
+    std::memset(ma, 0, sizeof(*ma));
+    if (table.empty()) return VQHIP_OK;
+    MaskTex* dev = (MaskTex*)((char*)work + offTable);
+    ma->table = dev; ma->side = (MaskSide*)((char*)work + offSide); ma->sideCap = sideCap; ma->tableCap = (uint32_t)table.size();
+    size_t next = 0;
+    return stageJobs<MaskTex>(ctx, st, table.size(), [&](MaskTex& t, size_t) { t = table[next++]; },
+                              [&](const MaskTex* src, size_t n, size_t first) { return copySlotToTable(ctx, st, src, n, dev + first, who); });
+}
+// the two draw types of each rasteriser behind one set of accessors
 const vqhip_shadow_draw& baseDraw(const vqhip_shadow_draw& d) { return d; }
 const vqhip_shadow_draw& baseDraw(const vqhip_shadow_masked_draw& d) { return d.draw; }
 const vqhip_texture2d* maskTexture(const vqhip_shadow_draw&) { return nullptr; }
@@ -1930,21 +1985,18 @@ const vqhip_scene_depth_draw& baseDraw(const vqhip_scene_masked_depth_draw& d) {
 const vqhip_material* maskMaterial(const vqhip_scene_depth_draw&) { return nullptr; }
 const vqhip_material* maskMaterial(const vqhip_scene_masked_depth_draw& d) { return d.material && (d.material->texDiffuse.reserved & VQHIP_MATERIAL_ALPHA_MASKED) ? d.material : nullptr; }
 } // extern "C++"
-
-// counters | boxes[6 n] | records[6 n]; false when the sizes do not fit
-bool rasterLayout(uint64_t instancedTriangles, size_t* boxes, size_t* records, size_t* total) {
-    if (instancedTriangles > ((uint64_t)1 << 40)) return false;
-    const uint64_t cap = instancedTriangles * 6;
-    const uint64_t b = kRasterCounterBytes, r = align256(b + cap * kRasterBoxBytes), t = align256(r + cap * kRasterRecordBytes);
-    if (t > (uint64_t)SIZE_MAX) return false;
-    *boxes = (size_t)b; *records = (size_t)r; *total = (size_t)t;
-    return true;
-}
 } // namespace
+
+// ---- Shadow-map rasteriser (raster.hip; docs/DESIGN_DETAILS.md §7.16) --------------------------------------------------------------------------------------
+// The view table's slot is held for the whole call: the mask table's and the jobs' slots must not lap the ring onto it
+static_assert(sizeof(RasterView) * VQHIP_SHADOW_MAX_VIEWS <= kConstSlotBytes, "the view table fits one ring slot");
+static_assert(slotsFor<RasterJob>(kRasterMaxDraws) + 1 < vqhip_ctx::kSlots, "one call never meets its own view-table slot again");
+constexpr size_t kRasterMaxMaskedDraws = 10000;                // vqhip_shadow_masked_depth with a masked draw: table slots + job slots + the view table's stay inside the ring
+static_assert(slotsFor<MaskTex>(kRasterMaxMaskedDraws) + slotsFor<RasterMaskedJob>(kRasterMaxMaskedDraws) + 1 < vqhip_ctx::kSlots, "one masked call never meets its own view-table slot again");
 
 size_t vqhip_shadow_depth_work_bytes(uint64_t instancedTriangles, int numViews) {
     size_t b, r, t;
-    if (numViews < 1 || numViews > VQHIP_SHADOW_MAX_VIEWS || !rasterLayout(instancedTriangles, &b, &r, &t)) return 0;
+    if (numViews < 1 || numViews > VQHIP_SHADOW_MAX_VIEWS || !workLayout(kShadowLayout, instancedTriangles, &b, &r, &t)) return 0;
     return t;
 }
 
@@ -1959,7 +2011,7 @@ int shadowDepthCall(vqhip_ctx* ctx, void* stream, const VIEW* views, int numView
     if (numViews < 1 || numViews > VQHIP_SHADOW_MAX_VIEWS) return fail(ctx, VQHIP_ERR_INVALID_ARG, who + ": numViews must be 1..64");
     if ((uintptr_t)work % 256) return fail(ctx, VQHIP_ERR_INVALID_ARG, who + ": work must be 256-byte aligned");
     const int tile = ctx->opt.rasterTile ? ctx->opt.rasterTile : 32;
-    auto bad = [&](int v, int d, const char* m) {
+    auto bad = [&](int v, int d, const std::string& m) {
         return fail(ctx, VQHIP_ERR_INVALID_ARG, who + ": view " + std::to_string(v) + (d >= 0 ? " draw " + std::to_string(d) : std::string()) + ": " + m);
     };
     RasterView hv[VQHIP_SHADOW_MAX_VIEWS];
@@ -1983,10 +2035,7 @@ int shadowDepthCall(vqhip_ctx* ctx, void* stream, const VIEW* views, int numView
             const vqhip_texture2d* tex = maskTexture(V.draws[d]);
             if (!D.mesh.positions || !D.mesh.indices || !D.matWorldViewProj) return bad(v, d, "positions, indices or matWorldViewProj is NULL");
             if (V.linearDepth && !D.matWorld) return bad(v, d, "matWorld is NULL in a linear-depth view");
-            if (D.mesh.indexBits != 16 && D.mesh.indexBits != 32) return bad(v, d, "indexBits must be 16 or 32");
-            if (D.mesh.numIndices % 3) return bad(v, d, "numIndices is not a multiple of 3");
-            if (D.mesh.strideBytes < 12 || D.mesh.strideBytes % 4) return bad(v, d, "strideBytes below 12 or not a multiple of 4");
-            if (D.numInstances < 1 || D.numInstances > VQHIP_SHADOW_MAX_INSTANCES) return bad(v, d, "numInstances must be 1..128");
+            if (const std::string m = badMeshDraw(D.mesh, D.numInstances, 12, VQHIP_SHADOW_MAX_INSTANCES); !m.empty()) return bad(v, d, m);
             if (D.cullMode != VQHIP_CULL_NONE && D.cullMode != VQHIP_CULL_FRONT && D.cullMode != VQHIP_CULL_BACK) return bad(v, d, "unknown cullMode");
             if ((uintptr_t)D.mesh.positions % 4 || (uintptr_t)D.matWorldViewProj % 4 || (uintptr_t)D.matWorld % 4 || (uintptr_t)D.mesh.indices % (D.mesh.indexBits / 8))
                 return bad(v, d, "positions / matrices must be 4-byte aligned, indices aligned to their size");
@@ -2022,13 +2071,12 @@ int shadowDepthCall(vqhip_ctx* ctx, void* stream, const VIEW* views, int numView
     if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": more than 20000 draws in one call");
     if ((totalTris + 255) / 256 + numJobs > 0x7fffffffull) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": more than 2^31 triangle lanes in one call");
     size_t offBoxes, offRecords, need, offTable = 0, offSide = 0;
-    bool fits = rasterLayout(totalTris, &offBoxes, &offRecords, &need);
+    bool fits = workLayout(kShadowLayout, totalTris, &offBoxes, &offRecords, &need);
     if (fits && kMaskedEntry) fits = numDrawsAll <= 0x7fffffffu && maskLayout(need, totalTris, maskedTris, (int)numDrawsAll, &offTable, &offSide, &need);
     if (!fits || workBytes < need)
         return fail(ctx, VQHIP_ERR_INVALID_ARG, who + (kMaskedEntry ? ": workBytes below vqhip_shadow_masked_depth_work_bytes(the call's instanced and masked instanced triangles, numViews, the views' draws)"
                                                                      : ": workBytes below vqhip_shadow_depth_work_bytes(the call's instanced triangles, numViews)"));
     const bool anyMasked = !table.empty();
-    // the view table's slot is held for the whole call: the table's and the larger jobs' slots must not lap the ring onto it
     if (anyMasked && numJobs > kRasterMaxMaskedDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": more than 10000 draws in one call that has a masked draw");
     if (maskedTris >= 0xffffffffull) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": 2^32 - 1 or more masked instanced triangles in one call");      // the record's 32-bit stamp
     for (int v = 0; v < numViews; ++v) {
@@ -2046,53 +2094,32 @@ int shadowDepthCall(vqhip_ctx* ctx, void* stream, const VIEW* views, int numView
     if (int rc = commitSlot(ctx, viewSlot, sizeof(RasterView) * numViews, st)) return rc;
     const RasterView* dviews = (const RasterView*)(ctx->devRing + (size_t)viewSlot * kConstSlotBytes);
     MaskArgs ma;
-    std::memset(&ma, 0, sizeof(ma));
-    if (anyMasked) {
-        ma.table = (const MaskTex*)((char*)work + offTable); ma.side = (MaskSide*)((char*)work + offSide); ma.sideCap = maskedTris; ma.tableCap = (uint32_t)table.size();
-        if (int rc = stageMaskTable(ctx, st, table, (MaskTex*)((char*)work + offTable), who.c_str())) return rc;
-    }
+    if (int rc = stageMask(ctx, st, table, work, offTable, offSide, maskedTris, who, &ma)) return rc;
     hipError_t e = launch_raster_begin(st, counters, numViews);
     if (e != hipSuccess) return failHip(ctx, e, (who + " counters launch").c_str());
-    // the draws, in ring slots of kRasterJobsPerSlot jobs (fewer of the larger masked jobs): one setup launch per slot
-    auto setupLaunches = [&](auto jobTag) -> int {
-        using JOB = decltype(jobTag);
-        constexpr bool kMaskedJob = std::is_same<JOB, RasterMaskedJob>::value;
-        constexpr size_t perSlot = kConstSlotBytes / sizeof(JOB);
-        int v = 0, d = 0;
-        size_t left = numJobs, jobNo = 0;
-        uint64_t firstMasked = 0;
-        while (left) {
-            int slot;
-            if (int rc = acquireSlot(ctx, &slot)) return rc;
-            JOB* jobs = (JOB*)(ctx->hostRing + (size_t)slot * kConstSlotBytes);
-            const size_t n = left < perSlot ? left : perSlot;
-            uint64_t blocks = 0;
-            for (size_t k = 0; k < n;) {
-                if (d >= views[v].numDraws) { ++v; d = 0; continue; }
-                const vqhip_shadow_draw& D = baseDraw(views[v].draws[d++]);
-                if (!D.mesh.numIndices) continue;
-                JOB& J = jobs[k++];
-                J.positions = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices; J.wvp = D.matWorldViewProj; J.world = D.matWorld;
-                J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numTris = D.mesh.numIndices / 3; J.numInstances = D.numInstances;
-                J.indexBits = D.mesh.indexBits; J.cullMode = D.cullMode; J.view = v; J.firstBlock = (uint32_t)blocks;
-                blocks += ((uint64_t)J.numTris * J.numInstances + 255) / 256;
-                if constexpr (kMaskedJob) {
-                    J.maskSlot = slotOfJob[jobNo]; J.firstMasked = (uint32_t)firstMasked; J.pad[0] = J.pad[1] = 0u;
-                    if (J.maskSlot) firstMasked += (uint64_t)J.numTris * J.numInstances;
-                }
-                ++jobNo;
-            }
-            if (int rc = commitSlot(ctx, slot, sizeof(JOB) * n, st)) return rc;
-            const JOB* djobs = (const JOB*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
-            if constexpr (kMaskedJob) e = launch_raster_setup(st, djobs, (int)n, (uint32_t)blocks, dviews, counters, boxes, records, ma);
-            else                      e = launch_raster_setup(st, djobs, (int)n, (uint32_t)blocks, dviews, counters, boxes, records);
-            if (e != hipSuccess) return failHip(ctx, e, (who + " setup launch").c_str());
-            if (int rc = releaseSlot(ctx, slot, st)) return rc;
-            left -= n;
+    // the draws that have indices, in ring slots of RasterJobs, or of the larger RasterMaskedJobs when a draw is masked: one setup launch per slot
+    int v = 0, d = 0;
+    size_t jobNo = 0;
+    uint64_t blocks = 0, firstMasked = 0;
+    auto fill = [&](auto& J, size_t k) {
+        if (!k) blocks = 0;
+        for (;;) {
+            if (d >= views[v].numDraws) { ++v; d = 0; continue; }
+            const vqhip_shadow_draw& D = baseDraw(views[v].draws[d++]);
+            if (!D.mesh.numIndices) continue;
+            J.world = D.matWorld; J.view = v;
+            const uint64_t tris = meshJob(J, D, blocks);
+            if constexpr (std::is_same<std::decay_t<decltype(J)>, RasterMaskedJob>::value) { maskJob(J, slotOfJob[jobNo], firstMasked, tris); J.pad[0] = J.pad[1] = 0u; }
+            ++jobNo;
+            return;
         }
-        return VQHIP_OK;
     };
-    if (int rc = anyMasked ? setupLaunches(RasterMaskedJob{}) : setupLaunches(RasterJob{})) return rc;
+    auto setup = [&](const auto* jobs, size_t n, size_t, const auto&... mask) {
+        hipError_t le = launch_raster_setup(st, jobs, (int)n, (uint32_t)blocks, dviews, counters, boxes, records, mask...);
+        return le == hipSuccess ? VQHIP_OK : failHip(ctx, le, (who + " setup launch").c_str());
+    };
+    if (int rc = anyMasked ? stageJobs<RasterMaskedJob>(ctx, st, numJobs, fill, [&](const RasterMaskedJob* jobs, size_t n, size_t first) { return setup(jobs, n, first, ma); })
+                           : stageJobs<RasterJob>(ctx, st, numJobs, fill, setup)) return rc;
     e = anyMasked ? launch_raster_fill(st, dviews, numViews, (uint32_t)fillBlocks, tile, counters, boxes, records, ma)
                   : launch_raster_fill(st, dviews, numViews, (uint32_t)fillBlocks, tile, counters, boxes, records);
     if (e != hipSuccess) return failHip(ctx, e, (who + " fill launch").c_str());
@@ -2118,24 +2145,11 @@ int vqhip_shadow_masked_depth(vqhip_ctx* ctx, void* stream, const vqhip_shadow_m
 }
 
 // ---- Main-view depth pre-pass (raster_view.hip; docs/DESIGN_DETAILS.md §7.17) ------------------------------------------------------------------------------------
-namespace {
-constexpr size_t kSceneJobsPerSlot = kConstSlotBytes / sizeof(SceneDepthJob);
-constexpr uint64_t kSceneMaxTriangles = (uint64_t)1 << 29;     // eight records each: the record counter is 32 bits wide; q stays far below 0xFFFFFFFF
-static_assert((kRasterMaxDraws + kSceneJobsPerSlot - 1) / kSceneJobsPerSlot < vqhip_ctx::kSlots, "one call never laps the ring");
-// counter | boxes[8 n] | records[8 n]; false when the sizes do not fit
-bool sceneDepthLayout(uint64_t instancedTriangles, size_t* boxes, size_t* records, size_t* total) {
-    if (instancedTriangles >= kSceneMaxTriangles) return false;
-    const uint64_t cap = instancedTriangles * kSceneFanMax;
-    const uint64_t b = kSceneCounterBytes, r = align256(b + cap * kSceneBoxBytes), t = align256(r + cap * kSceneRecordBytes);
-    if (t > (uint64_t)SIZE_MAX) return false;
-    *boxes = (size_t)b; *records = (size_t)r; *total = (size_t)t;
-    return true;
-}
-} // namespace
+static_assert(slotsFor<SceneDepthJob>(kRasterMaxDraws) < vqhip_ctx::kSlots, "one call never laps the ring");
 
 size_t vqhip_scene_depth_work_bytes(uint64_t instancedTriangles) {
     size_t b, r, t;
-    return sceneDepthLayout(instancedTriangles, &b, &r, &t) ? t : 0;
+    return workLayout(kSceneLayout, instancedTriangles, &b, &r, &t) ? t : 0;
 }
 
 // vqhip_scene_depth (DRAW = vqhip_scene_depth_draw) and vqhip_scene_masked_depth (DRAW = vqhip_scene_masked_depth_draw): one body, entered with the context guard held; `who` names the entry
@@ -2168,12 +2182,9 @@ int sceneDepthCall(vqhip_ctx* ctx, void* stream, const DRAW* draws, int numDraws
     for (int d = 0; d < numDraws; ++d) {
         const vqhip_scene_depth_draw& D = baseDraw(draws[d]);
         const vqhip_material* mat = maskMaterial(draws[d]);
-        auto badDraw = [&](const char* m) { return bad("draw " + std::to_string(d) + ": " + m); };
+        auto badDraw = [&](const std::string& m) { return bad("draw " + std::to_string(d) + ": " + m); };
         if (!D.mesh.positions || !D.mesh.indices || !D.matWorldViewProj) return badDraw("positions, indices or matWorldViewProj is NULL");
-        if (D.mesh.indexBits != 16 && D.mesh.indexBits != 32) return badDraw("indexBits must be 16 or 32");
-        if (D.mesh.numIndices % 3) return badDraw("numIndices is not a multiple of 3");
-        if (D.mesh.strideBytes < 12 || D.mesh.strideBytes % 4) return badDraw("strideBytes below 12 or not a multiple of 4");
-        if (D.numInstances < 1 || D.numInstances > VQHIP_SCENE_DEPTH_MAX_INSTANCES) return badDraw("numInstances must be 1..64");
+        if (const std::string m = badMeshDraw(D.mesh, D.numInstances, 12, VQHIP_SCENE_DEPTH_MAX_INSTANCES); !m.empty()) return badDraw(m);
         if (D.cullMode != VQHIP_CULL_NONE && D.cullMode != VQHIP_CULL_FRONT && D.cullMode != VQHIP_CULL_BACK) return badDraw("unknown cullMode");
         if ((uintptr_t)D.mesh.positions % 4 || (uintptr_t)D.matWorldViewProj % 4 || (uintptr_t)D.mesh.indices % (D.mesh.indexBits / 8))
             return badDraw("positions / matrices must be 4-byte aligned, indices aligned to their size");
@@ -2202,7 +2213,7 @@ int sceneDepthCall(vqhip_ctx* ctx, void* stream, const DRAW* draws, int numDraws
     if (totalTris >= kSceneMaxTriangles) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": 2^29 or more instanced triangles in one call");
     if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": more than 20000 draws in one call");
     size_t offBoxes, offRecords, need, offTable = 0, offSide = 0;
-    bool fits = sceneDepthLayout(totalTris, &offBoxes, &offRecords, &need);
+    bool fits = workLayout(kSceneLayout, totalTris, &offBoxes, &offRecords, &need);
     if (fits && kMaskedEntry) fits = maskLayout(need, totalTris, maskedTris, numDraws, &offTable, &offSide, &need);
     if (!fits || workBytes < need)
         return bad(kMaskedEntry ? "workBytes below vqhip_scene_masked_depth_work_bytes(the call's instanced and masked instanced triangles, numDraws)"
@@ -2228,45 +2239,28 @@ int sceneDepthCall(vqhip_ctx* ctx, void* stream, const DRAW* draws, int numDraws
     void* boxes = (char*)work + offBoxes;
     void* records = (char*)work + offRecords;
     MaskArgs ma;
-    std::memset(&ma, 0, sizeof(ma));
-    if (anyMasked) {
-        ma.table = (const MaskTex*)((char*)work + offTable); ma.side = (MaskSide*)((char*)work + offSide); ma.sideCap = sideTris; ma.tableCap = (uint32_t)table.size();
-        if (int rc = stageMaskTable(ctx, st, table, (MaskTex*)((char*)work + offTable), who.c_str())) return rc;
-    }
+    if (int rc = stageMask(ctx, st, table, work, offTable, offSide, sideTris, who, &ma)) return rc;
     hipError_t e = launch_raster_begin(st, counter, 1);
     if (e != hipSuccess) return failHip(ctx, e, (who + " counter launch").c_str());
-    // the draws, in ring slots of kSceneJobsPerSlot jobs: one setup launch per slot
+    // the draws that have indices, in ring slots of SceneDepthJobs: one setup launch per slot
     int d = 0;
-    size_t left = numJobs;
-    uint64_t firstQ = 0, firstMasked = 0;
     size_t jobNo = 0;
-    while (left) {
-        int slot;
-        if (int rc = acquireSlot(ctx, &slot)) return rc;
-        SceneDepthJob* jobs = (SceneDepthJob*)(ctx->hostRing + (size_t)slot * kConstSlotBytes);
-        const size_t n = left < kSceneJobsPerSlot ? left : kSceneJobsPerSlot;
-        uint64_t blocks = 0;
-        for (size_t k = 0; k < n;) {
-            const vqhip_scene_depth_draw& D = baseDraw(draws[d++]);
-            if (!D.mesh.numIndices) continue;
-            SceneDepthJob& J = jobs[k++];
-            J.positions = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices; J.wvp = D.matWorldViewProj;
-            J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numTris = D.mesh.numIndices / 3; J.numInstances = D.numInstances;
-            J.indexBits = D.mesh.indexBits; J.cullMode = D.cullMode; J.firstBlock = (uint32_t)blocks; J.firstQ = (uint32_t)firstQ;
-            blocks += ((uint64_t)J.numTris * J.numInstances + 255) / 256;
-            firstQ += (uint64_t)J.numTris * J.numInstances;
-            J.maskSlot = anyMasked ? slotOfJob[jobNo] : 0u; J.firstMasked = (uint32_t)firstMasked;
-            if (J.maskSlot) firstMasked += (uint64_t)J.numTris * J.numInstances;
-            ++jobNo;
-        }
-        if (int rc = commitSlot(ctx, slot, sizeof(SceneDepthJob) * n, st)) return rc;
-        const SceneDepthJob* djobs = (const SceneDepthJob*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
-        e = anyMasked ? launch_scene_setup(st, djobs, (int)n, (uint32_t)blocks, a, counter, boxes, records, ma)
-                      : launch_scene_setup(st, djobs, (int)n, (uint32_t)blocks, a, counter, boxes, records);
-        if (e != hipSuccess) return failHip(ctx, e, (who + " setup launch").c_str());
-        if (int rc = releaseSlot(ctx, slot, st)) return rc;
-        left -= n;
-    }
+    uint64_t blocks = 0, firstQ = 0, firstMasked = 0;
+    auto fill = [&](SceneDepthJob& J, size_t k) {
+        if (!k) blocks = 0;
+        while (!baseDraw(draws[d]).mesh.numIndices) ++d;
+        J.firstQ = (uint32_t)firstQ;
+        const uint64_t tris = meshJob(J, baseDraw(draws[d++]), blocks);
+        firstQ += tris;
+        maskJob(J, anyMasked ? slotOfJob[jobNo] : 0u, firstMasked, tris);
+        ++jobNo;
+    };
+    auto setup = [&](const SceneDepthJob* jobs, size_t n, size_t) {
+        hipError_t le = anyMasked ? launch_scene_setup(st, jobs, (int)n, (uint32_t)blocks, a, counter, boxes, records, ma)
+                                  : launch_scene_setup(st, jobs, (int)n, (uint32_t)blocks, a, counter, boxes, records);
+        return le == hipSuccess ? VQHIP_OK : failHip(ctx, le, (who + " setup launch").c_str());
+    };
+    if (int rc = stageJobs<SceneDepthJob>(ctx, st, numJobs, fill, setup)) return rc;
     e = anyMasked ? launch_scene_fill(st, a, scene_depth_tile(ctx->opt.rasterTile, samples), counter, boxes, records, ma)
                   : launch_scene_fill(st, a, scene_depth_tile(ctx->opt.rasterTile, samples), counter, boxes, records);
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (who + " fill launch").c_str());
@@ -2293,12 +2287,8 @@ int vqhip_scene_masked_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_mas
 }
 
 // ---- The lit draw's interpolants from meshes (raster_attr.hip; docs/DESIGN_DETAILS.md §7.18) ----------------------------------------------------------------------
-namespace {
-constexpr size_t kSurfaceJobsPerSlot = kConstSlotBytes / sizeof(SurfaceJob);
-// A call of 20 000 draws may take more slots than the ring has: acquireSlot then waits for the table copy that last read the slot, which this call enqueued.
-static_assert(kSurfaceJobsPerSlot >= 1, "a ring slot holds at least one SurfaceJob");
-} // namespace
-
+// A call of 20 000 draws may take more slots than the ring has (slotsFor<SurfaceJob>(kRasterMaxDraws) of them): acquireSlot then waits for the table copy that last
+// read the slot, which this call enqueued.
 size_t vqhip_scene_interpolants_work_bytes(int numDraws) {
     if (numDraws < 0) return 0;
     return align256((size_t)(numDraws > 0 ? numDraws : 1) * sizeof(SurfaceJob));
@@ -2330,14 +2320,11 @@ static int sceneInterpolants(vqhip_ctx* ctx, const std::string& w, void* stream,
     size_t numJobs = 0;
     for (int d = 0; d < numDraws; ++d) {
         const vqhip_scene_surface_draw& D = draws[d];
-        auto badDraw = [&](const char* m) { return bad("draw " + std::to_string(d) + ": " + m); };
+        auto badDraw = [&](const std::string& m) { return bad("draw " + std::to_string(d) + ": " + m); };
         if (!D.mesh.positions || !D.mesh.indices || !D.matWorldViewProj || !D.matWorld || !D.matNormal)
             return badDraw("positions, indices, matWorldViewProj, matWorld or matNormal is NULL");
         if (sv && !D.matWorldViewProjPrev) return badDraw("matWorldViewProjPrev is NULL while the sv planes are asked for");
-        if (D.mesh.indexBits != 16 && D.mesh.indexBits != 32) return badDraw("indexBits must be 16 or 32");
-        if (D.mesh.numIndices % 3) return badDraw("numIndices is not a multiple of 3");
-        if (D.mesh.strideBytes < 44 || D.mesh.strideBytes % 4) return badDraw("strideBytes below 44 or not a multiple of 4");
-        if (D.numInstances < 1 || D.numInstances > VQHIP_SCENE_DEPTH_MAX_INSTANCES) return badDraw("numInstances must be 1..64");
+        if (const std::string m = badMeshDraw(D.mesh, D.numInstances, 44, VQHIP_SCENE_DEPTH_MAX_INSTANCES); !m.empty()) return badDraw(m);
         if (D.materialIndex < 0) return badDraw("materialIndex is negative");
         if ((uintptr_t)D.mesh.positions % 4 || (uintptr_t)D.matWorldViewProj % 4 || (uintptr_t)D.matWorld % 4 || (uintptr_t)D.matNormal % 4 ||
             (uintptr_t)D.matWorldViewProjPrev % 4 || (uintptr_t)D.mesh.indices % (D.mesh.indexBits / 8))
@@ -2367,32 +2354,20 @@ static int sceneInterpolants(vqhip_ctx* ctx, const std::string& w, void* stream,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     SurfaceJob* table = (SurfaceJob*)work;
-    // the draws, in ring slots of kSurfaceJobsPerSlot jobs: one table-copy launch per slot
+    // the draws that have indices, in ring slots of SurfaceJobs: one table-copy launch per slot
     int d = 0;
-    size_t left = numJobs, done = 0;
     uint64_t firstQ = 0;
-    while (left) {
-        int slot;
-        if (int rc = acquireSlot(ctx, &slot)) return rc;
-        SurfaceJob* jobs = (SurfaceJob*)(ctx->hostRing + (size_t)slot * kConstSlotBytes);
-        const size_t n = left < kSurfaceJobsPerSlot ? left : kSurfaceJobsPerSlot;
-        for (size_t k = 0; k < n;) {
-            const vqhip_scene_surface_draw& D = draws[d++];
-            if (!D.mesh.numIndices) continue;
-            SurfaceJob& J = jobs[k++];
-            std::memset(&J, 0, sizeof(J));
-            J.vertices = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices;
-            J.wvp = D.matWorldViewProj; J.world = D.matWorld; J.normal = D.matNormal; J.wvpPrev = D.matWorldViewProjPrev;
-            J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numTris = D.mesh.numIndices / 3; J.numInstances = D.numInstances;
-            J.indexBits = D.mesh.indexBits; J.materialIndex = D.materialIndex; J.firstQ = (uint32_t)firstQ;
-            firstQ += (uint64_t)J.numTris * J.numInstances;
-        }
-        if (int rc = commitSlot(ctx, slot, sizeof(SurfaceJob) * n, st)) return rc;
-        hipError_t e = launch_table_copy(st, ctx->devRing + (size_t)slot * kConstSlotBytes, table + done, (uint32_t)(n * (sizeof(SurfaceJob) / 16)));
-        if (e != hipSuccess) return failHip(ctx, e, (w + " table-copy launch").c_str());
-        if (int rc = releaseSlot(ctx, slot, st)) return rc;
-        left -= n; done += n;
-    }
+    auto fill = [&](SurfaceJob& J, size_t) {
+        while (!draws[d].mesh.numIndices) ++d;
+        const vqhip_scene_surface_draw& D = draws[d++];
+        std::memset(&J, 0, sizeof(J));
+        J.vertices = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices;
+        J.wvp = D.matWorldViewProj; J.world = D.matWorld; J.normal = D.matNormal; J.wvpPrev = D.matWorldViewProjPrev;
+        J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numTris = D.mesh.numIndices / 3; J.numInstances = D.numInstances;
+        J.indexBits = D.mesh.indexBits; J.materialIndex = D.materialIndex; J.firstQ = (uint32_t)firstQ;
+        firstQ += (uint64_t)J.numTris * J.numInstances;
+    };
+    if (int rc = stageJobs<SurfaceJob>(ctx, st, numJobs, fill, [&](const SurfaceJob* src, size_t n, size_t first) { return copySlotToTable(ctx, st, src, n, table + first, w); })) return rc;
     const bool waveForm = ctx->opt.interpForm != 1;                                           // default: the wave form
     const QuadPlane qp = { planes[5], (uint32_t)quadPitch };
     hipError_t e = quadOut ? launch_scene_quad_interpolants(st, a, table, waveForm, qp) : launch_scene_interpolants(st, a, table, waveForm);
@@ -2413,3 +2388,4 @@ int vqhip_scene_quad_interpolants(vqhip_ctx* ctx, void* stream, const vqhip_scen
 }
 
 } // extern "C"
+
