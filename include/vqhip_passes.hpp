@@ -91,6 +91,17 @@ protected:
     template <class DRAW> static uint64_t InstancedTriangles(const DRAW& d) { return (uint64_t)(d.mesh.numIndices / 3) * d.numInstances; }
 };
 
+// A pass that owns no resource, window-sized or other: the caller brings every plane with the draw parameters.
+class OwnsNothingPass : public RenderPassBase {
+public:
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override {}
+    void OnCreateWindowSizeDependentResources(unsigned, unsigned, const IRenderPassResourceCollection* = nullptr) override {}
+    void OnDestroyWindowSizeDependentResources() override {}
+protected:
+    using RenderPassBase::RenderPassBase;
+};
+
 // ---------------------------------------------------------------------------------------------------------------
 // Forward lighting == VQRenderer::RenderSceneColor (SceneRendering.cpp:1619-1851, lit draws :1730-1784).
 // Owns the scene-colour target (Tex_SceneColor, RGBA16F: RenderResources.cpp:40,144-161).
@@ -898,7 +909,7 @@ private:
 // TexAvgRadiance[i], TexVariance[i], TexSampleCount[i]. TexAvgRadiance[1 - i] and the blue noise are bound by the engine and never read by the shader: not
 // parameters. The pass owns nothing, the caller ping-pongs; the engine's bClearHistoryBuffers is a plain clear of the history planes by the caller.
 // ---------------------------------------------------------------------------------------------------------------
-class HipSSRReprojectPass : public RenderPassBase {
+class HipSSRReprojectPass : public OwnsNothingPass {
 public:
     struct FDrawParameters : public IRenderPassDrawParameters {
         void* Stream = nullptr;
@@ -921,11 +932,7 @@ public:
         void* TexVarianceOut = nullptr;                          // TexVariance[i], R16F
         void* TexSampleCountOut = nullptr;                       // TexSampleCount[i], R16F
     };
-    explicit HipSSRReprojectPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
-    bool Initialize() override { return mCtx != nullptr; }
-    void Destroy() override {}
-    void OnCreateWindowSizeDependentResources(unsigned, unsigned, const IRenderPassResourceCollection* = nullptr) override {}
-    void OnDestroyWindowSizeDependentResources() override {}
+    explicit HipSSRReprojectPass(vqhip_ctx* Ctx) : OwnsNothingPass(Ctx) {}
     void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
         const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
         if (!p) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
@@ -948,7 +955,7 @@ public:
 // vqhip_ssr_prefilter. Reads TexRadiance[i] / TexVariance[i] / TexAvgRadiance[i] and writes TexRadiance[1 - i] / TexVariance[1 - i] (:1199-1212): the pass owns
 // nothing, the caller ping-pongs. Pixels of unlisted tiles are not written.
 // ---------------------------------------------------------------------------------------------------------------
-class HipSSRPrefilterPass : public RenderPassBase {
+class HipSSRPrefilterPass : public OwnsNothingPass {
 public:
     struct FDrawParameters : public IRenderPassDrawParameters {
         void* Stream = nullptr;
@@ -964,11 +971,7 @@ public:
         void* TexRadianceOut = nullptr;                          // TexRadiance[1 - i]
         void* TexVarianceOut = nullptr;                          // TexVariance[1 - i]
     };
-    explicit HipSSRPrefilterPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
-    bool Initialize() override { return mCtx != nullptr; }
-    void Destroy() override {}
-    void OnCreateWindowSizeDependentResources(unsigned, unsigned, const IRenderPassResourceCollection* = nullptr) override {}
-    void OnDestroyWindowSizeDependentResources() override {}
+    explicit HipSSRPrefilterPass(vqhip_ctx* Ctx) : OwnsNothingPass(Ctx) {}
     void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
         const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
         if (!p) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
@@ -983,7 +986,7 @@ public:
 // prefilter wrote (TexRadiance[1 - i], TexVariance[1 - i]), TexReprojectedRadiance and TexSampleCount[1 - i] (:1214-1222), writes TexRadiance[i] / TexVariance[i] —
 // the image vqhip_composite_reflections consumes (:1230).
 // ---------------------------------------------------------------------------------------------------------------
-class HipSSRResolveTemporalPass : public RenderPassBase {
+class HipSSRResolveTemporalPass : public OwnsNothingPass {
 public:
     struct FDrawParameters : public IRenderPassDrawParameters {
         void* Stream = nullptr;
@@ -999,11 +1002,7 @@ public:
         void* TexRadianceOut = nullptr;                          // TexRadiance[i]
         void* TexVarianceOut = nullptr;                          // TexVariance[i]
     };
-    explicit HipSSRResolveTemporalPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
-    bool Initialize() override { return mCtx != nullptr; }
-    void Destroy() override {}
-    void OnCreateWindowSizeDependentResources(unsigned, unsigned, const IRenderPassResourceCollection* = nullptr) override {}
-    void OnDestroyWindowSizeDependentResources() override {}
+    explicit HipSSRResolveTemporalPass(vqhip_ctx* Ctx) : OwnsNothingPass(Ctx) {}
     void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
         const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
         if (!p) { mStatus = VQHIP_ERR_INVALID_ARG; return; }

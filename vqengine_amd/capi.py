@@ -464,6 +464,40 @@ def _check_img(t, fmt, name, hw=None):
         raise ValueError(f"{name}: expected {hw[0]} x {hw[1]} pixels, got {tuple(t.shape[:2])}")
 
 
+def _check_plane(what, t, dtype, hw):               # this and the helpers below: what the SSR bindings check alike; a label carries the binding's prefix, if it has one
+    """one element per pixel, rows may be strided -> the row pitch in elements; what: "<label>: expected cuda <dtype as that binding spells it>" """
+    if not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == tuple(hw) and t.stride(1) == 1 and t.stride(0) >= hw[1]):
+        raise ValueError(f"{what} {tuple(hw)} with unit column stride")
+    return t.stride(0)
+
+
+def _check_dense(label, t, dtype, shape):
+    if not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
+        raise ValueError(f"{label}: expected contiguous cuda {str(dtype)[6:]} {tuple(shape)}")
+
+
+def _check_words(label, t, hw, fmt_name):           # packed 32-bit pixels, such as the R11G11B10_FLOAT average
+    if not (t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == tuple(hw) and t.is_contiguous()):
+        raise ValueError(f"{label}: expected contiguous cuda int32 {tuple(hw)} ({fmt_name} words)")
+
+
+def _check_normals(who, name, t, fmt, hw):          # R10G10B10A2_UNORM words or an image
+    if fmt == abi.FMT_R10G10B10A2_UNORM:
+        _check_words(who + name, t, hw, "R10G10B10A2_UNORM")
+    else:
+        _check_img(t, fmt, name, hw)
+
+
+def _check_list(label, t, n):                       # tile_list, counters, ray_list: at least n words
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= n):
+        raise ValueError(f"{label}: expected contiguous cuda int32 [{n}]")
+
+
+def _check_tiles(who, tile_list, counters, tiles):
+    _check_list(who + "tile_list", tile_list, tiles)
+    _check_list(who + "counters", counters, 2)
+
+
 def _halo_rows(halo_top, halo_bottom, fmt, width):
     """Both halos of a tile have the same row count (>= 10) and the tile's width and format."""
     rows = 0
@@ -617,51 +651,36 @@ class Context:
         shared / per_pass: abi.CacaoConstants and an array of four (vqengine_amd.cacao.constants). work: a cuda uint8 tensor of cacao_work_bytes bytes (allocated
         when None); out: uint8 [H,W], rows may be strided. Returns (ao, work): the R8_UNORM plane that forward lighting takes as texScreenSpaceAO, and the work
         buffer (cacao_work_planes views its intermediates)."""
-        if not (depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 2 and depth.stride(1) == 1):
-            raise ValueError(f"cacao: depth: expected cuda float32 [H,W] with unit column stride, got {tuple(depth.shape)} {depth.dtype} strides {depth.stride()}")
-        h, w = depth.shape
-        if normal_fmt == abi.FMT_RGBA32F:
-            ok = normals.dtype == torch.float32 and tuple(normals.shape) == (h, w, 4) and normals.stride(2) == 1 and normals.stride(1) == 4
-        else:
-            ok = normals.dtype == torch.int32 and tuple(normals.shape) == (h, w) and normals.stride(1) == 1
-        if not (ok and normals.is_cuda):
-            raise ValueError("cacao: normals: expected cuda int32 [H,W] (R10G10B10A2_UNORM words) or float32 [H,W,4] with dense pixels")
-        if work is None:
-            work = torch.empty((cacao_work_bytes(w, h),), dtype=torch.uint8, device=self.device)
-        if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
-            raise ValueError("cacao: work: expected a contiguous cuda uint8 tensor")
-        if out is None:
-            out = torch.empty((h, w), dtype=torch.uint8, device=self.device)
-        if not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (h, w) and out.stride(1) == 1):
-            raise ValueError(f"cacao: out: expected cuda uint8 {(h, w)} with unit column stride")
-        self._ck(self.lib.vqhip_cacao(self._h, self._stream(stream), _ptr(depth), depth.stride(0) * 4, _ptr(normals), normal_fmt, normals.stride(0) * normals.element_size(),
-                                      C.byref(shared), per_pass, int(quality), int(blur_passes), _ptr(work), work.numel(), _ptr(out), out.stride(0), w, h))
-        return out, work
+        return self._cacao("cacao", cacao_work_bytes, self.lib.vqhip_cacao, depth, normals, normal_fmt, shared, per_pass, (int(quality), int(blur_passes)), work, out, stream)
 
     def adaptive_cacao(self, depth, normals, normal_fmt, shared, per_pass, blur_passes=2, work=None, out=None, stream=None):
         """vqhip_adaptive_cacao, quality HIGHEST: the arguments of cacao() without `quality`; shared / per_pass from vqengine_amd.cacao.constants with settings at
         HIGHEST (its defaults). work: a cuda uint8 tensor of adaptive_cacao_work_bytes bytes (allocated when None). Returns (ao, work); adaptive_cacao_work_planes
         views the intermediates, the importance map and the load counter included."""
+        return self._cacao("adaptive_cacao", adaptive_cacao_work_bytes, self.lib.vqhip_adaptive_cacao, depth, normals, normal_fmt, shared, per_pass, (int(blur_passes),),
+                           work, out, stream)
+
+    def _cacao(self, who, work_bytes, call, depth, normals, normal_fmt, shared, per_pass, settings, work, out, stream):
+        """both bindings; settings: what the entry point takes between per_pass and work"""
         if not (depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 2 and depth.stride(1) == 1):
-            raise ValueError(f"adaptive_cacao: depth: expected cuda float32 [H,W] with unit column stride, got {tuple(depth.shape)} {depth.dtype} strides {depth.stride()}")
+            raise ValueError(f"{who}: depth: expected cuda float32 [H,W] with unit column stride, got {tuple(depth.shape)} {depth.dtype} strides {depth.stride()}")
         h, w = depth.shape
         if normal_fmt == abi.FMT_RGBA32F:
             ok = normals.dtype == torch.float32 and tuple(normals.shape) == (h, w, 4) and normals.stride(2) == 1 and normals.stride(1) == 4
         else:
             ok = normals.dtype == torch.int32 and tuple(normals.shape) == (h, w) and normals.stride(1) == 1
         if not (ok and normals.is_cuda):
-            raise ValueError("adaptive_cacao: normals: expected cuda int32 [H,W] (R10G10B10A2_UNORM words) or float32 [H,W,4] with dense pixels")
+            raise ValueError(f"{who}: normals: expected cuda int32 [H,W] (R10G10B10A2_UNORM words) or float32 [H,W,4] with dense pixels")
         if work is None:
-            work = torch.empty((adaptive_cacao_work_bytes(w, h),), dtype=torch.uint8, device=self.device)
+            work = torch.empty((work_bytes(w, h),), dtype=torch.uint8, device=self.device)
         if not (work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous()):
-            raise ValueError("adaptive_cacao: work: expected a contiguous cuda uint8 tensor")
+            raise ValueError(f"{who}: work: expected a contiguous cuda uint8 tensor")
         if out is None:
             out = torch.empty((h, w), dtype=torch.uint8, device=self.device)
         if not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (h, w) and out.stride(1) == 1):
-            raise ValueError(f"adaptive_cacao: out: expected cuda uint8 {(h, w)} with unit column stride")
-        self._ck(self.lib.vqhip_adaptive_cacao(self._h, self._stream(stream), _ptr(depth), depth.stride(0) * 4, _ptr(normals), normal_fmt,
-                                               normals.stride(0) * normals.element_size(), C.byref(shared), per_pass, int(blur_passes), _ptr(work), work.numel(),
-                                               _ptr(out), out.stride(0), w, h))
+            raise ValueError(f"{who}: out: expected cuda uint8 {(h, w)} with unit column stride")
+        self._ck(call(self._h, self._stream(stream), _ptr(depth), depth.stride(0) * 4, _ptr(normals), normal_fmt, normals.stride(0) * normals.element_size(),
+                      C.byref(shared), per_pass, *settings, _ptr(work), work.numel(), _ptr(out), out.stride(0), w, h))
         return out, work
 
     def shadow_depth(self, views, work=None, stream=None):
@@ -1291,20 +1310,11 @@ class Context:
         n_floats = sum(r * c for r, c in abi.depth_hierarchy_shapes(w, h))
         if not (flat.is_cuda and flat.dtype == torch.float32 and flat.untyped_storage().nbytes() - flat.storage_offset() * 4 >= n_floats * 4):
             raise ValueError("hierarchy: expected the cuda float32 buffer of depth_hierarchy for this frame size")
-        if normal_fmt == abi.FMT_R10G10B10A2_UNORM:
-            if not (normals.is_cuda and normals.dtype == torch.int32 and tuple(normals.shape) == (h, w) and normals.is_contiguous()):
-                raise ValueError(f"normals: expected contiguous cuda int32 {(h, w)} (R10G10B10A2_UNORM words)")
-        else:
-            _check_img(normals, normal_fmt, "normals", (h, w))
-        if not (roughness8.is_cuda and roughness8.dtype == torch.uint8 and tuple(roughness8.shape) == (h, w) and roughness8.is_contiguous()):
-            raise ValueError(f"roughness8: expected contiguous cuda uint8 {(h, w)}")
-        n = abi.SSR_BLUE_NOISE_SIZE
-        if not (blue_noise.is_cuda and blue_noise.dtype == torch.uint8 and tuple(blue_noise.shape) == (n, n, 2) and blue_noise.is_contiguous()):
-            raise ValueError(f"blue_noise: expected contiguous cuda uint8 {(n, n, 2)}")
-        if not (ray_list.is_cuda and ray_list.dtype == torch.int32 and ray_list.numel() >= h * w and ray_list.is_contiguous()):
-            raise ValueError(f"ray_list: expected contiguous cuda int32 [{h * w}]")
-        if not (counters.is_cuda and counters.dtype == torch.int32 and counters.numel() >= 2 and counters.is_contiguous()):
-            raise ValueError("counters: expected contiguous cuda int32 [2]")
+        _check_normals("", "normals", normals, normal_fmt, (h, w))
+        _check_dense("roughness8", roughness8, torch.uint8, (h, w))
+        _check_dense("blue_noise", blue_noise, torch.uint8, (abi.SSR_BLUE_NOISE_SIZE, abi.SSR_BLUE_NOISE_SIZE, 2))
+        _check_list("ray_list", ray_list, h * w)
+        _check_list("counters", counters, 2)
         self._ck(self.lib.vqhip_ssr_intersect(self._h, self._stream(stream), _ptr(ray_list), _ptr(counters), _ptr(lit_scene), lit_fmt, 0, _ptr(flat),
                                               _ptr(normals), normal_fmt, 0, _ptr(roughness8), _ptr(blue_noise), C.byref(cb), C.byref(env),
                                               _ptr(radiance), radiance_fmt, 0))
@@ -1313,23 +1323,16 @@ class Context:
     # ---- SSR denoiser passes 2 and 3 (docs/DESIGN_DETAILS.md §7.12) ------------------------------------------------
     def _denoise_common(self, who, tile_list, counters, roughness8, average, avg_fmt, cb, planes, out, out_fmt, out_variance):
         w, h = int(cb.bufferDimensions[0]), int(cb.bufferDimensions[1])
-        tiles = ((w + 7) // 8) * ((h + 7) // 8)
-        if not (tile_list.is_cuda and tile_list.dtype == torch.int32 and tile_list.is_contiguous() and tile_list.numel() >= tiles):
-            raise ValueError(f"{who}: tile_list: expected contiguous cuda int32 [{tiles}]")
-        if not (counters.is_cuda and counters.dtype == torch.int32 and counters.numel() >= 2 and counters.is_contiguous()):
-            raise ValueError(f"{who}: counters: expected contiguous cuda int32 [2]")
-        if not (roughness8.is_cuda and roughness8.dtype == torch.uint8 and tuple(roughness8.shape) == (h, w) and roughness8.is_contiguous()):
-            raise ValueError(f"{who}: roughness8: expected contiguous cuda uint8 {(h, w)}")
         h8, w8 = (h + 7) // 8, (w + 7) // 8
+        _check_tiles(f"{who}: ", tile_list, counters, h8 * w8)
+        _check_dense(f"{who}: roughness8", roughness8, torch.uint8, (h, w))
         if avg_fmt == abi.FMT_R11G11B10_FLOAT:
-            if not (average.is_cuda and average.dtype == torch.int32 and tuple(average.shape) == (h8, w8) and average.is_contiguous()):
-                raise ValueError(f"{who}: average: expected contiguous cuda int32 {(h8, w8)} (R11G11B10_FLOAT words)")
+            _check_words(f"{who}: average", average, (h8, w8), "R11G11B10_FLOAT")
         else:
             _check_img(average, avg_fmt, "average", (h8, w8))
         for name, (t, fmt) in planes.items():
             if fmt is None:                                                     # an R16F plane; rows may be strided
-                if not (t.is_cuda and t.dtype == torch.float16 and tuple(t.shape) == (h, w) and t.stride(1) == 1 and t.stride(0) >= w):
-                    raise ValueError(f"{who}: {name}: expected cuda float16 {(h, w)} with unit column stride")
+                _check_plane(f"{who}: {name}: expected cuda float16", t, torch.float16, (h, w))
             else:
                 _check_img(t, fmt, name, (h, w))
         if out is None:
@@ -1337,8 +1340,7 @@ class Context:
         _check_img(out, out_fmt, "out", (h, w))
         if out_variance is None:
             out_variance = torch.empty((h, w), dtype=torch.float16, device=self.device)
-        if not (out_variance.is_cuda and out_variance.dtype == torch.float16 and tuple(out_variance.shape) == (h, w) and out_variance.is_contiguous()):
-            raise ValueError(f"{who}: out_variance: expected contiguous cuda float16 {(h, w)}")
+        _check_dense(f"{who}: out_variance", out_variance, torch.float16, (h, w))
         return out, out_variance
 
     def ssr_prefilter(self, tile_list, counters, depth, normals, normal_fmt, roughness8, average, avg_fmt, radiance, radiance_fmt, variance, cb,
@@ -1347,13 +1349,8 @@ class Context:
         (level 0 of the hierarchy, rows may be strided); normals: int32 [H,W] (R10G10B10A2_UNORM) or float32 [H,W,4]; average: int32 [H8,W8] (R11G11B10_FLOAT) or
         float32 [H8,W8,4]; variance: float16 [H,W]. Pixels of unlisted tiles keep what `out` / `out_variance` held. Returns (out, out_variance)."""
         w, h = int(cb.bufferDimensions[0]), int(cb.bufferDimensions[1])
-        if not (depth.is_cuda and depth.dtype == torch.float32 and tuple(depth.shape) == (h, w) and depth.stride(1) == 1 and depth.stride(0) >= w):
-            raise ValueError(f"depth: expected cuda float32 {(h, w)} with unit column stride")
-        if normal_fmt == abi.FMT_R10G10B10A2_UNORM:
-            if not (normals.is_cuda and normals.dtype == torch.int32 and tuple(normals.shape) == (h, w) and normals.is_contiguous()):
-                raise ValueError(f"normals: expected contiguous cuda int32 {(h, w)} (R10G10B10A2_UNORM words)")
-        else:
-            _check_img(normals, normal_fmt, "normals", (h, w))
+        _check_plane("depth: expected cuda float32", depth, torch.float32, (h, w))
+        _check_normals("", "normals", normals, normal_fmt, (h, w))
         out, out_variance = self._denoise_common("ssr_prefilter", tile_list, counters, roughness8, average, avg_fmt, cb,
                                                  {"radiance": (radiance, radiance_fmt), "variance": (variance, None)}, out, out_fmt, out_variance)
         self._ck(self.lib.vqhip_ssr_prefilter(self._h, self._stream(stream), _ptr(tile_list), _ptr(counters), _ptr(depth), depth.stride(0), _ptr(normals), normal_fmt, 0,
@@ -1384,29 +1381,17 @@ class Context:
         is int32 [H8,W8] (R11G11B10_FLOAT words) or float32 [H8,W8,4]."""
         w, h = int(cb.bufferDimensions[0]), int(cb.bufferDimensions[1])
         h8, w8 = (h + 7) // 8, (w + 7) // 8
-        if not (tile_list.is_cuda and tile_list.dtype == torch.int32 and tile_list.is_contiguous() and tile_list.numel() >= h8 * w8):
-            raise ValueError(f"ssr_reproject: tile_list: expected contiguous cuda int32 [{h8 * w8}]")
-        if not (counters.is_cuda and counters.dtype == torch.int32 and counters.numel() >= 2 and counters.is_contiguous()):
-            raise ValueError("ssr_reproject: counters: expected contiguous cuda int32 [2]")
+        _check_tiles("ssr_reproject: ", tile_list, counters, h8 * w8)
 
-        def plane(t, name, dtype):                                                  # one element per pixel, rows may be strided
-            if not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == (h, w) and t.stride(1) == 1 and t.stride(0) >= w):
-                raise ValueError(f"ssr_reproject: {name}: expected cuda {dtype} {(h, w)} with unit column stride")
-            return t.stride(0)
-
-        def normal_plane(t, fmt, name):
-            if fmt == abi.FMT_R10G10B10A2_UNORM:
-                if not (t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (h, w) and t.is_contiguous()):
-                    raise ValueError(f"ssr_reproject: {name}: expected contiguous cuda int32 {(h, w)} (R10G10B10A2_UNORM words)")
-            else:
-                _check_img(t, fmt, name, (h, w))
+        def plane(t, name, dtype):                                                  # these messages spell the dtype with its module
+            return _check_plane(f"ssr_reproject: {name}: expected cuda {dtype}", t, dtype, (h, w))
         s = abi.SSRReprojectSurfaces()
         s.depth_pitch_px, s.depth_history_pitch_px = plane(depth, "depth", torch.float32), plane(depth_history, "depth_history", torch.float32)
         s.roughness_pitch_px, s.roughness_history_pitch_px = plane(roughness8, "roughness8", torch.uint8), plane(roughness8_history, "roughness8_history", torch.uint8)
         s.variance_history_pitch_px = plane(variance_history, "variance_history", torch.float16)
         s.sample_count_history_pitch_px = plane(sample_count_history, "sample_count_history", torch.float16)
-        normal_plane(normals, normal_fmt, "normals")
-        normal_plane(normal_history, normal_history_fmt, "normal_history")
+        _check_normals("ssr_reproject: ", "normals", normals, normal_fmt, (h, w))
+        _check_normals("ssr_reproject: ", "normal_history", normal_history, normal_history_fmt, (h, w))
         _check_img(radiance, radiance_fmt, "radiance", (h, w))
         _check_img(radiance_history, radiance_history_fmt, "radiance_history", (h, w))
         if motion_fmt not in (abi.FMT_RG16F, abi.FMT_RG32F):
@@ -1418,8 +1403,7 @@ class Context:
         if avg_fmt == abi.FMT_R11G11B10_FLOAT:
             if out_average is None:
                 out_average = torch.zeros((h8, w8), dtype=torch.int32, device=self.device)
-            if not (out_average.is_cuda and out_average.dtype == torch.int32 and tuple(out_average.shape) == (h8, w8) and out_average.is_contiguous()):
-                raise ValueError(f"ssr_reproject: out_average: expected contiguous cuda int32 {(h8, w8)} (R11G11B10_FLOAT words)")
+            _check_words("ssr_reproject: out_average", out_average, (h8, w8), "R11G11B10_FLOAT")
         else:
             if out_average is None:
                 out_average = torch.zeros((h8, w8, 4), dtype=torch.float32, device=self.device)
@@ -1428,8 +1412,7 @@ class Context:
         for t, name in ((out_variance, "out_variance"), (out_sample_count, "out_sample_count")):
             if t is None:
                 t = torch.zeros((h, w), dtype=torch.float16, device=self.device)
-            if not (t.is_cuda and t.dtype == torch.float16 and tuple(t.shape) == (h, w) and t.is_contiguous()):
-                raise ValueError(f"ssr_reproject: {name}: expected contiguous cuda float16 {(h, w)}")
+            _check_dense(f"ssr_reproject: {name}", t, torch.float16, (h, w))
             outs.append(t)
         out_variance, out_sample_count = outs
         for name, t in (("tile_list", tile_list), ("counters", counters), ("depth", depth), ("normals", normals), ("roughness", roughness8), ("depth_history", depth_history),

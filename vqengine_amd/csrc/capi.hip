@@ -1328,6 +1328,52 @@ int vqhip_composite_reflections(vqhip_ctx* ctx, void* stream, const void* reflec
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "composite_reflections launch");
 }
 
+// ---- SSR front ends (docs/DESIGN_DETAILS.md §7.11-7.13): what the six entry points below share ----------------------------------------------------------------
+namespace {
+struct Plane { const void* p; int pitchPx; size_t bpp; const char* name; };           // one full-frame plane; pitchPx 0: dense rows
+struct Span { const void* p; size_t n; const char* name; };                           // the bytes that a plane, a per-tile buffer or a list covers
+int pitchOr(int pitchPx, int W) { return pitchPx ? pitchPx : W; }
+size_t planeBytes(int W, int H, const Plane& q) { return ((size_t)(H - 1) * pitchOr(q.pitchPx, W) + W) * q.bpp; }
+Span spanOf(int W, int H, const Plane& q) { return { q.p, planeBytes(W, H, q), q.name }; }
+bool isNormalFmt(int f) { return f == VQHIP_FMT_R10G10B10A2_UNORM || f == VQHIP_FMT_RGBA32F; }
+bool isAvgFmt(int f) { return f == VQHIP_FMT_R11G11B10_FLOAT || f == VQHIP_FMT_RGBA32F; }
+size_t imgBpp(int f) { return f == VQHIP_FMT_RGBA32F ? 16 : 8; }
+size_t nrmBpp(int f) { return f == VQHIP_FMT_RGBA32F ? 16 : 4; }
+size_t avgBpp(int f) { return f == VQHIP_FMT_RGBA32F ? 16 : 4; }
+size_t motionBpp(int f) { return f == VQHIP_FMT_RG32F ? 8 : 4; }
+bool badEnv(const vqhip_envmap* env) { return !env->specular_cube || !env->brdf_lut || env->spec_res0 <= 0 || env->spec_mips <= 0 || env->lut_size <= 0; }
+void copyEnvRotation(float (&rot)[3][3], const VQ_SSSRConstants* cb) { for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) rot[i][j] = cb->envMapRotation.m[i][j]; }
+// cb->bufferDimensions as the frame; `suffix` ends the 4096 message. Returns VQHIP_OK or the failure already recorded in ctx
+int ssrFrame(vqhip_ctx* ctx, const char* who, const VQ_SSSRConstants* cb, const char* suffix, int* W, int* H) {
+    const uint32_t w = cb->bufferDimensions[0], h = cb->bufferDimensions[1];
+    if (w == 0 || h == 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, std::string(who) + ": bad bufferDimensions");
+    if (w > VQHIP_DEPTH_HIERARCHY_MAX_DIM || h > VQHIP_DEPTH_HIERARCHY_MAX_DIM)
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, std::string(who) + ": frames above 4096 in either dimension are not supported" + suffix);
+    *W = (int)w; *H = (int)h;
+    return VQHIP_OK;
+}
+const Plane* shortPitch(int W, const Plane* q, int n) {                                // the first plane whose rows are shorter than the frame's
+    for (int i = 0; i < n; ++i) if (pitchOr(q[i].pitchPx, W) < W) return &q[i];
+    return nullptr;
+}
+// The overlap questions of the denoiser passes: outputs against each other, against the inputs, against the tile list. Each finds the pair; the caller words the refusal
+bool overlapsAny(const Span& s, const Span* outs, int nOut) {
+    for (int i = 0; i < nOut; ++i) if (rangesOverlap(s.p, s.n, outs[i].p, outs[i].n)) return true;
+    return false;
+}
+bool overlapEachOther(const Span* outs, int nOut) {
+    for (int i = 0; i + 1 < nOut; ++i) if (overlapsAny(outs[i], outs + i + 1, nOut - i - 1)) return true;
+    return false;
+}
+const Plane* inputUnder(int W, int H, const Plane* in, int nIn, const Span* outs, int nOut) {     // the first input that one of `outs` lies on
+    for (int i = 0; i < nIn; ++i) if (overlapsAny(spanOf(W, H, in[i]), outs, nOut)) return &in[i];
+    return nullptr;
+}
+bool tilesUnder(int W, int H, const uint32_t* tileList, const uint32_t* counters, const Span* outs, int nOut) {
+    return overlapsAny({ tileList, (size_t)((W + 7) / 8) * ((H + 7) / 8) * 4, "" }, outs, nOut) || overlapsAny({ counters, 8, "" }, outs, nOut);
+}
+} // namespace
+
 int vqhip_ssr_environment_fallback(vqhip_ctx* ctx, void* stream, const void* sceneColorRoughness, vqhip_format sceneFmt, int scenePitchPx,
                                    const float* depth, int depthPitchPx, const void* normals, vqhip_format normalFmt, int normalPitchPx,
                                    int width, int height, const VQ_SSSRConstants* cb, const vqhip_envmap* env,
@@ -1338,18 +1384,18 @@ int vqhip_ssr_environment_fallback(vqhip_ctx* ctx, void* stream, const void* sce
     if (!sceneColorRoughness || !depth || !normals || !cb || !env || !outRadiance || width <= 0 || height <= 0 || (uint64_t)width * height >= (1ull << 28))
         return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_environment_fallback: bad argument");
     if (!isImageFmt(sceneFmt) || !isImageFmt(outFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_environment_fallback: scene colour and radiance must be RGBA32F or RGBA16F");
-    if (normalFmt != VQHIP_FMT_R10G10B10A2_UNORM && normalFmt != VQHIP_FMT_RGBA32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_environment_fallback: normals must be R10G10B10A2_UNORM or RGBA32F");
-    if (!env->specular_cube || !env->brdf_lut || env->spec_res0 <= 0 || env->spec_mips <= 0 || env->lut_size <= 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_environment_fallback: env needs the specular cube and the BRDF LUT");
+    if (!isNormalFmt(normalFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_environment_fallback: normals must be R10G10B10A2_UNORM or RGBA32F");
+    if (badEnv(env)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_environment_fallback: env needs the specular cube and the BRDF LUT");
     const uint32_t mc = cb->envMapSpecularIrradianceCubemapMipLevelCount;
     if (mc < 1 || mc > (uint32_t)env->spec_mips) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_environment_fallback: envMapSpecularIrradianceCubemapMipLevelCount must be in [1, env->spec_mips]");
-    auto pitch = [&](int p) { return p ? p : width; };
-    if (pitch(scenePitchPx) < width || pitch(depthPitchPx) < width || pitch(normalPitchPx) < width || pitch(outPitchPx) < width) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_environment_fallback: pitch < width");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     SsrArgs a;
+    a.scenePitch = pitchOr(scenePitchPx, width); a.depthPitch = pitchOr(depthPitchPx, width); a.normalPitch = pitchOr(normalPitchPx, width); a.outPitch = pitchOr(outPitchPx, width);
+    if (a.scenePitch < width || a.depthPitch < width || a.normalPitch < width || a.outPitch < width) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_environment_fallback: pitch < width");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
     a.scene = sceneColorRoughness; a.depth = depth; a.normals = normals; a.out = outRadiance; a.outRoughness = outExtractedRoughness;
-    a.width = width; a.height = height; a.scenePitch = pitch(scenePitchPx); a.depthPitch = pitch(depthPitchPx); a.normalPitch = pitch(normalPitchPx); a.outPitch = pitch(outPitchPx);
+    a.width = width; a.height = height;
     a.invProj = cb->invProjection; a.view = cb->view; a.invView = cb->invView;
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) a.rot[i][j] = cb->envMapRotation.m[i][j];
+    copyEnvRotation(a.rot, cb);
     a.invDimX = cb->inverseBufferDimensions[0]; a.invDimY = cb->inverseBufferDimensions[1];
     a.roughnessThreshold = cb->roughnessThreshold; a.mipCount = (float)mc;
     a.pow5ExpLog = ctx->pow5ExpLog; a.arithDxc = ctx->arithDxc; a.env = *env;
@@ -1365,13 +1411,11 @@ int vqhip_ssr_classify(vqhip_ctx* ctx, void* stream, const void* sceneColorRough
     if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "ssr_classify: ctx is NULL");
     CTX_GUARD(ctx, "ssr_classify");
     if (!sceneColorRoughness || !depth || !cb || !rayList || !counters) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_classify: NULL argument");
-    const uint32_t W = cb->bufferDimensions[0], H = cb->bufferDimensions[1];
-    if (W == 0 || H == 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_classify: bad bufferDimensions");
-    if (W > VQHIP_DEPTH_HIERARCHY_MAX_DIM || H > VQHIP_DEPTH_HIERARCHY_MAX_DIM)
-        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_classify: frames above 4096 in either dimension are not supported (the range of the depth hierarchy)");
+    int W, H;
+    if (int rc = ssrFrame(ctx, "ssr_classify", cb, " (the range of the depth hierarchy)", &W, &H)) return rc;
     if (!isImageFmt(sceneFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_classify: the scene colour must be RGBA32F or RGBA16F");
-    auto pitch = [&](int p) { return p ? p : (int)W; };
-    if (pitch(scenePitchPx) < (int)W || pitch(depthPitchPx) < (int)W || pitch(variancePitchPx) < (int)W) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_classify: pitch < width");
+    const int scenePitch = pitchOr(scenePitchPx, W), depthPitch = pitchOr(depthPitchPx, W), variancePitch = pitchOr(variancePitchPx, W);
+    if (scenePitch < W || depthPitch < W || variancePitch < W) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_classify: pitch < width");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     if (!ctx->ssrTiles) HIP_TRY(ctx, hipMalloc(&ctx->ssrTiles, sizeof(uint32_t) * 2 * kMaxSsrTiles));
@@ -1382,9 +1426,9 @@ int vqhip_ssr_classify(vqhip_ctx* ctx, void* stream, const void* sceneColorRough
     a.scene = sceneColorRoughness; a.depth = depth; a.variance = varianceHistory;
     a.rayList = rayList; a.counters = counters; a.tileList = denoiserTileList;
     a.tileRays = (uint32_t*)ctx->ssrTiles; a.tileFlag = a.tileRays + kMaxSsrTiles;
-    a.width = (int)W; a.height = (int)H; a.scenePitch = pitch(scenePitchPx); a.depthPitch = pitch(depthPitchPx); a.variancePitch = pitch(variancePitchPx);
+    a.width = W; a.height = H; a.scenePitch = scenePitch; a.depthPitch = depthPitch; a.variancePitch = variancePitch;
     a.sceneF32 = sceneFmt == VQHIP_FMT_RGBA32F;
-    a.tilesX = ((int)W + 7) / 8; a.tilesY = ((int)H + 7) / 8;
+    a.tilesX = (W + 7) / 8; a.tilesY = (H + 7) / 8;
     a.roughnessThreshold = cb->roughnessThreshold; a.varianceThreshold = cb->varianceThreshold;
     a.samplesPerQuad = cb->samplesPerQuad; a.varianceGuided = cb->temporalVarianceGuidedTracingEnabled;
     hipError_t e = launch_ssr_classify(st, a);
@@ -1405,29 +1449,25 @@ int vqhip_ssr_intersect(vqhip_ctx* ctx, void* stream, const uint32_t* rayList, c
     CTX_GUARD(ctx, "ssr_intersect");
     if (!rayList || !counters || !litScene || !hierarchy || !normals || !extractedRoughness || !blueNoise || !cb || !env || !radiance)
         return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: NULL argument");
-    const uint32_t W = cb->bufferDimensions[0], H = cb->bufferDimensions[1];
-    if (W == 0 || H == 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: bad bufferDimensions");
-    if (W > VQHIP_DEPTH_HIERARCHY_MAX_DIM || H > VQHIP_DEPTH_HIERARCHY_MAX_DIM)
-        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_intersect: frames above 4096 in either dimension are not supported (the range of the depth hierarchy)");
+    int W, H;
+    if (int rc = ssrFrame(ctx, "ssr_intersect", cb, " (the range of the depth hierarchy)", &W, &H)) return rc;
     if (!isImageFmt(litFmt) || !isImageFmt(radianceFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_intersect: lit scene and radiance must be RGBA32F or RGBA16F");
-    if (normalFmt != VQHIP_FMT_R10G10B10A2_UNORM && normalFmt != VQHIP_FMT_RGBA32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_intersect: normals must be R10G10B10A2_UNORM or RGBA32F");
+    if (!isNormalFmt(normalFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_intersect: normals must be R10G10B10A2_UNORM or RGBA32F");
     if (cb->maxTraversalIntersections > 256) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_intersect: maxTraversalIntersections above 256 (the engine's slider range) is not supported");
     if (cb->mostDetailedMip > 5) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_intersect: mostDetailedMip above 5 is not supported");
-    if (!env->specular_cube || !env->brdf_lut || env->spec_res0 <= 0 || env->spec_mips <= 0 || env->lut_size <= 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: env needs the specular cube and the BRDF LUT");
-    auto pitch = [&](int p) { return p ? p : (int)W; };
-    if (pitch(litPitchPx) < (int)W || pitch(normalPitchPx) < (int)W || pitch(radiancePitchPx) < (int)W) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: pitch < width");
-    if (rangesOverlap(litScene, ((size_t)(H - 1) * pitch(litPitchPx) + W) * (litFmt == VQHIP_FMT_RGBA32F ? 16 : 8),
-                      radiance, ((size_t)(H - 1) * pitch(radiancePitchPx) + W) * (radianceFmt == VQHIP_FMT_RGBA32F ? 16 : 8)))
-        return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: radiance overlaps the lit scene");
+    if (badEnv(env)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: env needs the specular cube and the BRDF LUT");
+    const Plane planes[] = { { litScene, litPitchPx, imgBpp(litFmt), "" }, { radiance, radiancePitchPx, imgBpp(radianceFmt), "" }, { normals, normalPitchPx, nrmBpp(normalFmt), "" } };
+    if (shortPitch(W, planes, 3)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: pitch < width");
+    if (rangesOverlap(litScene, planeBytes(W, H, planes[0]), radiance, planeBytes(W, H, planes[1]))) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: radiance overlaps the lit scene");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     SsrTraceArgs a;
     std::memset(&a, 0, sizeof(a));
     a.rayList = rayList; a.counters = counters; a.lit = litScene; a.mips = hierarchy; a.normals = normals; a.roughness = extractedRoughness; a.noise = blueNoise; a.out = radiance;
-    a.width = (int)W; a.height = (int)H; a.litPitch = pitch(litPitchPx); a.normalPitch = pitch(normalPitchPx); a.outPitch = pitch(radiancePitchPx);
+    a.width = W; a.height = H; a.litPitch = pitchOr(litPitchPx, W); a.normalPitch = pitchOr(normalPitchPx, W); a.outPitch = pitchOr(radiancePitchPx, W);
     a.litF32 = litFmt == VQHIP_FMT_RGBA32F; a.normF32 = normalFmt == VQHIP_FMT_RGBA32F; a.outF32 = radianceFmt == VQHIP_FMT_RGBA32F;
-    a.levels = vqhip_mip_level_count((int)W, (int)H);
+    a.levels = vqhip_mip_level_count(W, H);
     a.invViewProj = cb->invViewProjection; a.proj = cb->projection; a.invProj = cb->invProjection; a.view = cb->view; a.invView = cb->invView;
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) a.rot[i][j] = cb->envMapRotation.m[i][j];
+    copyEnvRotation(a.rot, cb);
     a.invDimX = cb->inverseBufferDimensions[0]; a.invDimY = cb->inverseBufferDimensions[1]; a.thickness = cb->depthBufferThickness;
     a.maxIter = cb->maxTraversalIntersections; a.minOcc = cb->minTraversalOccupancy; a.mostDetailedMip = cb->mostDetailedMip;
     a.pow5ExpLog = ctx->pow5ExpLog; a.arithDxc = ctx->arithDxc; a.env = *env;
@@ -1437,38 +1477,29 @@ int vqhip_ssr_intersect(vqhip_ctx* ctx, void* stream, const uint32_t* rayList, c
 
 // ---- SSR denoiser passes 2 and 3 (ssr_denoise.hip; docs/DESIGN_DETAILS.md §7.12) -----------------------------------------------------------
 namespace {
-struct DenoisePlane { const void* p; int pitch; size_t bpp; const char* name; };
 // fills what both passes share and validates it; returns VQHIP_OK or the failure already recorded in ctx
 int denoiseCommon(vqhip_ctx* ctx, const char* who, const VQ_SSSRConstants* cb, vqhip_format avgFmt, vqhip_format radianceFmt, vqhip_format outFmt,
-                  const DenoisePlane* in, int nIn, const uint32_t* tileList, const uint32_t* counters, const void* avg, void* outRadiance, int outPitchPx, void* outVariance, int outVariancePitchPx, SsrDenoiseArgs* a) {
+                  const Plane* in, int nIn, const uint32_t* tileList, const uint32_t* counters, const void* avg, void* outRadiance, int outPitchPx, void* outVariance, int outVariancePitchPx, SsrDenoiseArgs* a) {
     const std::string w(who);
-    const uint32_t W = cb->bufferDimensions[0], H = cb->bufferDimensions[1];
-    if (W == 0 || H == 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": bad bufferDimensions");
-    if (W > VQHIP_DEPTH_HIERARCHY_MAX_DIM || H > VQHIP_DEPTH_HIERARCHY_MAX_DIM)
-        return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": frames above 4096 in either dimension are not supported");
+    int W, H;
+    if (int rc = ssrFrame(ctx, who, cb, "", &W, &H)) return rc;
     if (!isImageFmt(radianceFmt) || !isImageFmt(outFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": radiance and output radiance must be RGBA32F or RGBA16F");
-    if (avgFmt != VQHIP_FMT_R11G11B10_FLOAT && avgFmt != VQHIP_FMT_RGBA32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": the average radiance must be R11G11B10_FLOAT or RGBA32F");
-    auto pitch = [&](int p) { return p ? p : (int)W; };
-    if (pitch(outPitchPx) < (int)W || pitch(outVariancePitchPx) < (int)W) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": pitch < width");
-    for (int i = 0; i < nIn; ++i) if (pitch(in[i].pitch) < (int)W) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": pitch < width");
-    const int tilesX = ((int)W + 7) / 8, tilesY = ((int)H + 7) / 8;
-    const size_t outBytes = ((size_t)(H - 1) * pitch(outPitchPx) + W) * (outFmt == VQHIP_FMT_RGBA32F ? 16 : 8);
-    const size_t varBytes = ((size_t)(H - 1) * pitch(outVariancePitchPx) + W) * 2;
-    if (rangesOverlap(outRadiance, outBytes, outVariance, varBytes)) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": the outputs overlap each other");
-    auto hitsOutput = [&](const void* p, size_t n) { return rangesOverlap(p, n, outRadiance, outBytes) || rangesOverlap(p, n, outVariance, varBytes); };
-    for (int i = 0; i < nIn; ++i)
-        if (hitsOutput(in[i].p, ((size_t)(H - 1) * pitch(in[i].pitch) + W) * in[i].bpp))
-            return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": an output overlaps the input " + in[i].name + " (the apron reads neighbours that other tiles write)");
-    if (hitsOutput(avg, (size_t)tilesX * tilesY * (avgFmt == VQHIP_FMT_RGBA32F ? 16 : 4)))
-        return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": an output overlaps the input averageRadiance");
-    if (hitsOutput(tileList, (size_t)tilesX * tilesY * 4) || hitsOutput(counters, 8))
-        return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": an output overlaps the tile list or its counters");
-    a->width = (int)W; a->height = (int)H; a->tilesX = tilesX; a->tilesY = tilesY; a->avgW = tilesX; a->avgH = tilesY;
+    if (!isAvgFmt(avgFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": the average radiance must be R11G11B10_FLOAT or RGBA32F");
+    const Plane out[] = { { outRadiance, outPitchPx, imgBpp(outFmt), "" }, { outVariance, outVariancePitchPx, 2, "" } };
+    if (shortPitch(W, out, 2) || shortPitch(W, in, nIn)) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": pitch < width");
+    const int tilesX = (W + 7) / 8, tilesY = (H + 7) / 8;
+    const Span outs[] = { spanOf(W, H, out[0]), spanOf(W, H, out[1]) };
+    if (overlapEachOther(outs, 2)) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": the outputs overlap each other");
+    if (const Plane* p = inputUnder(W, H, in, nIn, outs, 2))
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": an output overlaps the input " + p->name + " (the apron reads neighbours that other tiles write)");
+    if (overlapsAny({ avg, (size_t)tilesX * tilesY * avgBpp(avgFmt), "" }, outs, 2)) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": an output overlaps the input averageRadiance");
+    if (tilesUnder(W, H, tileList, counters, outs, 2)) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": an output overlaps the tile list or its counters");
+    a->width = W; a->height = H; a->tilesX = tilesX; a->tilesY = tilesY; a->avgW = tilesX; a->avgH = tilesY;
     a->avg = avg; a->avgF32 = avgFmt == VQHIP_FMT_RGBA32F; a->radF32 = radianceFmt == VQHIP_FMT_RGBA32F; a->outF32 = outFmt == VQHIP_FMT_RGBA32F;
-    a->outRadiance = outRadiance; a->outVariance = outVariance; a->outPitch = pitch(outPitchPx); a->outVariancePitch = pitch(outVariancePitchPx);
+    a->outRadiance = outRadiance; a->outVariance = outVariance; a->outPitch = pitchOr(outPitchPx, W); a->outVariancePitch = pitchOr(outVariancePitchPx, W);
     a->arithDxc = ctx->arithDxc; a->roughnessThreshold = cb->roughnessThreshold; a->temporalStability = cb->temporalStabilityFactor;
     auto roundUp8 = [](uint32_t v) { return (v & ~7u) == v ? v : v + 8u; };                       // FFX_DNSR_Reflections_RoundUp8 as written
-    a->roundUp8W = (float)roundUp8(W); a->roundUp8H = (float)roundUp8(H);
+    a->roundUp8W = (float)roundUp8((uint32_t)W); a->roundUp8H = (float)roundUp8((uint32_t)H);
     return VQHIP_OK;
 }
 } // namespace
@@ -1483,17 +1514,16 @@ int vqhip_ssr_prefilter(vqhip_ctx* ctx, void* stream, const uint32_t* denoiserTi
     CTX_GUARD(ctx, "ssr_prefilter");
     if (!denoiserTileList || !counters || !depth || !normals || !extractedRoughness || !averageRadiance || !radiance || !variance || !cb || !outRadiance || !outVariance)
         return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_prefilter: NULL argument");
-    if (normalFmt != VQHIP_FMT_R10G10B10A2_UNORM && normalFmt != VQHIP_FMT_RGBA32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_prefilter: normals must be R10G10B10A2_UNORM or RGBA32F");
+    if (!isNormalFmt(normalFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_prefilter: normals must be R10G10B10A2_UNORM or RGBA32F");
     SsrDenoiseArgs a;
     std::memset(&a, 0, sizeof(a));
-    const DenoisePlane in[] = { { depth, depthPitchPx, 4, "depth" }, { normals, normalPitchPx, normalFmt == VQHIP_FMT_RGBA32F ? (size_t)16 : (size_t)4, "normals" },
-                                { extractedRoughness, 0, 1, "extractedRoughness" }, { radiance, radiancePitchPx, radianceFmt == VQHIP_FMT_RGBA32F ? (size_t)16 : (size_t)8, "radiance" },
-                                { variance, variancePitchPx, 2, "variance" } };
+    const Plane in[] = { { depth, depthPitchPx, 4, "depth" }, { normals, normalPitchPx, nrmBpp(normalFmt), "normals" }, { extractedRoughness, 0, 1, "extractedRoughness" },
+                         { radiance, radiancePitchPx, imgBpp(radianceFmt), "radiance" }, { variance, variancePitchPx, 2, "variance" } };
     int rc = denoiseCommon(ctx, "ssr_prefilter", cb, avgFmt, radianceFmt, outFmt, in, 5, denoiserTileList, counters, averageRadiance, outRadiance, outPitchPx, outVariance, outVariancePitchPx, &a);
     if (rc) return rc;
-    auto pitch = [&](int p) { return p ? p : a.width; };
+    const int W = a.width;
     a.tileList = denoiserTileList; a.counters = counters; a.depth = depth; a.normals = normals; a.roughness = extractedRoughness; a.radiance = radiance; a.variance = variance;
-    a.depthPitch = pitch(depthPitchPx); a.normalPitch = pitch(normalPitchPx); a.radiancePitch = pitch(radiancePitchPx); a.variancePitch = pitch(variancePitchPx);
+    a.depthPitch = pitchOr(depthPitchPx, W); a.normalPitch = pitchOr(normalPitchPx, W); a.radiancePitch = pitchOr(radiancePitchPx, W); a.variancePitch = pitchOr(variancePitchPx, W);
     a.normF32 = normalFmt == VQHIP_FMT_RGBA32F;
     for (int i = 0; i < 4; ++i) { a.ipZ[i] = cb->invProjection.m[i][2]; a.ipW[i] = cb->invProjection.m[i][3]; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1515,15 +1545,15 @@ int vqhip_ssr_resolve_temporal(vqhip_ctx* ctx, void* stream, const uint32_t* den
     if (!isImageFmt(reprojectedFmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_resolve_temporal: the reprojected radiance must be RGBA32F or RGBA16F");
     SsrDenoiseArgs a;
     std::memset(&a, 0, sizeof(a));
-    const DenoisePlane in[] = { { extractedRoughness, 0, 1, "extractedRoughness" }, { radiance, radiancePitchPx, radianceFmt == VQHIP_FMT_RGBA32F ? (size_t)16 : (size_t)8, "radiance" },
-                                { reprojectedRadiance, reprojectedPitchPx, reprojectedFmt == VQHIP_FMT_RGBA32F ? (size_t)16 : (size_t)8, "reprojectedRadiance" },
-                                { variance, variancePitchPx, 2, "variance" }, { sampleCount, sampleCountPitchPx, 2, "sampleCount" } };
+    const Plane in[] = { { extractedRoughness, 0, 1, "extractedRoughness" }, { radiance, radiancePitchPx, imgBpp(radianceFmt), "radiance" },
+                         { reprojectedRadiance, reprojectedPitchPx, imgBpp(reprojectedFmt), "reprojectedRadiance" },
+                         { variance, variancePitchPx, 2, "variance" }, { sampleCount, sampleCountPitchPx, 2, "sampleCount" } };
     int rc = denoiseCommon(ctx, "ssr_resolve_temporal", cb, avgFmt, radianceFmt, outFmt, in, 5, denoiserTileList, counters, averageRadiance, outRadiance, outPitchPx, outVariance, outVariancePitchPx, &a);
     if (rc) return rc;
-    auto pitch = [&](int p) { return p ? p : a.width; };
+    const int W = a.width;
     a.tileList = denoiserTileList; a.counters = counters; a.roughness = extractedRoughness; a.radiance = radiance; a.reprojected = reprojectedRadiance;
     a.variance = variance; a.sampleCount = sampleCount;
-    a.radiancePitch = pitch(radiancePitchPx); a.reprojectedPitch = pitch(reprojectedPitchPx); a.variancePitch = pitch(variancePitchPx); a.sampleCountPitch = pitch(sampleCountPitchPx);
+    a.radiancePitch = pitchOr(radiancePitchPx, W); a.reprojectedPitch = pitchOr(reprojectedPitchPx, W); a.variancePitch = pitchOr(variancePitchPx, W); a.sampleCountPitch = pitchOr(sampleCountPitchPx, W);
     a.reprojF32 = reprojectedFmt == VQHIP_FMT_RGBA32F;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipError_t e = launch_ssr_resolve_temporal((hipStream_t)stream, a, ctx->nCUs);
@@ -1540,45 +1570,33 @@ int vqhip_ssr_reproject(vqhip_ctx* ctx, void* stream, const vqhip_ssr_reproject_
         !io->radiance || !io->radiance_history || !io->motion_vectors || !io->variance_history || !io->sample_count_history ||
         !io->out_reprojected || !io->out_average || !io->out_variance || !io->out_sample_count)
         return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_reproject: NULL plane");
-    const uint32_t W = cb->bufferDimensions[0], H = cb->bufferDimensions[1];
-    if (W == 0 || H == 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_reproject: bad bufferDimensions");
-    if (W > VQHIP_DEPTH_HIERARCHY_MAX_DIM || H > VQHIP_DEPTH_HIERARCHY_MAX_DIM)
-        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_reproject: frames above 4096 in either dimension are not supported");
-    auto isNormalFmt = [](int f) { return f == VQHIP_FMT_R10G10B10A2_UNORM || f == VQHIP_FMT_RGBA32F; };
+    int W, H;
+    if (int rc = ssrFrame(ctx, "ssr_reproject", cb, "", &W, &H)) return rc;
     if (!isNormalFmt(io->normals_fmt) || !isNormalFmt(io->normal_history_fmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_reproject: normals must be R10G10B10A2_UNORM or RGBA32F");
     if (!isImageFmt(io->radiance_fmt) || !isImageFmt(io->radiance_history_fmt) || !isImageFmt(io->out_reprojected_fmt))
         return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_reproject: radiance, its history and the reprojected radiance must be RGBA32F or RGBA16F");
     if (io->motion_fmt != VQHIP_FMT_RG16F && io->motion_fmt != VQHIP_FMT_RG32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_reproject: motion vectors must be RG16F or RG32F");
-    if (io->out_average_fmt != VQHIP_FMT_R11G11B10_FLOAT && io->out_average_fmt != VQHIP_FMT_RGBA32F)
-        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_reproject: the average radiance must be R11G11B10_FLOAT or RGBA32F");
-    auto pitch = [&](int p) { return p ? p : (int)W; };
-    auto imgBpp = [](int f) { return f == VQHIP_FMT_RGBA32F ? (size_t)16 : (size_t)8; };
-    auto nrmBpp = [](int f) { return f == VQHIP_FMT_RGBA32F ? (size_t)16 : (size_t)4; };
-    const int tilesX = ((int)W + 7) / 8, tilesY = ((int)H + 7) / 8;
-    struct Plane { const void* p; int pitch; size_t bpp; const char* name; };
+    if (!isAvgFmt(io->out_average_fmt)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "ssr_reproject: the average radiance must be R11G11B10_FLOAT or RGBA32F");
+    auto pitch = [&](int p) { return pitchOr(p, W); };
+    const int tilesX = (W + 7) / 8, tilesY = (H + 7) / 8;
     const Plane in[] = { { io->depth, io->depth_pitch_px, 4, "depth" }, { io->normals, io->normals_pitch_px, nrmBpp(io->normals_fmt), "normals" },
                          { io->roughness, io->roughness_pitch_px, 1, "roughness" }, { io->depth_history, io->depth_history_pitch_px, 4, "depth_history" },
                          { io->normal_history, io->normal_history_pitch_px, nrmBpp(io->normal_history_fmt), "normal_history" },
                          { io->roughness_history, io->roughness_history_pitch_px, 1, "roughness_history" }, { io->radiance, io->radiance_pitch_px, imgBpp(io->radiance_fmt), "radiance" },
                          { io->radiance_history, io->radiance_history_pitch_px, imgBpp(io->radiance_history_fmt), "radiance_history" },
-                         { io->motion_vectors, io->motion_pitch_px, io->motion_fmt == VQHIP_FMT_RG32F ? (size_t)8 : (size_t)4, "motion_vectors" },
+                         { io->motion_vectors, io->motion_pitch_px, motionBpp(io->motion_fmt), "motion_vectors" },
                          { io->variance_history, io->variance_history_pitch_px, 2, "variance_history" }, { io->sample_count_history, io->sample_count_history_pitch_px, 2, "sample_count_history" } };
     const Plane outFull[] = { { io->out_reprojected, io->out_reprojected_pitch_px, imgBpp(io->out_reprojected_fmt), "out_reprojected" },
                               { io->out_variance, io->out_variance_pitch_px, 2, "out_variance" }, { io->out_sample_count, io->out_sample_count_pitch_px, 2, "out_sample_count" } };
-    for (const Plane& p : in) if (pitch(p.pitch) < (int)W) return fail(ctx, VQHIP_ERR_INVALID_ARG, std::string("ssr_reproject: pitch < width: ") + p.name);
-    for (const Plane& p : outFull) if (pitch(p.pitch) < (int)W) return fail(ctx, VQHIP_ERR_INVALID_ARG, std::string("ssr_reproject: pitch < width: ") + p.name);
-    auto bytes = [&](const Plane& p) { return ((size_t)(H - 1) * pitch(p.pitch) + W) * p.bpp; };
-    struct Span { const void* p; size_t n; const char* name; };
-    const Span outs[] = { { outFull[0].p, bytes(outFull[0]), outFull[0].name }, { outFull[1].p, bytes(outFull[1]), outFull[1].name }, { outFull[2].p, bytes(outFull[2]), outFull[2].name },
-                          { io->out_average, (size_t)tilesX * tilesY * (io->out_average_fmt == VQHIP_FMT_RGBA32F ? 16 : 4), "out_average" } };
-    for (int i = 0; i < 4; ++i) for (int j = i + 1; j < 4; ++j)
-        if (rangesOverlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_reproject: the outputs overlap each other");
+    for (const Plane* p : { shortPitch(W, in, 11), shortPitch(W, outFull, 3) })
+        if (p) return fail(ctx, VQHIP_ERR_INVALID_ARG, std::string("ssr_reproject: pitch < width: ") + p->name);
+    const Span outs[] = { spanOf(W, H, outFull[0]), spanOf(W, H, outFull[1]), spanOf(W, H, outFull[2]),
+                          { io->out_average, (size_t)tilesX * tilesY * avgBpp(io->out_average_fmt), "out_average" } };
+    if (overlapEachOther(outs, 4)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_reproject: the outputs overlap each other");
     for (const Span& o : outs) {
-        for (const Plane& p : in)
-            if (rangesOverlap(p.p, bytes(p), o.p, o.n))
-                return fail(ctx, VQHIP_ERR_INVALID_ARG, std::string("ssr_reproject: ") + o.name + " overlaps the input " + p.name + " (tiles read what other tiles would write; ping-pong the history)");
-        if (rangesOverlap(io->tile_list, (size_t)tilesX * tilesY * 4, o.p, o.n) || rangesOverlap(io->counters, 8, o.p, o.n))
-            return fail(ctx, VQHIP_ERR_INVALID_ARG, std::string("ssr_reproject: ") + o.name + " overlaps the tile list or its counters");
+        if (const Plane* p = inputUnder(W, H, in, 11, &o, 1))
+            return fail(ctx, VQHIP_ERR_INVALID_ARG, std::string("ssr_reproject: ") + o.name + " overlaps the input " + p->name + " (tiles read what other tiles would write; ping-pong the history)");
+        if (tilesUnder(W, H, io->tile_list, io->counters, &o, 1)) return fail(ctx, VQHIP_ERR_INVALID_ARG, std::string("ssr_reproject: ") + o.name + " overlaps the tile list or its counters");
     }
     SsrReprojectArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1586,7 +1604,7 @@ int vqhip_ssr_reproject(vqhip_ctx* ctx, void* stream, const vqhip_ssr_reproject_
     a.depthHist = io->depth_history; a.normalHist = io->normal_history; a.roughnessHist = io->roughness_history;
     a.radiance = io->radiance; a.radianceHist = io->radiance_history; a.motion = io->motion_vectors; a.varianceHist = io->variance_history; a.sampleCountHist = io->sample_count_history;
     a.outReprojected = io->out_reprojected; a.outAverage = io->out_average; a.outVariance = io->out_variance; a.outSampleCount = io->out_sample_count;
-    a.width = (int)W; a.height = (int)H; a.tilesX = tilesX; a.tilesY = tilesY;
+    a.width = W; a.height = H; a.tilesX = tilesX; a.tilesY = tilesY;
     a.depthPitch = pitch(io->depth_pitch_px); a.normalPitch = pitch(io->normals_pitch_px); a.roughnessPitch = pitch(io->roughness_pitch_px);
     a.depthHistPitch = pitch(io->depth_history_pitch_px); a.normalHistPitch = pitch(io->normal_history_pitch_px); a.roughnessHistPitch = pitch(io->roughness_history_pitch_px);
     a.radiancePitch = pitch(io->radiance_pitch_px); a.radianceHistPitch = pitch(io->radiance_history_pitch_px); a.motionPitch = pitch(io->motion_pitch_px);
@@ -1734,59 +1752,6 @@ size_t vqhip_cacao_plane_offset_bytes(int width, int height, int plane, int slic
     }
 }
 
-int vqhip_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_t depthPitchBytes, const void* normals, int normalFmt, size_t normalPitchBytes,
-        const VQ_CacaoConstants* shared, const VQ_CacaoConstants perPass[4], int qualityLevel, int blurPassCount,
-        void* work, size_t workBytes, uint8_t* ao, size_t aoPitchBytes, int width, int height) {
-    vqk::Range range_("Ambient Occlusion (FidelityFX CACAO)");
-    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "cacao: ctx is NULL");
-    CTX_GUARD(ctx, "cacao");
-    if (!depth || !normals || !shared || !perPass || !work || !ao) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: NULL argument");
-    if (width <= 0 || height <= 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: bad dimensions");
-    if (width > VQHIP_CACAO_MAX_DIM || height > VQHIP_CACAO_MAX_DIM) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: frames above 16384 in either dimension are not supported");
-    if (qualityLevel < VQHIP_CACAO_QUALITY_LOWEST || qualityLevel > VQHIP_CACAO_QUALITY_HIGHEST) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: qualityLevel is not an FFX_CACAO_Quality");
-    if (qualityLevel == VQHIP_CACAO_QUALITY_HIGHEST)
-        return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: quality HIGHEST (the adaptive base pass, the importance map and the importance-driven tap loop) is vqhip_adaptive_cacao, with its larger work buffer; this entry point runs HIGH");
-    if (qualityLevel != VQHIP_CACAO_QUALITY_HIGH) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: quality levels LOWEST, LOW and MEDIUM are not implemented; use HIGH");
-    if (normalFmt != VQHIP_FMT_R10G10B10A2_UNORM && normalFmt != VQHIP_FMT_RGBA32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "cacao: normals must be R10G10B10A2_UNORM or RGBA32F");
-    if (blurPassCount < 0 || blurPassCount > VQHIP_CACAO_MAX_BLUR_PASSES) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: blurPassCount must be 0..8");
-    const size_t normalPx = normalFmt == VQHIP_FMT_RGBA32F ? 16 : 4;
-    if (depthPitchBytes < (size_t)width * 4 || depthPitchBytes % 4) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: depthPitchBytes below 4 * width or not a multiple of 4");
-    if (normalPitchBytes < (size_t)width * normalPx || normalPitchBytes % normalPx) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: normalPitchBytes below the row size or not a multiple of the pixel size");
-    if (aoPitchBytes < (size_t)width) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: aoPitchBytes below the width");
-    if (depthPitchBytes / 4 > 0x7fffffffu || normalPitchBytes / normalPx > 0x7fffffffu || aoPitchBytes > 0x7fffffffu) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: pitch too large");
-    CacaoLayout L;
-    cacaoLayout(width, height, &L);
-    if (workBytes < L.total) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: workBytes below vqhip_cacao_work_bytes(width, height)");
-    if ((uintptr_t)work % 256) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: work must be 256-byte aligned");
-    // the constants must describe THIS frame: the kernels address by the integer sizes and compute with the blocks' floats
-    auto sizesMatch = [&](const VQ_CacaoConstants& c) {
-        return c.SSAOBufferDimensions[0] == (float)L.hw && c.SSAOBufferDimensions[1] == (float)L.hh && c.DepthBufferDimensions[0] == (float)width &&
-               c.DepthBufferDimensions[1] == (float)height && c.InputOutputBufferDimensions[0] == (float)width && c.InputOutputBufferDimensions[1] == (float)height &&
-               c.DeinterleavedDepthBufferDimensions[0] == (float)L.hw && c.DeinterleavedDepthBufferDimensions[1] == (float)L.hh;
-    };
-    if (!sizesMatch(*shared)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: the shared constants are not those of this frame size at native resolution (FFX_CACAO_UpdateBufferSizeInfo(width, height, false))");
-    for (int i = 0; i < 4; ++i) {
-        if (!sizesMatch(perPass[i])) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: a per-pass constants block is not of this frame size at native resolution");
-        if (perPass[i].PassIndex != i) return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: perPass[i].PassIndex must be i");
-    }
-    const size_t depthBytes = (size_t)(height - 1) * depthPitchBytes + (size_t)width * 4, normalBytes = (size_t)(height - 1) * normalPitchBytes + (size_t)width * normalPx;
-    const size_t aoBytes = (size_t)(height - 1) * aoPitchBytes + (size_t)width;
-    if (rangesOverlap(work, L.total, depth, depthBytes) || rangesOverlap(work, L.total, normals, normalBytes) || rangesOverlap(work, L.total, ao, aoBytes) ||
-        rangesOverlap(ao, aoBytes, depth, depthBytes) || rangesOverlap(ao, aoBytes, normals, normalBytes))
-        return fail(ctx, VQHIP_ERR_INVALID_ARG, "cacao: work and ao must not overlap each other or the inputs");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    CacaoArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.depth = depth; a.normals = normals; a.work = (uint8_t*)work; a.ao = ao;
-    for (int k = 0; k < 4; ++k) { a.offDepth[k] = L.depth[k]; a.mw[k] = L.mw[k]; a.mh[k] = L.mh[k]; }
-    a.offNormals = L.normals; a.offPing = L.ping; a.offPong = L.pong;
-    a.width = width; a.height = height; a.hw = L.hw; a.hh = L.hh;
-    a.depthPitch = (int)(depthPitchBytes / 4); a.normalPitch = (int)(normalPitchBytes / normalPx); a.aoPitch = (int)aoPitchBytes;
-    a.normF32 = normalFmt == VQHIP_FMT_RGBA32F; a.blurPasses = blurPassCount;
-    hipError_t e = launch_cacao((hipStream_t)stream, a, *shared, perPass);
-    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "cacao launch");
-}
-
 // ---- FidelityFX CACAO at quality HIGHEST (cacao.hip; docs/DESIGN_DETAILS.md §7.15): HIGH's work layout as the prefix, three planes appended ------------------
 namespace {
 struct AdaptiveCacaoLayout { CacaoLayout high; size_t importance, importancePong, counter, total; int iw, ih; };
@@ -1818,44 +1783,51 @@ size_t vqhip_adaptive_cacao_plane_offset_bytes(int width, int height, int plane,
     }
 }
 
-int vqhip_adaptive_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_t depthPitchBytes, const void* normals, int normalFmt, size_t normalPitchBytes,
-        const VQ_CacaoConstants* shared, const VQ_CacaoConstants perPass[4], int blurPassCount,
+// Both entry points behind their prologue: vqhip_cacao (adaptive false: `qualityLevel` must be HIGH, HIGH's work layout) and vqhip_adaptive_cacao (HIGHEST)
+static int cacaoCall(vqhip_ctx* ctx, const char* who, bool adaptive, void* stream, const float* depth, size_t depthPitchBytes, const void* normals, int normalFmt,
+        size_t normalPitchBytes, const VQ_CacaoConstants* shared, const VQ_CacaoConstants perPass[4], int qualityLevel, int blurPassCount,
         void* work, size_t workBytes, uint8_t* ao, size_t aoPitchBytes, int width, int height) {
-    vqk::Range range_("Ambient Occlusion (FidelityFX CACAO)");
-    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: ctx is NULL");
-    CTX_GUARD(ctx, "adaptive_cacao");
-    if (!depth || !normals || !shared || !perPass || !work || !ao) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: NULL argument");
-    if (width <= 0 || height <= 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: bad dimensions");
-    if (width > VQHIP_CACAO_MAX_DIM || height > VQHIP_CACAO_MAX_DIM) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "adaptive_cacao: frames above 16384 in either dimension are not supported");
-    if (normalFmt != VQHIP_FMT_R10G10B10A2_UNORM && normalFmt != VQHIP_FMT_RGBA32F) return fail(ctx, VQHIP_ERR_UNSUPPORTED, "adaptive_cacao: normals must be R10G10B10A2_UNORM or RGBA32F");
-    if (blurPassCount < 0 || blurPassCount > VQHIP_CACAO_MAX_BLUR_PASSES) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: blurPassCount must be 0..8");
+    const std::string w(who);
+    auto bad = [&](int code, const char* what) { return fail(ctx, code, w + ": " + what); };
+    if (!depth || !normals || !shared || !perPass || !work || !ao) return bad(VQHIP_ERR_INVALID_ARG, "NULL argument");
+    if (width <= 0 || height <= 0) return bad(VQHIP_ERR_INVALID_ARG, "bad dimensions");
+    if (width > VQHIP_CACAO_MAX_DIM || height > VQHIP_CACAO_MAX_DIM) return bad(VQHIP_ERR_UNSUPPORTED, "frames above 16384 in either dimension are not supported");
+    if (!adaptive) {
+        if (qualityLevel < VQHIP_CACAO_QUALITY_LOWEST || qualityLevel > VQHIP_CACAO_QUALITY_HIGHEST) return bad(VQHIP_ERR_INVALID_ARG, "qualityLevel is not an FFX_CACAO_Quality");
+        if (qualityLevel == VQHIP_CACAO_QUALITY_HIGHEST)
+            return bad(VQHIP_ERR_UNSUPPORTED, "quality HIGHEST (the adaptive base pass, the importance map and the importance-driven tap loop) is vqhip_adaptive_cacao, with its larger work buffer; this entry point runs HIGH");
+        if (qualityLevel != VQHIP_CACAO_QUALITY_HIGH) return bad(VQHIP_ERR_UNSUPPORTED, "quality levels LOWEST, LOW and MEDIUM are not implemented; use HIGH");
+    }
+    if (!isNormalFmt(normalFmt)) return bad(VQHIP_ERR_UNSUPPORTED, "normals must be R10G10B10A2_UNORM or RGBA32F");
+    if (blurPassCount < 0 || blurPassCount > VQHIP_CACAO_MAX_BLUR_PASSES) return bad(VQHIP_ERR_INVALID_ARG, "blurPassCount must be 0..8");
     const size_t normalPx = normalFmt == VQHIP_FMT_RGBA32F ? 16 : 4;
-    if (depthPitchBytes < (size_t)width * 4 || depthPitchBytes % 4) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: depthPitchBytes below 4 * width or not a multiple of 4");
-    if (normalPitchBytes < (size_t)width * normalPx || normalPitchBytes % normalPx) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: normalPitchBytes below the row size or not a multiple of the pixel size");
-    if (aoPitchBytes < (size_t)width) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: aoPitchBytes below the width");
-    if (depthPitchBytes / 4 > 0x7fffffffu || normalPitchBytes / normalPx > 0x7fffffffu || aoPitchBytes > 0x7fffffffu) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: pitch too large");
-    AdaptiveCacaoLayout A;
+    if (depthPitchBytes < (size_t)width * 4 || depthPitchBytes % 4) return bad(VQHIP_ERR_INVALID_ARG, "depthPitchBytes below 4 * width or not a multiple of 4");
+    if (normalPitchBytes < (size_t)width * normalPx || normalPitchBytes % normalPx) return bad(VQHIP_ERR_INVALID_ARG, "normalPitchBytes below the row size or not a multiple of the pixel size");
+    if (aoPitchBytes < (size_t)width) return bad(VQHIP_ERR_INVALID_ARG, "aoPitchBytes below the width");
+    if (depthPitchBytes / 4 > 0x7fffffffu || normalPitchBytes / normalPx > 0x7fffffffu || aoPitchBytes > 0x7fffffffu) return bad(VQHIP_ERR_INVALID_ARG, "pitch too large");
+    AdaptiveCacaoLayout A;                                                               // HIGH's layout is its prefix
     adaptiveCacaoLayout(width, height, &A);
     const CacaoLayout& L = A.high;
-    if (workBytes < A.total) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: workBytes below vqhip_adaptive_cacao_work_bytes(width, height)");
-    if ((uintptr_t)work % 256) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: work must be 256-byte aligned");
-    // the constants must describe THIS frame, the importance map included: the kernels address by the integer sizes and compute with the blocks' floats
+    const size_t total = adaptive ? A.total : L.total;
+    if (workBytes < total) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": workBytes below vqhip_" + w + "_work_bytes(width, height)");
+    if ((uintptr_t)work % 256) return bad(VQHIP_ERR_INVALID_ARG, "work must be 256-byte aligned");
+    // the constants must describe THIS frame, at HIGHEST the importance map included: the kernels address by the integer sizes and compute with the blocks' floats
     auto sizesMatch = [&](const VQ_CacaoConstants& c) {
         return c.SSAOBufferDimensions[0] == (float)L.hw && c.SSAOBufferDimensions[1] == (float)L.hh && c.DepthBufferDimensions[0] == (float)width &&
                c.DepthBufferDimensions[1] == (float)height && c.InputOutputBufferDimensions[0] == (float)width && c.InputOutputBufferDimensions[1] == (float)height &&
                c.DeinterleavedDepthBufferDimensions[0] == (float)L.hw && c.DeinterleavedDepthBufferDimensions[1] == (float)L.hh &&
-               c.ImportanceMapDimensions[0] == (float)A.iw && c.ImportanceMapDimensions[1] == (float)A.ih;
+               (!adaptive || (c.ImportanceMapDimensions[0] == (float)A.iw && c.ImportanceMapDimensions[1] == (float)A.ih));
     };
-    if (!sizesMatch(*shared)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: the shared constants are not those of this frame size at native resolution (FFX_CACAO_UpdateBufferSizeInfo(width, height, false))");
+    if (!sizesMatch(*shared)) return bad(VQHIP_ERR_INVALID_ARG, "the shared constants are not those of this frame size at native resolution (FFX_CACAO_UpdateBufferSizeInfo(width, height, false))");
     for (int i = 0; i < 4; ++i) {
-        if (!sizesMatch(perPass[i])) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: a per-pass constants block is not of this frame size at native resolution");
-        if (perPass[i].PassIndex != i) return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: perPass[i].PassIndex must be i");
+        if (!sizesMatch(perPass[i])) return bad(VQHIP_ERR_INVALID_ARG, "a per-pass constants block is not of this frame size at native resolution");
+        if (perPass[i].PassIndex != i) return bad(VQHIP_ERR_INVALID_ARG, "perPass[i].PassIndex must be i");
     }
     const size_t depthBytes = (size_t)(height - 1) * depthPitchBytes + (size_t)width * 4, normalBytes = (size_t)(height - 1) * normalPitchBytes + (size_t)width * normalPx;
     const size_t aoBytes = (size_t)(height - 1) * aoPitchBytes + (size_t)width;
-    if (rangesOverlap(work, A.total, depth, depthBytes) || rangesOverlap(work, A.total, normals, normalBytes) || rangesOverlap(work, A.total, ao, aoBytes) ||
+    if (rangesOverlap(work, total, depth, depthBytes) || rangesOverlap(work, total, normals, normalBytes) || rangesOverlap(work, total, ao, aoBytes) ||
         rangesOverlap(ao, aoBytes, depth, depthBytes) || rangesOverlap(ao, aoBytes, normals, normalBytes))
-        return fail(ctx, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: work and ao must not overlap each other or the inputs");
+        return bad(VQHIP_ERR_INVALID_ARG, "work and ao must not overlap each other or the inputs");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     CacaoArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1866,8 +1838,28 @@ int vqhip_adaptive_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_
     a.depthPitch = (int)(depthPitchBytes / 4); a.normalPitch = (int)(normalPitchBytes / normalPx); a.aoPitch = (int)aoPitchBytes;
     a.normF32 = normalFmt == VQHIP_FMT_RGBA32F; a.blurPasses = blurPassCount;
     const CacaoAdaptiveArgs ad = { A.importance, A.importancePong, A.counter, A.iw, A.ih };
-    hipError_t e = launch_cacao_adaptive((hipStream_t)stream, a, ad, *shared, perPass);
-    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, "adaptive_cacao launch");
+    hipError_t e = adaptive ? launch_cacao_adaptive((hipStream_t)stream, a, ad, *shared, perPass) : launch_cacao((hipStream_t)stream, a, *shared, perPass);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (w + " launch").c_str());
+}
+
+int vqhip_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_t depthPitchBytes, const void* normals, int normalFmt, size_t normalPitchBytes,
+        const VQ_CacaoConstants* shared, const VQ_CacaoConstants perPass[4], int qualityLevel, int blurPassCount,
+        void* work, size_t workBytes, uint8_t* ao, size_t aoPitchBytes, int width, int height) {
+    vqk::Range range_("Ambient Occlusion (FidelityFX CACAO)");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "cacao: ctx is NULL");
+    CTX_GUARD(ctx, "cacao");
+    return cacaoCall(ctx, "cacao", false, stream, depth, depthPitchBytes, normals, normalFmt, normalPitchBytes, shared, perPass, qualityLevel, blurPassCount,
+                     work, workBytes, ao, aoPitchBytes, width, height);
+}
+
+int vqhip_adaptive_cacao(vqhip_ctx* ctx, void* stream, const float* depth, size_t depthPitchBytes, const void* normals, int normalFmt, size_t normalPitchBytes,
+        const VQ_CacaoConstants* shared, const VQ_CacaoConstants perPass[4], int blurPassCount,
+        void* work, size_t workBytes, uint8_t* ao, size_t aoPitchBytes, int width, int height) {
+    vqk::Range range_("Ambient Occlusion (FidelityFX CACAO)");
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "adaptive_cacao: ctx is NULL");
+    CTX_GUARD(ctx, "adaptive_cacao");
+    return cacaoCall(ctx, "adaptive_cacao", true, stream, depth, depthPitchBytes, normals, normalFmt, normalPitchBytes, shared, perPass, VQHIP_CACAO_QUALITY_HIGHEST, blurPassCount,
+                     work, workBytes, ao, aoPitchBytes, width, height);
 }
 
 // ---- The rasterisers' front ends (docs/DESIGN_DETAILS.md §7.16-7.20): what the eight entry points below share -------------------------------------------------
