@@ -355,7 +355,9 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * vqhip_shadow_depth (+ _work_bytes), vqhip_shadow_mesh / _draw / _view, VQHIP_CULL_*, option raster_tile;
                                * vqhip_scene_depth (+ _work_bytes), vqhip_scene_depth_draw / _targets;
                                * vqhip_scene_interpolants (+ _work_bytes), vqhip_scene_surface_draw, vqhip_scene_interpolant_targets, option interp_form;
-                               * vqhip_scene_masked_depth, vqhip_shadow_masked_depth (+ _work_bytes), vqhip_scene_masked_depth_draw, vqhip_shadow_masked_draw / _view */
+                               * vqhip_scene_masked_depth, vqhip_shadow_masked_depth (+ _work_bytes), vqhip_scene_masked_depth_draw, vqhip_shadow_masked_draw / _view;
+                               * vqhip_scene_quad_interpolants and the three _quad producers, vqhip_scene_quad_targets;
+                               * vqhip_object_ids (+ _work_bytes), vqhip_object_id_draw; vqhip_outline (+ _work_bytes), VQ_OutlineData, vqhip_outline_draw / _targets */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -1263,8 +1265,8 @@ VQHIP_API int vqhip_scene_interpolants(vqhip_ctx* ctx, void* stream, const vqhip
  * A masked draw's mesh is the engine's vertex: uv at byte 36, strideBytes >= 44. Textures are vqhip_texture2d: RGBA8_UNORM mip chains in device memory; the
  * descriptors (materials, texDiffuseAlpha) are HOST memory, consumed before the call returns.
  * (The names put `masked` before `depth` so that the prefixes vqhip_scene_depth* / vqhip_shadow_depth* keep denoting the opaque pair alone.)
- * Out of scope: the heightmap and tessellation variants, the separate texAlphaMask map (t3: bound, not read by these shaders), the ObjectID and Outline passes'
- * masked permutations.
+ * Out of scope: the heightmap and tessellation variants, the separate texAlphaMask map (t3: bound, not read by these shaders), the Outline pass's
+ * masked permutation (the ObjectID pass's rides on this call: vqhip_object_ids, below).
  * Work: the opaque call's layout is the prefix; behind it a device table of the draws' textures (48 bytes per draw, staged through the constant ring like
  * vqhip_scene_interpolants' table: one table-copy launch per ring slot) and one 64-byte side record per masked instanced triangle (the unclipped clip-space
  * x, y, w and the uv of its three vertices, the draw's table slot). Kernels with a masked draw: counter(s), table copy, setup, fill. No allocation, no memset
@@ -1345,6 +1347,107 @@ VQHIP_API int vqhip_forward_lighting_from_materials_quad(vqhip_ctx* ctx, void* s
 VQHIP_API int vqhip_scene_normals_from_materials_quad(vqhip_ctx* ctx, void* stream,
         const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
         void* out, vqhip_format outFmt, int out_row_pitch_px, const void* quadUV, int quad_pitch_px);
+
+/* ---- The ObjectID pass (picking): ObjectIDPass::RecordCommands (ObjectIDPass.cpp:160-278) == ObjectID.hlsl, as a visibility-buffer resolve over an owner plane.
+ * The pass clears its own D32 depth to 1.0 and its R32G32B32A32_SINT target to (0, 0, 0, 0), sets the viewport {0, 0, W, H, 0, 1} at one sample, and draws the main
+ * view's draw list with cull NONE for EVERY draw (the pass ignores iFaceCull), DepthClipEnable TRUE, depth LESS with writes; PSMain returns
+ * int4(ObjID[instance].x, meshID, materialID, ObjID[instance].w). Its rasteriser therefore is vqhip_scene_depth (or vqhip_scene_masked_depth) at samples 1 with
+ * every draw's cullMode set to VQHIP_CULL_NONE — the pass's OWN depth call, not the pre-pass's, whose cull modes differ — and its pixel shader is this call over that
+ * call's `primitive` plane. docs/DESIGN_DETAILS.md §7.21 is the normative statement; tests/object_ids_ref.py states it in numpy:
+ *   P0  q is decoded as §7.18 I0 decodes it: first(draw) = the instanced triangles of the draws before it, instance = (q - first(draw)) / numTris. A pixel whose q
+ *       is 0xFFFFFFFF, or at or beyond the call's instanced triangles, receives (0, 0, 0, 0), the pass's clear colour; any other pixel receives
+ *       (objID[instance].x, meshID, materialID, objID[instance].w). Any owner content is safe: no q moves a load or a store out of bounds.
+ *   draws   host array, consumed before the call returns: the draw list of the depth call that produced `owner`, in its order, with its index and instance
+ *           counts — that gives q its meaning. objID is device memory, read when the kernel runs. Draws with numIndices == 0 own no q.
+ *   owner   uint32 [height][owner_pitch_px] (0 = width), 4-byte aligned.
+ *   ids     int32 [height][ids_pitch_px][4] (0 = width), 16-byte aligned: the pass's render target; one texel of it is what the engine reads back (ReadBackPixel).
+ *   work    vqhip_object_ids_work_bytes(numDraws) bytes, 256-byte aligned: the device home of the draw table.
+ * The table is staged through the context's constant ring (one table-copy launch per ring slot, which holds well over 1 000 draws), then ONE kernel. No allocation, no memset node, no
+ * readback. Option interp_form lane | wave selects the resolve's form as it does for vqhip_scene_interpolants (a wave whose 64 pixels share one q fetches the
+ * draw once); both give the same bits. Default: wave for frames of 2^22 pixels or more, lane below (profiles/r22a_editor_passes.md).
+ * The "_AlphaMasked" permutation (ObjectID.hlsl: discard where texDiffuse.Sample(AnisoSampler, uv * scale + offset).a < 0.01) rides on vqhip_scene_masked_depth's
+ * rule M3: fragments that rule discards never reach the owner plane, so the ids show what lies behind the holes. One difference from ObjectID.hlsl: M3 discards
+ * only when the material's HasDiffuseMap bit is set, ObjectID.hlsl has no such test. It shows only for a material flagged masked WITHOUT a diffuse map, which
+ * Material::IsAlphaMasked excludes.
+ * Out of scope: the tessellation and heightmap variants of the pass. The Outline pass is vqhip_outline (below); the Magnifier pass runs on the swap-chain image. */
+typedef struct vqhip_object_id_draw {   /* one DrawIndexedInstanced of ObjectIDPass::RecordCommands, in the order of the depth call that produced `owner` */
+    uint32_t numIndices, numInstances;  /* what that call drew: gives q its meaning (numIndices a multiple of 3, numInstances 1 .. 64) */
+    const int32_t* objID;               /* device, int4 [numInstances], 4-byte aligned: PerObjectLightingData.ObjID; .x and .w are read */
+    int32_t meshID, materialID;
+} vqhip_object_id_draw;
+VQHIP_STATIC_ASSERT(sizeof(vqhip_object_id_draw) == 24 && offsetof(vqhip_object_id_draw, objID) == 8 && offsetof(vqhip_object_id_draw, meshID) == 16,
+                    "vqhip_object_id_draw layout");
+/* Bytes of work for a call of numDraws draws: 32 per draw, rounded up to 256 (256 for numDraws == 0). 0 for numDraws < 0. Host-only. */
+VQHIP_API size_t vqhip_object_ids_work_bytes(int numDraws);
+/* Returns VQHIP_ERR_INVALID_ARG — launching nothing, leaving `ids` untouched — for NULL pointers (ctx, owner, ids, work, draws with numDraws > 0, a draw's objID),
+ * numDraws < 0, width or height outside 1 .. 8192, a pitch that is negative or below width, ids not 16-byte aligned, owner or an objID not 4-byte aligned,
+ * numInstances outside 1 .. 64, numIndices % 3 != 0, work not 256-byte aligned, workBytes below vqhip_object_ids_work_bytes(numDraws), or ids overlapping the owner
+ * plane or the work buffer; VQHIP_ERR_UNSUPPORTED for more than 20 000 draws with numIndices > 0 or 2^29 or more instanced triangles in one call (the limits of
+ * vqhip_scene_depth). */
+VQHIP_API int vqhip_object_ids(vqhip_ctx* ctx, void* stream, const vqhip_object_id_draw* draws, int numDraws, int width, int height,
+        const uint32_t* owner, int owner_pitch_px, int32_t* ids /* int4 [height][ids_pitch_px], 16-byte aligned */, int ids_pitch_px,
+        void* work, size_t workBytes);
+
+/* ---- The Outline pass (selection highlight): both passes of OutlinePass::RecordCommands (OutlinePass.cpp:247-405, Outline.hlsl; drawn last into scene colour,
+ * SceneRendering.cpp:514) in one call, at 1 sample per pixel. The pass clears its own D24S8 (depth 1.0, stencil 0); each selected (mesh, material) pair is one
+ * non-instanced draw with a constant buffer OutlineData. Every draw runs pass 0 ("RenderStencil": no render target, position = mul(mul(matProj, matWorldView),
+ * vPosition), cull NONE, depth LESS with writes, stencil ALWAYS / REPLACE 1), then every draw runs pass 1 ("RenderOutline": the vertex moved in view space by
+ * normalize(mul(matNormalView, float4(Normal, 0)).xyx) * 0.5 — the swizzle is .xyx in the reference and is kept as written —, depth ALWAYS without writes, stencil
+ * NOT_EQUAL 1, blending off, PSMain returns the interpolated pow(Color, 2.2) into the RGBA16F target). docs/DESIGN_DETAILS.md §7.21 is the normative statement
+ * (rules O1 .. O6); tests/outline_ref.py states it in numpy on top of tests/scene_depth_ref.py:
+ *   O1  pass-0 vertex: P = (x, y + 0.0f, z); WVP.m[r][c] = ((WV[r][0]*Pr[0][c] + WV[r][1]*Pr[1][c]) + WV[r][2]*Pr[2][c]) + WV[r][3]*Pr[3][c], every operation
+ *       rounded in binary32; clip[j] = §7.16 R1's mulPoint(P, WVP, j). Binary32 whatever vqhip_set_arithmetic says.
+ *   O2  pass-1 vertex: V[j] = mulPoint(P, matWorldView, j) for j < 3; n[j] = ((N.x*M[0][j] + N.y*M[1][j]) + N.z*M[2][j]) + 0.0f*M[3][j] with M = matNormalView;
+ *       v = (n[0], n[1], n[0]); viewNormal = the contract's as-written normalize(v); E = V + viewNormal * 0.5f componentwise (one product, one sum);
+ *       clip[j] = mulPoint(E, matProj, j). A vertex with a non-finite clip component drops its triangle (both rules) — in particular a normal whose view-space x
+ *       and y are both zero drops every pass-1 triangle that uses it.
+ *   O3  both passes then run §7.17's V2 (seven planes), V3 (viewport, 16.8 snap) and R4 (int64 edge functions, top-left rule, the sample at the pixel centre). Cull NONE.
+ *   O4  the mark: a pixel is marked iff some pass-0 fragment of ANY draw covers it with a V5 depth whose saturated value is below 1.0 (LESS against the cleared D24:
+ *       every binary32 below 1.0 converts to a code below 0xFFFFFF). Order-independent.
+ *   O5  the write: a pixel is written iff it is not marked and at least one pass-1 fragment covers it (depth ALWAYS: any depth counts). It receives the colour of
+ *       the covering draw SUBMITTED LAST; the four channels are pow_(Color.c, 2.2f) in the contract's pow, each stored round-to-nearest-even as a half (a NaN as
+ *       0x7E00 with its sign). Every other pixel of sceneColor keeps its bits.
+ *   O6  the interpolated constant attribute equals the constant.
+ * O1's matrix product, O4's D24 conversion and O6 are UNPINNED against a D3D12 device (docs/WARP_CALIBRATION.md §5), beside what §7.17 lists (V2, V5).
+ * Kernels on `stream`: counter, one setup launch per ring slot of draws (both vertex stages, both clips, records of two kinds), one tile fill (a 32-bit LDS word
+ * per pixel: a mark bit by atomic OR, 1 + the draw's number by atomic MAX — no order dependence), which also clears selection / writer. No allocation, no memset
+ * node, no readback. Draw descriptors are host memory, consumed before the call returns; meshes and constant buffers are device memory, read when the kernels run.
+ * numDraws == 0 leaves sceneColor untouched and clears selection / writer. Option raster_tile 64 is honoured.
+ * Out of scope: 4x MSAA (the library has no per-sample scene colour: vqhip_forward_lighting_msaa shades and resolves in one kernel; it would take a sample-mask /
+ * writer output here and an override input in that resolve), the pass's "_AlphaMasked" permutation, the tessellation and heightmap variants (the null heightmap's
+ * + 0.0f is kept), the Magnifier pass. */
+typedef struct VQ_OutlineData {  /* byte for byte the cbuffer OutlineData of Outline.hlsl / FOutlineRenderData::FConstantBuffer (DrawData.h:69-79) */
+    VQ_matrix matWorld, matWorldView, matNormalView, matProj, matViewInverse;
+    VQ_float4 Color, uvScaleBias; float Scale, HeightDisplacement;
+    float pad_[2];               /* the tail padding of the 16-byte aligned C++ struct */
+} VQ_OutlineData;
+typedef struct vqhip_outline_draw {
+    vqhip_shadow_mesh mesh;      /* the engine's vertex: position @0, normal @12; strideBytes >= 24, a multiple of 4 */
+    const VQ_OutlineData* cb;    /* device, 4-byte aligned; read when the kernels run: matWorldView, matNormalView, matProj, Color */
+} vqhip_outline_draw;
+typedef struct vqhip_outline_targets {   /* device */
+    void*     sceneColor;        /* RGBA16F [height][pitch], 8-byte aligned: modified IN PLACE, only where O5 writes */
+    uint8_t*  selection;         /* or NULL: 1 where pass 0 marked the pixel (the stencil), else 0 */
+    uint32_t* writer;            /* or NULL, 4-byte aligned: index (into draws) of the draw whose colour the pixel received, 0xFFFFFFFF for none */
+    int32_t pitch, selection_pitch, writer_pitch, reserved;   /* pixels (= bytes for selection) per row, 0 = width; reserved 0 */
+} vqhip_outline_targets;
+VQHIP_STATIC_ASSERT(sizeof(VQ_OutlineData) == 368 && offsetof(VQ_OutlineData, matWorldView) == 64 && offsetof(VQ_OutlineData, matNormalView) == 128 &&
+                    offsetof(VQ_OutlineData, matProj) == 192 && offsetof(VQ_OutlineData, matViewInverse) == 256 && offsetof(VQ_OutlineData, Color) == 320 &&
+                    offsetof(VQ_OutlineData, uvScaleBias) == 336 && offsetof(VQ_OutlineData, Scale) == 352 && offsetof(VQ_OutlineData, HeightDisplacement) == 356,
+                    "VQ_OutlineData layout");
+VQHIP_STATIC_ASSERT(sizeof(vqhip_outline_draw) == 40 && offsetof(vqhip_outline_draw, cb) == 32, "vqhip_outline_draw layout");
+VQHIP_STATIC_ASSERT(sizeof(vqhip_outline_targets) == 40 && offsetof(vqhip_outline_targets, pitch) == 24, "vqhip_outline_targets layout");
+/* Bytes of work for a call that draws `triangles` triangles (sum over draws of numIndices / 3): a counter, 16 bytes per draw of the colour table (sized for
+ * min(triangles, 20 000) draws: a draw with indices has a triangle) and sixteen records of 56 bytes per triangle (each pass: a fan of at most eight). 0 for 2^28
+ * or more triangles (the records must fit the 32-bit counter) or a size that does not fit size_t. Host-only. */
+VQHIP_API size_t vqhip_outline_work_bytes(uint64_t triangles);
+/* Returns VQHIP_ERR_INVALID_ARG — launching nothing, leaving the outputs untouched — for NULL pointers (ctx, out, sceneColor, work, draws with numDraws > 0, a
+ * mesh's positions or indices, cb), numDraws < 0, width or height outside 1 .. 8192, a negative pitch or one below width, reserved != 0, sceneColor not 8-byte
+ * aligned, writer not 4-byte aligned, an indexBits other than 16 / 32, numIndices % 3 != 0, a stride below 24 or not a multiple of 4, positions or cb not 4-byte
+ * aligned, indices not aligned to their size, work not 256-byte aligned, workBytes below vqhip_outline_work_bytes of the call's own triangle count, or an output
+ * overlapping another output or the work buffer; VQHIP_ERR_UNSUPPORTED for more than 20 000 draws with indices or 2^28 or more triangles in one call. */
+VQHIP_API int vqhip_outline(vqhip_ctx* ctx, void* stream, const vqhip_outline_draw* draws, int numDraws, int width, int height,
+        const vqhip_outline_targets* out, void* work, size_t workBytes);
 
 #ifdef __cplusplus
 }

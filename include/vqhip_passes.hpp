@@ -1046,4 +1046,129 @@ private:
     unsigned mWidth = 0, mHeight = 0;
 };
 
+// ---------------------------------------------------------------------------------------------------------------
+// Picking == ObjectIDPass::RecordCommands (ObjectIDPass.cpp:160-278) and its ReadBackPixel (:283-303): the pass's OWN depth call — the main view's draw list
+// through vqhip_scene_masked_depth at one sample with EVERY draw's cullMode forced to VQHIP_CULL_NONE (the pass ignores iFaceCull; a frame without a masked material
+// enqueues what vqhip_scene_depth enqueues) — and then vqhip_object_ids over that call's owner plane (docs/DESIGN_DETAILS.md §7.21 P0). FDrawParameters is
+// MaskedDepthPrePass's draw list and materials plus, per draw, what ObjectID.hlsl writes: the uploaded ObjID block, the mesh id and the material id. The pass owns
+// its depth plane (the pass's D32), the owner plane, the ids plane (the pass's R32G32B32A32_SINT target) and both work buffers. W and H are the window's.
+// ---------------------------------------------------------------------------------------------------------------
+class ObjectIDPass : public RenderPassBase {
+public:
+    struct FResourceParameters : public IRenderPassResourceCollection {};
+    struct FObjectID { const int32_t* ObjID = nullptr; int32_t MeshID = 0; int32_t MaterialID = 0; };   // ObjID: device, int4 [numInstances]
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        const std::vector<vqhip_scene_depth_draw>* Draws = nullptr;             // the main view's draw list; cullMode is ignored. nullptr or empty: ids all zero
+        const std::vector<FObjectID>* IDs = nullptr;                            // per draw, the size of *Draws
+        const std::vector<int32_t>* MaterialIndex = nullptr;                    // per draw, or nullptr; < 0: no material (opaque) — as MaskedDepthPrePass
+        const vqhip_material* Materials = nullptr; int NumMaterials = 0;        // HOST
+    };
+    explicit ObjectIDPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    ~ObjectIDPass() override { OnDestroyWindowSizeDependentResources(); }
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { OnDestroyWindowSizeDependentResources(); mDepthWork.Release(); mIdsWork.Release(); }
+    void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override {
+        OnDestroyWindowSizeDependentResources();
+        mWidth = Width; mHeight = Height;
+        const size_t px = (size_t)Width * Height;
+        mDepth = Alloc(px * 4); mOwner = Alloc(px * 4); mIds = Alloc(px * 16);
+    }
+    void OnDestroyWindowSizeDependentResources() override { Free(mDepth); Free(mOwner); Free(mIds); mWidth = mHeight = 0; }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p || !mDepth || !mOwner || !mIds) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        const int numDraws = p->Draws ? (int)p->Draws->size() : 0;
+        if ((numDraws && (!p->IDs || (int)p->IDs->size() != numDraws)) || (p->MaterialIndex && (int)p->MaterialIndex->size() != numDraws)) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        mDraws.resize((size_t)numDraws); mIdDraws.resize((size_t)numDraws);
+        uint64_t triangles = 0, masked = 0;
+        for (int d = 0; d < numDraws; ++d) {
+            vqhip_scene_masked_depth_draw& m = mDraws[(size_t)d];
+            m.draw = (*p->Draws)[(size_t)d];
+            m.draw.cullMode = VQHIP_CULL_NONE;                                   // ObjectIDPass.cpp: one rasteriser state for every draw
+            const int32_t index = p->MaterialIndex ? (*p->MaterialIndex)[(size_t)d] : -1;
+            if (index >= p->NumMaterials || (index >= 0 && !p->Materials)) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+            m.material = index >= 0 ? p->Materials + index : nullptr;
+            const uint64_t n = InstancedTriangles(m.draw);
+            triangles += n;
+            if (m.material && (m.material->texDiffuse.reserved & VQHIP_MATERIAL_ALPHA_MASKED)) masked += n;
+            const FObjectID& id = (*p->IDs)[(size_t)d];
+            vqhip_object_id_draw& o = mIdDraws[(size_t)d];
+            o.numIndices = m.draw.mesh.numIndices; o.numInstances = m.draw.numInstances; o.objID = id.ObjID; o.meshID = id.MeshID; o.materialID = id.MaterialID;
+        }
+        if (!mDepthWork.Reserve(vqhip_scene_masked_depth_work_bytes(triangles, masked, numDraws)) || !mIdsWork.Reserve(vqhip_object_ids_work_bytes(numDraws))) { mStatus = VQHIP_ERR_HIP; return; }
+        vqhip_scene_depth_targets t = {};
+        t.depth = (float*)mDepth; t.primitive = (uint32_t*)mOwner;
+        mStatus = vqhip_scene_masked_depth(mCtx, p->Stream, numDraws ? mDraws.data() : nullptr, numDraws, (int)mWidth, (int)mHeight, 1, &t, mDepthWork.ptr, mDepthWork.bytes);
+        if (mStatus != VQHIP_OK) return;
+        mStatus = vqhip_object_ids(mCtx, p->Stream, numDraws ? mIdDraws.data() : nullptr, numDraws, (int)mWidth, (int)mHeight, (const uint32_t*)mOwner, 0, (int32_t*)mIds, 0,
+                                   mIdsWork.ptr, mIdsWork.bytes);
+    }
+    // ObjectIDPass::ReadBackPixel: the int4 at (X, Y) of the ids plane after the work enqueued on Stream — one 16-byte copy and a stream wait. Coordinates outside
+    // the window (and a failed copy) return (-1, -1, -1, -1), as the reference does.
+    struct FPixel { int32_t x, y, z, w; };
+    FPixel ReadBackPixel(int X, int Y, void* Stream = nullptr) const {
+        FPixel px = { -1, -1, -1, -1 };
+        if (!mIds || X < 0 || Y < 0 || X >= (int)mWidth || Y >= (int)mHeight) return px;
+        FPixel got;
+        const char* src = (const char*)mIds + ((size_t)Y * mWidth + (size_t)X) * 16;
+        if (hipMemcpyAsync(&got, src, 16, hipMemcpyDeviceToHost, (hipStream_t)Stream) != hipSuccess || hipStreamSynchronize((hipStream_t)Stream) != hipSuccess) return px;
+        return got;
+    }
+    const int32_t* GetObjectIDs() const { return (const int32_t*)mIds; }          // int4 [H][W]
+    const float* GetDepth() const { return (const float*)mDepth; }                // the pass's own depth, [H][W]
+    const uint32_t* GetOwner() const { return (const uint32_t*)mOwner; }          // [H][W]
+    size_t GetDepthWorkBytes() const { return mDepthWork.bytes; }
+    size_t GetIdsWorkBytes() const { return mIdsWork.bytes; }
+private:
+    WorkBuffer mDepthWork, mIdsWork;
+    void* mDepth = nullptr; void* mOwner = nullptr; void* mIds = nullptr;
+    unsigned mWidth = 0, mHeight = 0;
+    std::vector<vqhip_scene_masked_depth_draw> mDraws;                          // consumed by the calls before they return; kept to spare the allocations
+    std::vector<vqhip_object_id_draw> mIdDraws;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// Selection highlight == OutlinePass::RecordCommands (OutlinePass.cpp:247-405), drawn last into scene colour by VQRenderer::RenderOutline
+// (SceneRendering.cpp:514): vqhip_outline, both passes in one call at one sample per pixel (docs/DESIGN_DETAILS.md §7.21 O1 .. O6). FDrawParameters carries the
+// selected draws (FSceneDrawData::outlineRenderParams, each FOutlineRenderData as a vqhip_outline_draw whose cb is the uploaded OutlineData block) and the scene
+// colour to write into (RGBA16F, HipSceneColorPass's). Selection and Writer are the library's additions (the stencil mark and the draw each written pixel took its
+// colour from); leave them NULL for the engine's own output. W and H are the window's. The pass owns the work buffer. With MSAA the engine draws the outline
+// into the multisampled target: that form is not built (§7.21), the call refuses nothing but writes the one-sample picture.
+// ---------------------------------------------------------------------------------------------------------------
+class OutlinePass : public RenderPassBase {
+public:
+    struct FResourceParameters : public IRenderPassResourceCollection {};
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        const std::vector<vqhip_outline_draw>* Draws = nullptr;                 // nullptr or empty: nothing selected — scene colour stays, Selection / Writer are cleared
+        void* SceneColor = nullptr;                                             // RGBA16F [H][SceneColorPitch], modified in place
+        int SceneColorPitch = 0;                                                // pixels per row, 0 = W
+        uint8_t* Selection = nullptr;                                           // optional, [H][W]
+        uint32_t* Writer = nullptr;                                             // optional, [H][W]
+    };
+    explicit OutlinePass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { mWork.Release(); }
+    void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override { mWidth = Width; mHeight = Height; }
+    void OnDestroyWindowSizeDependentResources() override { mWidth = mHeight = 0; }
+    bool Reserve(uint64_t Triangles) { return mWork.Reserve(vqhip_outline_work_bytes(Triangles)); }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p || !p->SceneColor) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        uint64_t triangles = 0;
+        const int numDraws = p->Draws ? (int)p->Draws->size() : 0;
+        for (int d = 0; d < numDraws; ++d) triangles += (*p->Draws)[(size_t)d].mesh.numIndices / 3;
+        if (!Reserve(triangles)) { mStatus = VQHIP_ERR_HIP; return; }
+        vqhip_outline_targets t = {};
+        t.sceneColor = p->SceneColor; t.pitch = p->SceneColorPitch; t.selection = p->Selection; t.writer = p->Writer;
+        mStatus = vqhip_outline(mCtx, p->Stream, numDraws ? p->Draws->data() : nullptr, numDraws, (int)mWidth, (int)mHeight, &t, mWork.ptr, mWork.bytes);
+    }
+    const void* GetWorkBuffer() const { return mWork.ptr; }
+    size_t GetWorkBytes() const { return mWork.bytes; }
+private:
+    WorkBuffer mWork;
+    unsigned mWidth = 0, mHeight = 0;
+};
+
 } // namespace vqhip

@@ -293,6 +293,32 @@ SURFACE_VERTEX_BYTES = 44                    # the engine's vertex: position @0,
 SURFACE_JOB_BYTES = 80                       # one draw's entry of vqhip_scene_interpolants' table in its work buffer
 
 
+class ObjectIdDraw(C.Structure):  # vqhip_object_id_draw
+    _fields_ = [("numIndices", C.c_uint32), ("numInstances", C.c_uint32), ("objID", C.c_void_p), ("meshID", C.c_int32), ("materialID", C.c_int32)]
+
+
+OBJECT_ID_JOB_BYTES = 32                     # one draw's entry of vqhip_object_ids' table in its work buffer
+
+
+class OutlineData(C.Structure):  # VQ_OutlineData == the cbuffer OutlineData of Outline.hlsl / FOutlineRenderData::FConstantBuffer
+    _fields_ = [("matWorld", matrix), ("matWorldView", matrix), ("matNormalView", matrix), ("matProj", matrix), ("matViewInverse", matrix),
+                ("Color", float4), ("uvScaleBias", float4), ("Scale", C.c_float), ("HeightDisplacement", C.c_float), ("pad_", C.c_float * 2)]
+
+
+class OutlineDraw(C.Structure):  # vqhip_outline_draw
+    _fields_ = [("mesh", ShadowMesh), ("cb", C.c_void_p)]
+
+
+class OutlineTargets(C.Structure):  # vqhip_outline_targets
+    _fields_ = [("sceneColor", C.c_void_p), ("selection", C.c_void_p), ("writer", C.c_void_p), ("pitch", C.c_int32), ("selection_pitch", C.c_int32),
+                ("writer_pitch", C.c_int32), ("reserved", C.c_int32)]
+
+
+OUTLINE_DATA_BYTES = 368                     # sizeof(VQ_OutlineData)
+OUTLINE_RECORDS_PER_TRIANGLE = 16            # vqhip_outline's work buffer: eight mark and eight paint records per triangle, 8 + 48 bytes each
+NO_WRITER = 0xFFFFFFFF                       # vqhip_outline's writer value for "not written"
+
+
 def _chk(t, size, **offs):
     assert C.sizeof(t) == size, (t.__name__, C.sizeof(t), size)
     for k, v in offs.items():
@@ -328,6 +354,10 @@ _chk(SceneDepthMaskedDraw, 56, material=48)
 _chk(ShadowMaskedDraw, 64, texDiffuseAlpha=56)
 _chk(ShadowMaskedView, 56, pitchBytes=8, dim=16, linearDepth=20, cameraPosition=24, farPlane=36, draws=40, numDraws=48)
 _chk(ShadowView, 56, pitchBytes=8, dim=16, linearDepth=20, cameraPosition=24, farPlane=36, draws=40, numDraws=48)
+_chk(ObjectIdDraw, 24, numInstances=4, objID=8, meshID=16, materialID=20)
+_chk(OutlineData, 368, matWorldView=64, matNormalView=128, matProj=192, matViewInverse=256, Color=320, uvScaleBias=336, Scale=352, HeightDisplacement=356)
+_chk(OutlineDraw, 40, cb=32)
+_chk(OutlineTargets, 40, selection=8, writer=16, pitch=24, selection_pitch=28, writer_pitch=32, reserved=36)
 _chk(CacaoConstants, 384, EffectRadius=48, InvSharpness=96, PassIndex=100, PatternRotScaleMatrices=112, NormalsUnpackMul=192, SSAOBufferDimensions=208,
      DepthBufferOffset=240, PerPassFullResUVOffset=248, DeinterleavedDepthBufferNormalisedOffset=312, NormalsWorldToViewspaceMatrix=320)
 

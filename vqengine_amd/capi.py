@@ -127,6 +127,10 @@ def load_library():
                                                              C.POINTER(abi.PerFrameData), C.POINTER(abi.PerViewLightingData), vp, i32,
                                                              C.POINTER(abi.EnvMap), C.POINTER(abi.ShadowMaps), vp, i32, i32, C.POINTER(abi.PsmainTargets), vp, i32]),
         "vqhip_scene_normals_from_materials_quad": (i32, [vp, vp, C.POINTER(abi.Interpolants), C.POINTER(abi.MaterialDesc), i32, vp, i32, i32, vp, i32]),
+        "vqhip_object_ids_work_bytes": (sz, [i32]),
+        "vqhip_object_ids": (i32, [vp, vp, C.POINTER(abi.ObjectIdDraw), i32, i32, i32, vp, i32, vp, i32, vp, sz]),
+        "vqhip_outline_work_bytes": (sz, [C.c_uint64]),
+        "vqhip_outline": (i32, [vp, vp, C.POINTER(abi.OutlineDraw), i32, i32, i32, C.POINTER(abi.OutlineTargets), vp, sz]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -166,6 +170,7 @@ EXPORTED_SYMBOLS = [
     "vqhip_scene_interpolants", "vqhip_scene_interpolants_work_bytes",
     "vqhip_scene_masked_depth", "vqhip_scene_masked_depth_work_bytes", "vqhip_shadow_masked_depth", "vqhip_shadow_masked_depth_work_bytes",
     "vqhip_scene_quad_interpolants", "vqhip_gbuffer_from_materials_quad", "vqhip_forward_lighting_from_materials_quad", "vqhip_scene_normals_from_materials_quad",
+    "vqhip_object_ids", "vqhip_object_ids_work_bytes", "vqhip_outline", "vqhip_outline_work_bytes",
 ]
 
 
@@ -226,6 +231,33 @@ class SurfaceDraw:
     def depth_draw(self, cull=abi.CULL_NONE):
         """the same draw for vqhip_scene_depth / vqhip_shadow_depth"""
         return ShadowDraw(self.vertices, self.indices, self.wvp, self.world, cull)
+
+
+def object_ids_work_bytes(num_draws):
+    """vqhip_object_ids_work_bytes: the work buffer (the draw table's device home) of a vqhip_object_ids call of `num_draws` draws. Host-only."""
+    return load_library().vqhip_object_ids_work_bytes(int(num_draws))
+
+
+class ObjectIdDraw:
+    """One vqhip_object_id_draw: what one draw of the depth call that wrote the owner plane drew (num_indices, and the instance count = obj_id.shape[0]), and what
+    ObjectID.hlsl writes for it. obj_id: cuda int32 [n, 4] contiguous (PerObjectLightingData.ObjID; columns 0 and 3 are read); mesh_id, material_id: ints."""
+
+    def __init__(self, num_indices, obj_id, mesh_id, material_id):
+        self.num_indices, self.obj_id, self.mesh_id, self.material_id = int(num_indices), obj_id, int(mesh_id), int(material_id)
+
+
+def outline_work_bytes(triangles):
+    """vqhip_outline_work_bytes: the work buffer of a vqhip_outline call that draws `triangles` triangles in all (0: too many). Host-only."""
+    return load_library().vqhip_outline_work_bytes(int(triangles))
+
+
+class OutlineDraw:
+    """One vqhip_outline_draw: one selected (mesh, material) pair. vertices: cuda float32 [V, k] with k >= 6 and unit column stride (position 3, normal 3; the row
+    stride is the vertex stride); indices: cuda 1-D int16 / uint16 (read as 16-bit unsigned) or int32, a triangle list; cb: cuda uint8 [368] contiguous or float32
+    [92], one VQ_OutlineData (outline_scene.outline_data builds it)."""
+
+    def __init__(self, vertices, indices, cb):
+        self.vertices, self.indices, self.cb = vertices, indices, cb
 
 
 def scene_depth_work_bytes(instanced_triangles):
@@ -946,6 +978,105 @@ class Context:
 
         def call(stream=None, _keep=keep):
             self._ck(fn(self._h, self._stream(stream), cdraws, len(draws), w, h, _ptr(owner), owner.stride(0), C.byref(arg), _ptr(work), work.numel()))
+        return call, res
+
+    def object_ids(self, draws, width, height, owner, out=None, work=None, stream=None):
+        """vqhip_object_ids: the ObjectID pass's target of the ObjectIdDraw list `draws` (the draw list of the cull-NONE scene_depth call that wrote `owner`, in the
+        same order) under the owner plane `owner`: cuda int32 [H, W] with unit column stride — scene_depth's `primitive` at 1 sample. out: a preallocated cuda
+        int32 [H, W, 4] with dense pixels (its row stride is the pitch), else allocated dense. Returns a dict: ids, work."""
+        call, res = self.object_ids_prepared(draws, width, height, owner, out, work)
+        call(stream)
+        return res
+
+    def object_ids_prepared(self, draws, width, height, owner, out=None, work=None):
+        """The descriptors of an object_ids call built once: returns (call, result) with call(stream=None) issuing vqhip_object_ids on the same draws, owner plane
+        and target again. The tensors must stay alive and in place."""
+        who_ = "object_ids"
+        draws = list(draws)
+        w, h = int(width), int(height)
+        if not (1 <= w <= abi.SCENE_DEPTH_MAX_DIM and 1 <= h <= abi.SCENE_DEPTH_MAX_DIM):
+            raise ValueError(f"{who_}: width and height must be 1..{abi.SCENE_DEPTH_MAX_DIM}")
+        if not (owner.is_cuda and owner.dtype == torch.int32 and tuple(owner.shape) == (h, w) and owner.stride(1) == 1 and owner.stride(0) >= w):
+            raise ValueError(f"{who_}: owner: expected cuda int32 {(h, w)} with unit column stride, got {tuple(owner.shape)} {owner.dtype} strides {owner.stride()}")
+        ids = out if out is not None else torch.empty((h, w, 4), dtype=torch.int32, device=self.device)
+        if not (ids.is_cuda and ids.dtype == torch.int32 and tuple(ids.shape) == (h, w, 4) and ids.stride(2) == 1 and ids.stride(1) == 4 and ids.stride(0) % 4 == 0
+                and ids.stride(0) >= 4 * w):
+            raise ValueError(f"{who_}: out: expected cuda int32 {(h, w, 4)} with dense pixels, got {tuple(ids.shape)} {ids.dtype} strides {ids.stride()}")
+        cdraws = (abi.ObjectIdDraw * max(1, len(draws)))()
+        for j, dr in enumerate(draws):
+            who = f"{who_}: draw {j}"
+            o = dr.obj_id
+            if not (o.is_cuda and o.dtype == torch.int32 and o.dim() == 2 and o.shape[1] == 4 and o.is_contiguous()):
+                raise ValueError(f"{who}: obj_id: expected cuda int32 [n, 4] contiguous")
+            _check_instances_cull(who, o.shape[0], abi.SCENE_DEPTH_MAX_INSTANCES)
+            if dr.num_indices < 0 or dr.num_indices % 3:
+                raise ValueError(f"{who}: num_indices: expected a multiple of 3")
+            c = cdraws[j]
+            c.numIndices, c.numInstances, c.objID, c.meshID, c.materialID = dr.num_indices, o.shape[0], o.data_ptr(), dr.mesh_id, dr.material_id
+        work = _work_tensor(who_, work, object_ids_work_bytes(len(draws)), self.device)
+        res = {"ids": ids, "work": work}
+        keep = (draws, res, owner)
+
+        def call(stream=None, _keep=keep):
+            self._ck(self.lib.vqhip_object_ids(self._h, self._stream(stream), cdraws, len(draws), w, h, _ptr(owner), owner.stride(0), _ptr(ids), ids.stride(0) // 4,
+                                               _ptr(work), work.numel()))
+        return call, res
+
+    def outline(self, draws, width, height, scene_color, selection=True, writer=True, out=None, work=None, stream=None):
+        """vqhip_outline: both passes of the Outline pass over the OutlineDraw list `draws`, writing the outline's colour IN PLACE into `scene_color`: cuda
+        float16 [H, W, 4] with dense pixels (its row stride is the pitch). selection / writer: also return the stencil mark (uint8 [H, W]) and the index of the
+        draw whose colour each pixel received (int32 [H, W]; the bits are uint32, -1 = not written). out: a dict of preallocated `selection` / `writer` tensors
+        (their row strides are the pitches). Returns a dict: scene_color, selection, writer (where asked for), work."""
+        call, res = self.outline_prepared(draws, width, height, scene_color, selection, writer, out, work)
+        call(stream)
+        return res
+
+    def outline_prepared(self, draws, width, height, scene_color, selection=True, writer=True, out=None, work=None):
+        """The descriptors of an outline call built once: returns (call, result) with call(stream=None) issuing vqhip_outline on the same draws and targets again.
+        The tensors must stay alive and in place."""
+        who_ = "outline"
+        draws, out = list(draws), dict(out or {})
+        w, h = int(width), int(height)
+        if not (1 <= w <= abi.SCENE_DEPTH_MAX_DIM and 1 <= h <= abi.SCENE_DEPTH_MAX_DIM):
+            raise ValueError(f"{who_}: width and height must be 1..{abi.SCENE_DEPTH_MAX_DIM}")
+        sc = scene_color
+        if not (sc.is_cuda and sc.dtype == torch.float16 and tuple(sc.shape) == (h, w, 4) and sc.stride(2) == 1 and sc.stride(1) == 4 and sc.stride(0) % 4 == 0
+                and sc.stride(0) >= 4 * w):
+            raise ValueError(f"{who_}: scene_color: expected cuda float16 {(h, w, 4)} with dense pixels, got {tuple(sc.shape)} {sc.dtype} strides {sc.stride()}")
+        res = {"scene_color": sc}
+        for key, want, dtype in (("selection", selection, torch.uint8), ("writer", writer, torch.int32)):
+            if not want:
+                continue
+            t = out.get(key)
+            if t is None:
+                t = torch.empty((h, w), dtype=dtype, device=self.device)
+            if not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == (h, w) and t.stride(1) == 1 and t.stride(0) >= w):
+                raise ValueError(f"{who_}: {key}: expected cuda {dtype} {(h, w)} with unit column stride, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+            res[key] = t
+        cdraws = (abi.OutlineDraw * max(1, len(draws)))()
+        tris = 0
+        for j, dr in enumerate(draws):
+            who = f"{who_}: draw {j}"
+            p, ix, cb = dr.vertices, dr.indices, dr.cb
+            _check_vertices(who, "vertices", p, 6)
+            bits = _check_indices(who, ix)
+            if not (cb.is_cuda and cb.is_contiguous() and cb.numel() * cb.element_size() == abi.OUTLINE_DATA_BYTES):
+                raise ValueError(f"{who}: cb: expected a contiguous cuda tensor of {abi.OUTLINE_DATA_BYTES} bytes (one VQ_OutlineData)")
+            c = cdraws[j]
+            _fill_mesh(c, p, ix, bits, empty_indices=p.data_ptr())
+            c.cb = cb.data_ptr()
+            tris += ix.numel() // 3
+        res["work"] = work = _work_tensor(who_, work, outline_work_bytes(tris), self.device, " (0: too many triangles)")
+        tg = abi.OutlineTargets()
+        tg.sceneColor, tg.pitch = sc.data_ptr(), sc.stride(0) // 4
+        if selection:
+            tg.selection, tg.selection_pitch = res["selection"].data_ptr(), res["selection"].stride(0)
+        if writer:
+            tg.writer, tg.writer_pitch = res["writer"].data_ptr(), res["writer"].stride(0)
+        keep = (draws, res)
+
+        def call(stream=None, _keep=keep):
+            self._ck(self.lib.vqhip_outline(self._h, self._stream(stream), cdraws, len(draws), w, h, C.byref(tg), _ptr(work), work.numel()))
         return call, res
 
     def msaa_resolve_surfaces(self, depth_ms, coverage=None, normals=None, normals_fmt=abi.FMT_R10G10B10A2_UNORM, roughness=None, background=None,

@@ -2379,5 +2379,169 @@ int vqhip_scene_quad_interpolants(vqhip_ctx* ctx, void* stream, const vqhip_scen
     return sceneInterpolants(ctx, "scene_quad_interpolants", stream, draws, numDraws, width, height, owner, owner_pitch_px, &out->planes, out, work, workBytes);
 }
 
+// ---- The ObjectID pass's target from an owner plane (raster_ids.hip; docs/DESIGN_DETAILS.md §7.21 P0) ---------------------------------------------------------------
+size_t vqhip_object_ids_work_bytes(int numDraws) {
+    if (numDraws < 0) return 0;
+    return align256((size_t)(numDraws > 0 ? numDraws : 1) * sizeof(ObjectIdJob));
+}
+
+int vqhip_object_ids(vqhip_ctx* ctx, void* stream, const vqhip_object_id_draw* draws, int numDraws, int width, int height,
+                     const uint32_t* owner, int owner_pitch_px, int32_t* ids, int ids_pitch_px, void* work, size_t workBytes) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "object_ids: ctx is NULL");
+    CTX_GUARD(ctx, "object_ids");
+    vqk::Range range_("RenderObjectIDPass");
+    const std::string w = "object_ids";
+    auto bad = [&](const std::string& m) { return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": " + m); };
+    if (!owner || !ids || !work) return bad("NULL argument (owner, ids or work)");
+    if (numDraws < 0 || (numDraws > 0 && !draws)) return bad("numDraws < 0, or draws is NULL");
+    if (width < 1 || width > VQHIP_SCENE_DEPTH_MAX_DIM || height < 1 || height > VQHIP_SCENE_DEPTH_MAX_DIM) return bad("width and height must be 1..8192");
+    if (owner_pitch_px < 0 || ids_pitch_px < 0) return bad("negative pitch");
+    const size_t ownerPitch = owner_pitch_px ? (size_t)owner_pitch_px : (size_t)width, idsPitch = ids_pitch_px ? (size_t)ids_pitch_px : (size_t)width;
+    if (ownerPitch < (size_t)width || idsPitch < (size_t)width) return bad("a pitch below width");
+    if ((uintptr_t)ids % 16) return bad("ids is not 16-byte aligned");
+    if ((uintptr_t)owner % 4) return bad("owner must be 4-byte aligned");
+    if ((uintptr_t)work % 256) return bad("work must be 256-byte aligned");
+    uint64_t totalTris = 0;
+    size_t numJobs = 0;
+    for (int d = 0; d < numDraws; ++d) {
+        const vqhip_object_id_draw& D = draws[d];
+        auto badDraw = [&](const std::string& m) { return bad("draw " + std::to_string(d) + ": " + m); };
+        if (!D.objID) return badDraw("objID is NULL");
+        if ((uintptr_t)D.objID % 4) return badDraw("objID must be 4-byte aligned");
+        if (D.numIndices % 3) return badDraw("numIndices is not a multiple of 3");
+        if (D.numInstances < 1 || D.numInstances > VQHIP_SCENE_DEPTH_MAX_INSTANCES) return badDraw("numInstances must be 1..64");
+        if (D.numIndices) { totalTris += (uint64_t)(D.numIndices / 3) * D.numInstances; ++numJobs; }
+    }
+    if (totalTris >= kSceneMaxTriangles) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": 2^29 or more instanced triangles in one call");
+    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": more than 20000 draws in one call");
+    const size_t need = vqhip_object_ids_work_bytes(numDraws);
+    if (workBytes < need) return bad("workBytes below vqhip_object_ids_work_bytes(numDraws)");
+    const size_t rows = (size_t)(height - 1);
+    const size_t ownerBytes = (rows * ownerPitch + width) * 4, idsBytes = (rows * idsPitch + width) * 16;
+    if (rangesOverlap(work, need, ids, idsBytes)) return bad("ids overlaps the work buffer");
+    if (rangesOverlap(owner, ownerBytes, ids, idsBytes)) return bad("ids overlaps the owner plane");
+
+    ObjectIdArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.owner = owner; a.ids = ids; a.ownerPitch = (uint32_t)ownerPitch; a.idsPitch = (uint32_t)idsPitch;
+    a.width = width; a.height = height; a.numJobs = (int32_t)numJobs; a.totalTris = (uint32_t)totalTris;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    ObjectIdJob* table = (ObjectIdJob*)work;
+    // the draws that have indices, in ring slots of ObjectIdJobs: one table-copy launch per slot
+    int d = 0;
+    uint64_t firstQ = 0;
+    auto fill = [&](ObjectIdJob& J, size_t) {
+        while (!draws[d].numIndices) ++d;
+        const vqhip_object_id_draw& D = draws[d++];
+        std::memset(&J, 0, sizeof(J));
+        J.objID = D.objID; J.numTris = D.numIndices / 3; J.numInstances = D.numInstances; J.meshID = D.meshID; J.materialID = D.materialID;
+        J.firstQ = (uint32_t)firstQ;
+        firstQ += (uint64_t)J.numTris * J.numInstances;
+    };
+    if (int rc = stageJobs<ObjectIdJob>(ctx, st, numJobs, fill, [&](const ObjectIdJob* src, size_t n, size_t first) { return copySlotToTable(ctx, st, src, n, table + first, w); })) return rc;
+    // default: the wave form from 2^22 pixels on, the lane form below (profiles/r22a_editor_passes.md: 41.7 against 45.1 us at 3840 x 2160, 28.1 against 21.0 us at 1920 x 1080)
+    const bool waveForm = ctx->opt.interpForm ? ctx->opt.interpForm != 1 : (uint64_t)width * (uint64_t)height >= ((uint64_t)1 << 22);
+    hipError_t e = launch_object_ids(st, a, table, waveForm);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (w + " launch").c_str());
+}
+
+// ---- The Outline pass (raster_outline.hip; docs/DESIGN_DETAILS.md §7.21 O1 .. O6) ----------------------------------------------------------------------------------
+static_assert(slotsFor<OutlineJob>(kRasterMaxDraws) < vqhip_ctx::kSlots, "one call never laps the ring");
+static constexpr uint64_t kOutlineMaxTriangles = (uint64_t)1 << 28;   // sixteen records each: the record counter is 32 bits wide
+// counter | OutlineColor[min(triangles, max draws), at least 1] | boxes[16 n] | records[16 n]; false above the limit or when the sizes do not fit
+static bool outlineLayout(uint64_t triangles, size_t* colors, size_t* colorCap, size_t* boxes, size_t* records, size_t* total) {
+    if (triangles >= kOutlineMaxTriangles) return false;
+    const uint64_t cap = triangles * kOutlineFanMax, nc = triangles < kRasterMaxDraws ? (triangles ? triangles : 1) : kRasterMaxDraws;
+    const uint64_t c = kOutlineCounterBytes, b = align256(c + nc * sizeof(OutlineColor)), r = align256(b + cap * kOutlineBoxBytes), t = align256(r + cap * kOutlineRecordBytes);
+    if (t > (uint64_t)SIZE_MAX) return false;
+    *colors = (size_t)c; *colorCap = (size_t)nc; *boxes = (size_t)b; *records = (size_t)r; *total = (size_t)t;
+    return true;
+}
+
+size_t vqhip_outline_work_bytes(uint64_t triangles) {
+    size_t c, nc, b, r, t;
+    return outlineLayout(triangles, &c, &nc, &b, &r, &t) ? t : 0;
+}
+
+int vqhip_outline(vqhip_ctx* ctx, void* stream, const vqhip_outline_draw* draws, int numDraws, int width, int height,
+                  const vqhip_outline_targets* out, void* work, size_t workBytes) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "outline: ctx is NULL");
+    CTX_GUARD(ctx, "outline");
+    vqk::Range range_("RenderOutline");
+    const std::string w = "outline";
+    auto bad = [&](const std::string& m) { return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": " + m); };
+    if (!out || !out->sceneColor || !work) return bad("NULL argument (out, out->sceneColor or work)");
+    if (numDraws < 0 || (numDraws > 0 && !draws)) return bad("numDraws < 0, or draws is NULL");
+    if (width < 1 || width > VQHIP_SCENE_DEPTH_MAX_DIM || height < 1 || height > VQHIP_SCENE_DEPTH_MAX_DIM) return bad("width and height must be 1..8192");
+    if (out->reserved != 0) return bad("reserved must be 0");
+    if (out->pitch < 0 || out->selection_pitch < 0 || out->writer_pitch < 0) return bad("negative pitch");
+    const size_t pitch = out->pitch ? (size_t)out->pitch : (size_t)width, selPitch = out->selection_pitch ? (size_t)out->selection_pitch : (size_t)width;
+    const size_t wrPitch = out->writer_pitch ? (size_t)out->writer_pitch : (size_t)width;
+    if (pitch < (size_t)width || selPitch < (size_t)width || wrPitch < (size_t)width) return bad("a pitch below width");
+    if ((uintptr_t)out->sceneColor % 8) return bad("sceneColor is not 8-byte aligned");
+    if ((uintptr_t)out->writer % 4) return bad("writer must be 4-byte aligned");
+    if ((uintptr_t)work % 256) return bad("work must be 256-byte aligned");
+    uint64_t totalTris = 0;
+    size_t numJobs = 0;
+    for (int d = 0; d < numDraws; ++d) {
+        const vqhip_outline_draw& D = draws[d];
+        auto badDraw = [&](const std::string& m) { return bad("draw " + std::to_string(d) + ": " + m); };
+        if (!D.mesh.positions || !D.mesh.indices || !D.cb) return badDraw("positions, indices or cb is NULL");
+        if (const std::string m = badMeshDraw(D.mesh, 1, 24, 1); !m.empty()) return badDraw(m);
+        if ((uintptr_t)D.mesh.positions % 4 || (uintptr_t)D.cb % 4 || (uintptr_t)D.mesh.indices % (D.mesh.indexBits / 8))
+            return badDraw("positions / cb must be 4-byte aligned, indices aligned to their size");
+        if (D.mesh.numIndices) { totalTris += D.mesh.numIndices / 3; ++numJobs; }
+    }
+    if (totalTris >= kOutlineMaxTriangles) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": 2^28 or more triangles in one call");
+    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": more than 20000 draws in one call");
+    size_t offColors, colorCap, offBoxes, offRecords, need;
+    if (!outlineLayout(totalTris, &offColors, &colorCap, &offBoxes, &offRecords, &need) || workBytes < need)
+        return bad("workBytes below vqhip_outline_work_bytes(the call's triangles)");
+    const size_t rows = (size_t)(height - 1);
+    const void* const planes[3] = { out->sceneColor, out->selection, out->writer };
+    const size_t bytes[3] = { (rows * pitch + width) * 8, rows * selPitch + width, (rows * wrPitch + width) * 4 };
+    for (int k = 0; k < 3; ++k) {
+        if (!planes[k]) continue;
+        if (rangesOverlap(work, need, planes[k], bytes[k])) return bad("an output overlaps the work buffer");
+        for (int m = 0; m < k; ++m) if (planes[m] && rangesOverlap(planes[m], bytes[m], planes[k], bytes[k])) return bad("an output overlaps another output");
+    }
+
+    OutlineArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.sceneColor = out->sceneColor; a.selection = out->selection; a.writer = out->writer;
+    a.colors = (OutlineColor*)((char*)work + offColors); a.colorCap = (uint32_t)colorCap;
+    a.recCap = totalTris * kOutlineFanMax; a.pitch = (uint32_t)pitch; a.selectionPitch = (uint32_t)selPitch; a.writerPitch = (uint32_t)wrPitch;
+    a.width = width; a.height = height;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* counter = (uint32_t*)work;
+    void* boxes = (char*)work + offBoxes;
+    void* records = (char*)work + offRecords;
+    hipError_t e = launch_raster_begin(st, counter, 1);
+    if (e != hipSuccess) return failHip(ctx, e, (w + " counter launch").c_str());
+    // the draws that have indices, in ring slots of OutlineJobs: one setup launch per slot
+    int d = 0;
+    uint64_t blocks = 0;
+    auto fill = [&](OutlineJob& J, size_t k) {
+        if (!k) blocks = 0;
+        while (!draws[d].mesh.numIndices) ++d;
+        const vqhip_outline_draw& D = draws[d];
+        std::memset(&J, 0, sizeof(J));
+        J.positions = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices; J.cb = D.cb;
+        J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numTris = D.mesh.numIndices / 3; J.indexBits = D.mesh.indexBits;
+        J.firstBlock = (uint32_t)blocks; J.drawIndex = (uint32_t)d;
+        blocks += ((uint64_t)J.numTris + 255) / 256;
+        ++d;
+    };
+    auto setup = [&](const OutlineJob* jobs, size_t n, size_t first) {
+        hipError_t le = launch_outline_setup(st, jobs, (int)n, (uint32_t)first, (uint32_t)blocks, a, counter, boxes, records);
+        return le == hipSuccess ? VQHIP_OK : failHip(ctx, le, (w + " setup launch").c_str());
+    };
+    if (int rc = stageJobs<OutlineJob>(ctx, st, numJobs, fill, setup)) return rc;
+    e = launch_outline_fill(st, a, ctx->opt.rasterTile == 64 ? 64 : 32, counter, boxes, records);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (w + " fill launch").c_str());
+}
+
 } // extern "C"
 

@@ -351,6 +351,48 @@ hipError_t launch_table_copy(hipStream_t s, const void* src, void* dst, uint32_t
 hipError_t launch_scene_interpolants(hipStream_t s, const SceneInterpArgs& a, const SurfaceJob* table, bool waveForm);   // waveForm: waves with one owner fetch it once
 hipError_t launch_scene_quad_interpolants(hipStream_t s, const SceneInterpArgs& a, const SurfaceJob* table, bool waveForm, const QuadPlane& quad);
 
+// The ObjectID pass's render target from an owner plane (vqhip_object_ids, raster_ids.hip; docs/DESIGN_DETAILS.md §7.21 P0). The draw table travels as
+// vqhip_scene_interpolants' does: ring slots -> k_table_copy -> the work buffer. Work buffer: ObjectIdJob[number of draws with numIndices > 0], nothing else.
+struct alignas(16) ObjectIdJob {     // one vqhip_object_id_draw
+    const int32_t* objID;
+    uint32_t numTris, numInstances;
+    int32_t meshID, materialID;
+    uint32_t firstQ;                 // sequence number of (instance 0, triangle 0): the instanced triangles of the draws before
+    uint32_t pad;
+};
+static_assert(sizeof(ObjectIdJob) == 32, "ObjectIdJob is two uint4");
+struct ObjectIdArgs {
+    const uint32_t* owner; int32_t* ids;
+    uint32_t ownerPitch, idsPitch;                        // pixels per row
+    int32_t width, height, numJobs;
+    uint32_t totalTris;                                   // q at or beyond it owns nothing
+};
+hipError_t launch_object_ids(hipStream_t s, const ObjectIdArgs& a, const ObjectIdJob* table, bool waveForm);   // waveForm: waves with one owner fetch its draw once
+
+// The Outline pass (vqhip_outline, raster_outline.hip; docs/DESIGN_DETAILS.md §7.21 O1 .. O6). The draw jobs travel in constant-ring slots.
+// Work buffer: one record counter (256 B) | OutlineColor[min(triangles, 20 000)] (one per draw with indices: the four colour halfs and the draw's index, written by
+// the setup kernel) | the records' pixel boxes (8 B each) | the records (48 B each: three snapped vertices, three z/w, 0 for a mark record or 1 + the job's number
+// for a paint record); recCap = 16 x the call's triangles (each pass: a triangle clipped by seven planes is a fan of at most eight).
+struct alignas(16) OutlineJob {      // one vqhip_outline_draw
+    const uint8_t* positions; const void* indices; const VQ_OutlineData* cb;
+    uint32_t strideBytes, numVertices, numTris;
+    int32_t indexBits;
+    uint32_t firstBlock;             // of this k_outline_setup launch: ceil(numTris / 256) blocks per job
+    uint32_t drawIndex;              // into the caller's draws
+};
+static_assert(sizeof(OutlineJob) == 48, "OutlineJob is three uint4");
+struct alignas(16) OutlineColor { uint32_t rg, ba, drawIndex, pad; };
+struct OutlineArgs {
+    void* sceneColor; uint8_t* selection; uint32_t* writer;
+    OutlineColor* colors;
+    uint64_t recCap;
+    uint32_t pitch, selectionPitch, writerPitch, colorCap;
+    int32_t width, height;
+};
+static constexpr size_t kOutlineBoxBytes = 8, kOutlineRecordBytes = 48, kOutlineCounterBytes = 256, kOutlineFanMax = 16;
+hipError_t launch_outline_setup(hipStream_t s, const OutlineJob* jobs, int numJobs, uint32_t firstJob, uint32_t blocks, const OutlineArgs& a, uint32_t* counter, void* boxes, void* records);
+hipError_t launch_outline_fill(hipStream_t s, const OutlineArgs& a, int tile, const uint32_t* counter, const void* boxes, const void* records);
+
 // launchers (each returns the hipError_t of the launch)
 hipError_t launch_forward_lighting(hipStream_t s, const ShadeArgs& a, bool hasEnv, bool hasCasters, int outFmt, const Options& opt);
 hipError_t launch_blur_x(hipStream_t s, const void* in, void* out, int W, int H, int fmt, const Options& opt);
