@@ -1,12 +1,14 @@
 #!/usr/bin/env python
-"""Writes what tests/test_gpu_ssr_cacao_front_ends.py compares with: every refusal text of the SSR and CACAO entry points and of their bindings, as the library and
-the bindings word them NOW. It is meant to be run on the state BEFORE a change of that host code, on the GPU:
+"""Writes what a front-end test module compares with (tests/test_gpu_ssr_cacao_front_ends.py, the default, or with --module tests.test_gpu_lit_front_ends the
+lit draw's): every refusal text of its entry points and of their bindings, as the library and the bindings word them NOW. It is meant to be run on the state
+BEFORE a change of that host code, on the GPU:
 
-    VQHIP_LIBRARY_PATH=<libvqhip.so built from the commit before> python scripts/record_ssr_cacao_refusals.py --capi <capi.py of that commit> [--out FILE]
+    VQHIP_LIBRARY_PATH=<libvqhip.so built from the commit before> python scripts/record_ssr_cacao_refusals.py [--module MODULE] --capi <capi.py of that commit> [--out FILE]
 
---capi loads that file as the bindings whose ValueErrors are recorded (it sits beside the package's abi module); without it the package's own capi.py is used.
-The default --out is tests/golden/ssr_cacao_refusals.json."""
+The module supplies make_small(), LISTENED, listen(), wrong_twice(), python_refusals() and GOLDEN, the default --out. --capi loads that file as the bindings whose
+ValueErrors are recorded (it sits beside the package's abi module); without it the package's own capi.py is used."""
 import argparse
+import importlib
 import importlib.util
 import json
 import os
@@ -18,10 +20,11 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--module", default="tests.test_gpu_ssr_cacao_front_ends", help="the front-end test module to record for")
     ap.add_argument("--capi", help="a capi.py to take the bindings' refusals from")
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "ssr_cacao_refusals.json"))
+    ap.add_argument("--out", help="default: the module's GOLDEN")
     args = ap.parse_args()
-    from tests import test_gpu_ssr_cacao_front_ends as T
+    T = importlib.import_module(args.module)
     from vqengine_amd import capi
     bindings = capi
     if args.capi:
@@ -29,15 +32,16 @@ def main():
         bindings = importlib.util.module_from_spec(spec)
         sys.modules[spec.name] = bindings
         spec.loader.exec_module(bindings)
+    out_path = args.out or T.GOLDEN
     ctx, old = capi.Context(0), bindings.Context(0)
     small = T.make_small()
     golden = {"library": {which: T.listen(ctx, small, which) for which in sorted(T.LISTENED)}, "wrong_twice": T.wrong_twice(ctx, small), "python": T.python_refusals(old, small)}
     old.close()
     ctx.close()
-    with open(args.out, "w") as f:
+    with open(out_path, "w") as f:
         json.dump(golden, f, indent=1, sort_keys=True)
         f.write("\n")
-    print(f"{args.out}: {sum(len(v) for v in golden['library'].values())} refusals of the six refusal tests, {len(golden['wrong_twice'])} calls wrong twice, "
+    print(f"{out_path}: {sum(len(v) for v in golden['library'].values())} refusals of the {len(T.LISTENED)} refusal tests, {len(golden['wrong_twice'])} calls wrong twice, "
           f"{len(golden['python'])} ValueErrors; library {capi.lib_path()}")
 
 

@@ -530,6 +530,42 @@ def _check_tiles(who, tile_list, counters, tiles):
     _check_list(who + "counters", counters, 2)
 
 
+def _byref(struct):                                 # this and the helpers below: what the lit-draw bindings build alike. An optional struct argument
+    return C.byref(struct) if struct is not None else None
+
+
+def _interpolants(ip):
+    """the vqhip_interpolants planes (float32 cuda [H,W,4]) -> (abi.Interpolants, H, W)"""
+    for i, t in enumerate(ip):
+        _check_img(t, FMT_RGBA32F, f"ip{i}")
+    h, w = ip[0].shape[0], ip[0].shape[1]
+    return abi.Interpolants(ip[0].data_ptr(), ip[1].data_ptr(), ip[2].data_ptr(), w, h, w), h, w
+
+
+def _gbuffer(planes, h, w):                         # four dense planes that the caller has checked
+    return abi.GBuffer(planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(), planes[3].data_ptr(), w, h, w)
+
+
+def _ssao(ssao):
+    if ssao is None:
+        return None
+    if not (ssao.is_cuda and ssao.is_contiguous() and ssao.dtype == torch.uint8 and ssao.dim() == 2):
+        raise ValueError("ssao: expected contiguous cuda uint8 [H,W]")
+    return abi.SSAO(ssao.data_ptr(), ssao.shape[1], ssao.shape[0])
+
+
+def _extra_point(extra_point):                      # the extension array of point lights -> (pointer, count)
+    n = len(extra_point) if extra_point is not None else 0
+    return (C.cast(extra_point, C.c_void_p) if n else C.c_void_p(None)), n
+
+
+def _out_image(out, h, w, fmt, device):             # `out`, or a new image when None: H x W pixels of `fmt`
+    if out is None:
+        out = empty_image(h, w, fmt, device)
+    _check_img(out, fmt, "out", (h, w))
+    return out
+
+
 def _halo_rows(halo_top, halo_bottom, fmt, width):
     """Both halos of a tile have the same row count (>= 10) and the tile's width and format."""
     rows = 0
@@ -610,17 +646,10 @@ class Context:
         h, w = g0.shape[0], g0.shape[1]
         for i, g in enumerate(gb):
             _check_img(g, FMT_RGBA32F, f"gb{i}", (h, w))             # all four planes share one shape
-        if out is None:
-            out = empty_image(h, w, out_fmt, self.device)
-        _check_img(out, out_fmt, "out", (h, w))
-        gbuf = abi.GBuffer(g0.data_ptr(), g1.data_ptr(), g2.data_ptr(), g3.data_ptr(), w, h, w)
-        n_extra = 0
-        extra_ptr = C.c_void_p(None)
-        if extra_point is not None and len(extra_point):
-            n_extra = len(extra_point)
-            extra_ptr = C.cast(extra_point, C.c_void_p)
-        args = (self._h, self._stream(stream), C.byref(gbuf), C.byref(per_frame), C.byref(per_view), extra_ptr, n_extra, C.byref(env) if env is not None else None,
-                C.byref(shadow) if shadow is not None else None, _ptr(out), out.shape[1], out_fmt)
+        out = _out_image(out, h, w, out_fmt, self.device)
+        gbuf = _gbuffer(gb, h, w)
+        args = (self._h, self._stream(stream), C.byref(gbuf), C.byref(per_frame), C.byref(per_view), *_extra_point(extra_point), _byref(env), _byref(shadow),
+                _ptr(out), out.shape[1], out_fmt)
         rc = self.lib.vqhip_forward_lighting(*args) if _targets is None else self.lib.vqhip_forward_lighting_mrt(*args, C.byref(_targets))
         self._ck(rc)
         return out
@@ -640,18 +669,13 @@ class Context:
                 _check_img(p, FMT_RGBA32F, f"layer {k} gb{i}", (h, w))
             if not (cov.is_cuda and cov.is_contiguous() and cov.dtype == torch.uint8 and tuple(cov.shape) == (h, w)):
                 raise ValueError(f"coverage {k}: expected contiguous cuda uint8 tensor of shape {(h, w)}, got {tuple(cov.shape)} {cov.dtype} {cov.device}")
-            g.layer[k] = abi.GBuffer(gb[0].data_ptr(), gb[1].data_ptr(), gb[2].data_ptr(), gb[3].data_ptr(), w, h, w)
+            g.layer[k] = _gbuffer(gb, h, w)
             g.coverage[k] = cov.data_ptr()
         if background is not None:
             _check_img(background, out_fmt, "background", (h, w))
-        if out is None:
-            out = empty_image(h, w, out_fmt, self.device)
-        _check_img(out, out_fmt, "out", (h, w))
-        n_extra = len(extra_point) if extra_point is not None else 0
-        extra_ptr = C.cast(extra_point, C.c_void_p) if n_extra else C.c_void_p(None)
-        self._ck(self.lib.vqhip_forward_lighting_msaa(self._h, self._stream(stream), C.byref(g), C.byref(per_frame), C.byref(per_view), extra_ptr, n_extra,
-                                                      C.byref(env) if env is not None else None, C.byref(shadow) if shadow is not None else None,
-                                                      _ptr(background), w, _ptr(out), w, out_fmt))
+        out = _out_image(out, h, w, out_fmt, self.device)
+        self._ck(self.lib.vqhip_forward_lighting_msaa(self._h, self._stream(stream), C.byref(g), C.byref(per_frame), C.byref(per_view), *_extra_point(extra_point),
+                                                      _byref(env), _byref(shadow), _ptr(background), w, _ptr(out), w, out_fmt))
         return out
 
     # ---- 4x MSAA surface resolve + depth hierarchy (ResolveMSAA_DepthPrePass / DownsampleDepth, SceneRendering.cpp:484-499) ------
@@ -1249,7 +1273,7 @@ class Context:
         if not (t is not None and t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (h, w, 4) and t.stride(2) == 1 and t.stride(1) == 4
                 and t.stride(0) % 4 == 0 and t.stride(0) >= 4 * w):
             raise ValueError(f"{who}: quad_uv: expected cuda float32 {(h, w, 4)} with dense pixels (the quad_uv plane of scene_quad_interpolants)")
-        return C.c_void_p(t.data_ptr()), t.stride(0) // 4
+        return _ptr(t), t.stride(0) // 4
 
     def gbuffer_from_materials_quad(self, ip, materials, ambient, quad_uv, ssao=None, out=None, stream=None):
         """vqhip_gbuffer_from_materials_quad (docs/DESIGN_DETAILS.md §7.20): gbuffer_from_materials with the uv derivatives taken from the helper lanes in
@@ -1272,22 +1296,14 @@ class Context:
     def gbuffer_from_materials(self, ip, materials, ambient, ssao=None, out=None, stream=None, _quad=None):
         """ip: 3 float32 cuda tensors [H,W,4] (vqhip_interpolants planes); materials: ctypes array of abi.MaterialDesc whose
         texture pointers are device pointers; ssao: uint8 cuda [H,W] or None. Returns the 4 G-buffer planes."""
-        for i, t in enumerate(ip):
-            _check_img(t, FMT_RGBA32F, f"ip{i}")
-        h, w = ip[0].shape[0], ip[0].shape[1]
+        inter, h, w = _interpolants(ip)
         if out is None:
             out = tuple(torch.empty((h, w, 4), dtype=torch.float32, device=self.device) for _ in range(4))
         for i, t in enumerate(out):
             _check_img(t, FMT_RGBA32F, f"gb{i}")
-        inter = abi.Interpolants(ip[0].data_ptr(), ip[1].data_ptr(), ip[2].data_ptr(), w, h, w)
-        gbuf = abi.GBuffer(out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), w, h, w)
-        s = None
-        if ssao is not None:
-            if not (ssao.is_cuda and ssao.is_contiguous() and ssao.dtype == torch.uint8 and ssao.dim() == 2):
-                raise ValueError("ssao: expected contiguous cuda uint8 [H,W]")
-            s = abi.SSAO(ssao.data_ptr(), ssao.shape[1], ssao.shape[0])
+        gbuf, s = _gbuffer(out, h, w), _ssao(ssao)
         n = len(materials) if materials is not None else 0
-        args = (self._h, self._stream(stream), C.byref(inter), materials if n else None, n, float(ambient), C.byref(s) if s is not None else None, C.byref(gbuf))
+        args = (self._h, self._stream(stream), C.byref(inter), materials if n else None, n, float(ambient), _byref(s), C.byref(gbuf))
         self._ck(self.lib.vqhip_gbuffer_from_materials(*args) if _quad is None
                  else self.lib.vqhip_gbuffer_from_materials_quad(*args, *self._quad_plane(_quad, h, w, "gbuffer_from_materials_quad")))
         return out
@@ -1295,13 +1311,10 @@ class Context:
     def scene_normals_from_materials(self, ip, materials, out_fmt=abi.FMT_R10G10B10A2_UNORM, out=None, stream=None, _quad=None):
         """The Z pre-pass's colour target (DepthPrePass.hlsl:PSMain): Tex_SceneNormals as int32 [H,W] (R10G10B10A2_UNORM bits; torch has no uint32) or
         float32 [H,W,4]. ip / materials as for gbuffer_from_materials (ip2 is not modified)."""
-        for i, t in enumerate(ip):
-            _check_img(t, FMT_RGBA32F, f"ip{i}")
-        h, w = ip[0].shape[0], ip[0].shape[1]
+        inter, h, w = _interpolants(ip)
         if out is None:
             out = (torch.empty((h, w), dtype=torch.int32, device=self.device) if out_fmt == abi.FMT_R10G10B10A2_UNORM
                    else empty_image(h, w, FMT_RGBA32F, self.device))
-        inter = abi.Interpolants(ip[0].data_ptr(), ip[1].data_ptr(), ip[2].data_ptr(), w, h, w)
         n = len(materials) if materials is not None else 0
         args = (self._h, self._stream(stream), C.byref(inter), materials if n else None, n, _ptr(out), out_fmt, w)
         self._ck(self.lib.vqhip_scene_normals_from_materials(*args) if _quad is None
@@ -1319,28 +1332,14 @@ class Context:
                                         env=None, shadow=None, stream=None, _targets=None, _quad=None):
         """PSMain in one kernel: gbuffer_from_materials(ip, materials, per_frame.fAmbientLightingFactor, ssao) + forward_lighting, the G-buffer
         record never leaving registers. Same bits as the two calls."""
-        for i, t in enumerate(ip):
-            _check_img(t, FMT_RGBA32F, f"ip{i}")
-        h, w = ip[0].shape[0], ip[0].shape[1]
-        if out is None:
-            out = empty_image(h, w, out_fmt, self.device)
-        _check_img(out, out_fmt, "out", (h, w))
-        inter = abi.Interpolants(ip[0].data_ptr(), ip[1].data_ptr(), ip[2].data_ptr(), w, h, w)
-        s = None
-        if ssao is not None:
-            if not (ssao.is_cuda and ssao.is_contiguous() and ssao.dtype == torch.uint8 and ssao.dim() == 2):
-                raise ValueError("ssao: expected contiguous cuda uint8 [H,W]")
-            s = abi.SSAO(ssao.data_ptr(), ssao.shape[1], ssao.shape[0])
+        inter, h, w = _interpolants(ip)
+        out = _out_image(out, h, w, out_fmt, self.device)
+        s = _ssao(ssao)
         n = len(materials) if materials is not None else 0
-        n_extra, extra_ptr = 0, C.c_void_p(None)
-        if extra_point is not None and len(extra_point):
-            n_extra, extra_ptr = len(extra_point), C.cast(extra_point, C.c_void_p)
-        args = (self._h, self._stream(stream), C.byref(inter), materials if n else None, n, C.byref(s) if s is not None else None,
-                C.byref(per_frame), C.byref(per_view), extra_ptr, n_extra, C.byref(env) if env is not None else None,
-                C.byref(shadow) if shadow is not None else None, _ptr(out), out.shape[1], out_fmt)
+        args = (self._h, self._stream(stream), C.byref(inter), materials if n else None, n, _byref(s), C.byref(per_frame), C.byref(per_view),
+                *_extra_point(extra_point), _byref(env), _byref(shadow), _ptr(out), out.shape[1], out_fmt)
         if _quad is not None:
-            self._ck(self.lib.vqhip_forward_lighting_from_materials_quad(*args, C.byref(_targets) if _targets is not None else None,
-                                                                         *self._quad_plane(_quad, h, w, "forward_lighting_from_materials_quad")))
+            self._ck(self.lib.vqhip_forward_lighting_from_materials_quad(*args, _byref(_targets), *self._quad_plane(_quad, h, w, "forward_lighting_from_materials_quad")))
             return out
         self._ck(self.lib.vqhip_forward_lighting_from_materials(*args) if _targets is None
                  else self.lib.vqhip_forward_lighting_from_materials_mrt(*args, C.byref(_targets)))

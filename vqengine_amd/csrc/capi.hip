@@ -112,6 +112,22 @@ int releaseSlot(vqhip_ctx* ctx, int slot, hipStream_t st) {
     ctx->slotBusy[slot] = true;
     return VQHIP_OK;
 }
+// One constant block of the lit draws into the next ring slot: acquire the slot, fill it (fillFrameConstants or fillGbufConstants with `args`), commit it in front
+// of `st`. *dev = where the kernels read the block; the caller releases *slot behind the kernel that reads it
+template <class Block, class Fill, class... Args>
+int stageConstants(vqhip_ctx* ctx, hipStream_t st, int* slot, const Block** dev, Fill fill, Args... args) {
+    if (const int rc = acquireSlot(ctx, slot)) return rc;
+    const size_t bytes = fill(ctx, *slot, args...);
+    *dev = (const Block*)(ctx->devRing + (size_t)*slot * kConstSlotBytes);
+    return commitSlot(ctx, *slot, bytes, st);
+}
+// the four planes of a vqhip_gbuffer as a kernel's arguments take them (to read or to write); false: one is NULL, and the caller words the refusal
+template <class Args>
+bool gbufferPlanes(const vqhip_gbuffer& g, Args* a) {
+    using P = decltype(a->gb0);
+    a->gb0 = (P)g.gb0; a->gb1 = (P)g.gb1; a->gb2 = (P)g.gb2; a->gb3 = (P)g.gb3;
+    return g.gb0 && g.gb1 && g.gb2 && g.gb3;
+}
 
 int ensureScratch(vqhip_ctx* ctx, size_t bytes) {
     if (ctx->scratchBytes >= bytes) return VQHIP_OK;
@@ -200,6 +216,23 @@ float rangeCullThreshold(float range) {
     while (t > 0.0f && sqrtf(t) >= range) t = nextafterf(t, 0.0f);           // now sqrtf(t) < range (or t == 0)
     while (sqrtf(t) < range) { if (t == FLT_MAX) return INFINITY; t = nextafterf(t, INFINITY); }
     return t;
+}
+
+// The bytes from a plane's first pixel to the end of its last row: `height` rows of `width` pixels of `bpp` bytes, `pitchPx` pixels apart. Every front end measures with this
+size_t planeExtent(int width, int height, size_t pitchPx, size_t bpp) { return ((size_t)(height - 1) * pitchPx + (size_t)width) * bpp; }
+bool rangesOverlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
+struct Span { const void* p; size_t n; const char* name; };                           // the bytes that a plane, a per-tile buffer or a list covers; p NULL: nothing
+// The overlap questions of the front ends: one span against a list (the quad-uv plane against a draw's outputs, an input against a pass's outputs), a list against itself
+bool overlapsAny(const Span& s, const Span* outs, int nOut) {
+    for (int i = 0; i < nOut; ++i) if (rangesOverlap(s.p, s.n, outs[i].p, outs[i].n)) return true;
+    return false;
+}
+bool overlapEachOther(const Span* outs, int nOut) {
+    for (int i = 0; i + 1 < nOut; ++i) if (overlapsAny(outs[i], outs + i + 1, nOut - i - 1)) return true;
+    return false;
 }
 
 } // namespace
@@ -428,6 +461,31 @@ static int fillMrt(vqhip_ctx* ctx, const char* who, const vqhip_psmain_targets* 
     return VQHIP_OK;
 }
 
+// vqhip_forward_lighting (targets == NULL) and its _mrt form
+static int forwardLighting(vqhip_ctx* ctx, void* stream, const vqhip_gbuffer* gb, const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
+        const VQ_PointLight* extraPoint, int numExtraPoint, const vqhip_envmap* env, const vqhip_shadowmaps* sm,
+        void* out, int out_row_pitch_px, vqhip_format outFmt, const vqhip_psmain_targets* targets) {
+    vqk::Range range_("RenderSceneColor");
+    ShadeArgs a;
+    if (!gb || !perFrame || !perView || !out) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting: NULL argument");
+    if (!gbufferPlanes(*gb, &a)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting: NULL G-buffer plane");
+    if (gb->width <= 0 || gb->height <= 0 || gb->row_pitch_px < gb->width || out_row_pitch_px < gb->width)
+        return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting: bad dimensions / pitch");
+    bool casters = false;
+    int rc = validateLighting(ctx, "forward_lighting", perFrame, perView, extraPoint, numExtraPoint, env, sm, outFmt, &casters);
+    if (rc) return rc;
+    if ((rc = fillMrt(ctx, "forward_lighting", targets, gb->width, &a.mrt)) != VQHIP_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    int slot;
+    if ((rc = stageConstants(ctx, st, &slot, &a.fc, fillFrameConstants, perFrame, perView, extraPoint, numExtraPoint, env, sm)) != VQHIP_OK) return rc;
+    a.out = out;
+    a.width = gb->width; a.height = gb->height; a.pitch = gb->row_pitch_px; a.outPitch = out_row_pitch_px;
+    a.arithDxc = ctx->arithDxc;
+    hipError_t e = launch_forward_lighting(st, a, env != nullptr, casters, outFmt, ctx->opt);
+    if (e != hipSuccess) return failHip(ctx, e, "forward_lighting launch");
+    return releaseSlot(ctx, slot, st);
+}
 int vqhip_forward_lighting(vqhip_ctx* ctx, void* stream, const vqhip_gbuffer* gb,
         const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
         const VQ_PointLight* extraPoint, int numExtraPoint,
@@ -435,44 +493,16 @@ int vqhip_forward_lighting(vqhip_ctx* ctx, void* stream, const vqhip_gbuffer* gb
         void* out, int out_row_pitch_px, vqhip_format outFmt) {
     if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "forward_lighting: ctx is NULL");
     CTX_GUARD(ctx, "forward_lighting");
-    return vqhip_forward_lighting_mrt(ctx, stream, gb, perFrame, perView, extraPoint, numExtraPoint, env, sm, out, out_row_pitch_px, outFmt, nullptr);
+    return forwardLighting(ctx, stream, gb, perFrame, perView, extraPoint, numExtraPoint, env, sm, out, out_row_pitch_px, outFmt, nullptr);
 }
-
 int vqhip_forward_lighting_mrt(vqhip_ctx* ctx, void* stream, const vqhip_gbuffer* gb,
         const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
         const VQ_PointLight* extraPoint, int numExtraPoint,
         const vqhip_envmap* env, const vqhip_shadowmaps* sm,
         void* out, int out_row_pitch_px, vqhip_format outFmt, const vqhip_psmain_targets* targets) {
-    vqk::Range range_("RenderSceneColor");
     if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "forward_lighting: ctx is NULL");
     CTX_GUARD(ctx, "forward_lighting");
-    if (!gb || !perFrame || !perView || !out) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting: NULL argument");
-    if (!gb->gb0 || !gb->gb1 || !gb->gb2 || !gb->gb3) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting: NULL G-buffer plane");
-    if (gb->width <= 0 || gb->height <= 0 || gb->row_pitch_px < gb->width || out_row_pitch_px < gb->width)
-        return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting: bad dimensions / pitch");
-    bool casters = false;
-    int rc = validateLighting(ctx, "forward_lighting", perFrame, perView, extraPoint, numExtraPoint, env, sm, outFmt, &casters);
-    if (rc) return rc;
-    MrtArgs mrt;
-    if ((rc = fillMrt(ctx, "forward_lighting", targets, gb->width, &mrt)) != VQHIP_OK) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    int slot;
-    rc = acquireSlot(ctx, &slot);
-    if (rc) return rc;
-    const size_t bytes = fillFrameConstants(ctx, slot, perFrame, perView, extraPoint, numExtraPoint, env, sm);
-    rc = commitSlot(ctx, slot, bytes, st);
-    if (rc) return rc;
-    ShadeArgs a;
-    a.mrt = mrt;
-    a.gb0 = (const float4*)gb->gb0; a.gb1 = (const float4*)gb->gb1; a.gb2 = (const float4*)gb->gb2; a.gb3 = (const float4*)gb->gb3;
-    a.out = out;
-    a.fc = (const FrameConstants*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
-    a.width = gb->width; a.height = gb->height; a.pitch = gb->row_pitch_px; a.outPitch = out_row_pitch_px;
-    a.arithDxc = ctx->arithDxc;
-    hipError_t e = launch_forward_lighting(st, a, env != nullptr, casters, outFmt, ctx->opt);
-    if (e != hipSuccess) return failHip(ctx, e, "forward_lighting launch");
-    return releaseSlot(ctx, slot, st);
+    return forwardLighting(ctx, stream, gb, perFrame, perView, extraPoint, numExtraPoint, env, sm, out, out_row_pitch_px, outFmt, targets);
 }
 
 int vqhip_forward_lighting_msaa(vqhip_ctx* ctx, void* stream, const vqhip_gbuffer_msaa* gb,
@@ -497,11 +527,10 @@ int vqhip_forward_lighting_msaa(vqhip_ctx* ctx, void* stream, const vqhip_gbuffe
     std::memset(&a, 0, sizeof(a));
     for (int k = 0; k < gb->layers; ++k) {
         const vqhip_gbuffer& g = gb->layer[k];
-        if (!g.gb0 || !g.gb1 || !g.gb2 || !g.gb3 || !gb->coverage[k])
+        if (!gbufferPlanes(g, &a.L[k]) || !gb->coverage[k])
             return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_msaa: NULL plane or coverage of layer " + std::to_string(k));
         if (g.width != W || g.height != H) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_msaa: layers of different sizes");
         if (g.row_pitch_px < W) return fail(ctx, VQHIP_ERR_INVALID_ARG, "forward_lighting_msaa: pitch below the width");
-        a.L[k].gb0 = (const float4*)g.gb0; a.L[k].gb1 = (const float4*)g.gb1; a.L[k].gb2 = (const float4*)g.gb2; a.L[k].gb3 = (const float4*)g.gb3;
         a.L[k].cov = gb->coverage[k]; a.L[k].pitch = g.row_pitch_px;
     }
     bool casters = false;
@@ -519,13 +548,8 @@ int vqhip_forward_lighting_msaa(vqhip_ctx* ctx, void* stream, const vqhip_gbuffe
     }
     if (!ctx->edgeFree) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->edgeFree, hipEventDisableTiming));
     int slot;
-    rc = acquireSlot(ctx, &slot);
-    if (rc) return rc;
-    const size_t bytes = fillFrameConstants(ctx, slot, perFrame, perView, extraPoint, numExtraPoint, env, sm);
-    rc = commitSlot(ctx, slot, bytes, st);
-    if (rc) return rc;
+    if ((rc = stageConstants(ctx, st, &slot, &a.fc, fillFrameConstants, perFrame, perView, extraPoint, numExtraPoint, env, sm)) != VQHIP_OK) return rc;
     a.bg = background; a.out = out;
-    a.fc = (const FrameConstants*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
     a.edgeCount = (uint32_t*)ctx->edge; a.edgeList = (uint32_t*)ctx->edge + 1;
     a.width = W; a.height = H; a.layers = gb->layers; a.covPitch = covPitch; a.bgPitch = background_pitch_px; a.outPitch = out_row_pitch_px;
     HIP_TRY(ctx, hipMemsetAsync(ctx->edge, 0, 4, st));
@@ -769,10 +793,6 @@ size_t vqhip_depth_hierarchy_bytes(int width, int height) {
 }
 
 namespace {
-bool rangesOverlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
 // the hierarchy kernels over `src` (a plane, or the four samples per pixel) on `st`; arguments are validated by the callers
 int enqueueDepthHierarchy(vqhip_ctx* ctx, hipStream_t st, const float* src, int srcPitch, int W, int H, float* mips, unsigned flags, bool ms) {
     HierArgs a;
@@ -919,12 +939,18 @@ static bool badTexture(const vqhip_texture2d& t) {
     return t.texels && (t.width <= 0 || t.height <= 0 || t.mips <= 0 || t.mips > vqhip_mip_level_count(t.width, t.height));
 }
 
+// The producers' kernels address a float4 plane with 32-bit byte offsets and pack pixel coordinates into 24 bits; `boundHeight`: the interpolant planes, whose
+// height no earlier check has bounded
+static int planeFitsOffsets(vqhip_ctx* ctx, const std::string& w, int pitch, int height, bool boundHeight = false) {
+    if ((uint64_t)pitch * height * 16u >= (1ull << 32) || pitch >= (1 << 24) || (boundHeight && height >= (1 << 24)))
+        return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": a plane must be smaller than 4 GiB (32-bit offsets in the kernel)");
+    return VQHIP_OK;
+}
 static int validateProducer(vqhip_ctx* ctx, const char* who, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials, const vqhip_ssao* ssao) {
     const std::string w(who);
     if (!in || !in->ip0 || !in->ip1 || !in->ip2) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": NULL plane");
     if (in->width <= 0 || in->height <= 0 || in->row_pitch_px < in->width) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": bad dimensions / pitch");
-    if ((uint64_t)in->row_pitch_px * in->height * 16u >= (1ull << 32) || in->row_pitch_px >= (1 << 24) || in->height >= (1 << 24))
-        return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": a plane must be smaller than 4 GiB (32-bit offsets in the kernel)");
+    if (const int rc = planeFitsOffsets(ctx, w, in->row_pitch_px, in->height, true)) return rc;
     if (numMaterials < 0 || numMaterials > kMaxMaterials || (numMaterials > 0 && !materials))
         return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": bad materials / numMaterials (see vqhip_max_materials)");
     for (int i = 0; i < numMaterials; ++i) {
@@ -947,54 +973,49 @@ static size_t fillGbufConstants(vqhip_ctx* ctx, int slot, const vqhip_material* 
     return offsetof(GbufConstants, mats) + (size_t)numMaterials * sizeof(vqhip_material);
 }
 
-// The quad-uv plane of the _quad producers (docs/DESIGN_DETAILS.md §7.20 Q2), validated after validateProducer: *bytes = the extent the kernel reads
-static int validateQuadPlane(vqhip_ctx* ctx, const std::string& w, const vqhip_interpolants* in, const void* quadUV, int quad_pitch_px, QuadPlane* qp, size_t* bytes) {
+// The quad-uv plane of the _quad producers (docs/DESIGN_DETAILS.md §7.20 Q2), validated after validateProducer. `outs`: every plane the call writes (p NULL: a target that
+// is not bound); the extent the kernel reads of quadUV must lie on none of them
+static int validateQuadPlane(vqhip_ctx* ctx, const std::string& w, const vqhip_interpolants* in, const void* quadUV, int quad_pitch_px, const Span* outs, int nOut, QuadPlane* qp) {
     if (!quadUV) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quadUV is NULL");
     if ((uintptr_t)quadUV % 16) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quadUV is not 16-byte aligned");
     if (quad_pitch_px < 0) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": negative quad_pitch_px");
     const int pitch = quad_pitch_px ? quad_pitch_px : in->row_pitch_px;
     if (pitch < in->width) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quad_pitch_px below the width");
-    if ((uint64_t)pitch * in->height * 16u >= (1ull << 32) || pitch >= (1 << 24))
-        return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": a plane must be smaller than 4 GiB (32-bit offsets in the kernel)");
+    if (const int rc = planeFitsOffsets(ctx, w, pitch, in->height)) return rc;
+    if (overlapsAny({ quadUV, planeExtent(in->width, in->height, pitch, 16), "" }, outs, nOut)) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quadUV overlaps an output");
     qp->uv = const_cast<void*>(quadUV); qp->pitch = (uint32_t)pitch;
-    *bytes = ((size_t)(in->height - 1) * pitch + in->width) * 16;
     return VQHIP_OK;
 }
-// the extent of an output plane of `px` bytes per pixel
-static size_t planeBytes(const vqhip_interpolants* in, int pitch, size_t px) { return ((size_t)(in->height - 1) * pitch + in->width) * px; }
+// a plane of the draw's frame that the call writes, `bpp` bytes per pixel, as an entry of that list
+static Span written(const vqhip_interpolants* in, const void* p, int pitch, size_t bpp) { return { p, planeExtent(in->width, in->height, pitch, bpp), "" }; }
+// the interpolant planes and the frame as the producers' kernels take them; a->gc comes from stageConstants, the four G-buffer planes from gbufferPlanes (or stay NULL)
+static void gbufArgs(GbufArgs* a, const vqhip_interpolants* in, int outPitch) {
+    a->ip0 = (const float4*)in->ip0; a->ip1 = (const float4*)in->ip1; a->ip2 = (const float4*)in->ip2;
+    a->width = in->width; a->height = in->height; a->pitch = in->row_pitch_px; a->outPitch = outPitch;
+}
 
 // vqhip_gbuffer_from_materials (quad == false) and its _quad form: one body, the launch differs
 static int gbufferFromMaterials(vqhip_ctx* ctx, const std::string& w, bool quad, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
                                 float fAmbientLightingFactor, const vqhip_ssao* ssao, const vqhip_gbuffer* out, const void* quadUV, int quad_pitch_px) {
     vqk::Range range_("Geometry");                       // :1723 (surface assembly half of the lit draws)
-    if (!out || !out->gb0 || !out->gb1 || !out->gb2 || !out->gb3) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": NULL plane");
+    GbufArgs a;
+    if (!out || !gbufferPlanes(*out, &a)) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": NULL plane");
     int rc = validateProducer(ctx, w.c_str(), in, materials, numMaterials, ssao);
     if (rc) return rc;
     if (out->width != in->width || out->height != in->height || out->row_pitch_px < in->width)
         return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": bad dimensions / pitch");
-    if ((uint64_t)out->row_pitch_px * out->height * 16u >= (1ull << 32) || out->row_pitch_px >= (1 << 24))
-        return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": a plane must be smaller than 4 GiB (32-bit offsets in the kernel)");
+    if ((rc = planeFitsOffsets(ctx, w, out->row_pitch_px, out->height)) != VQHIP_OK) return rc;
     QuadPlane qp = { nullptr, 0 };
     if (quad) {
-        size_t qb;
-        if ((rc = validateQuadPlane(ctx, w, in, quadUV, quad_pitch_px, &qp, &qb)) != VQHIP_OK) return rc;
-        const void* const outs[5] = { out->gb0, out->gb1, out->gb2, out->gb3, in->ip2 };     // ip2.w receives the discard's -1
-        for (int k = 0; k < 5; ++k)
-            if (rangesOverlap(quadUV, qb, outs[k], planeBytes(in, k < 4 ? out->row_pitch_px : in->row_pitch_px, 16))) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quadUV overlaps an output");
+        const Span outs[] = { written(in, out->gb0, out->row_pitch_px, 16), written(in, out->gb1, out->row_pitch_px, 16), written(in, out->gb2, out->row_pitch_px, 16),
+                              written(in, out->gb3, out->row_pitch_px, 16), written(in, in->ip2, in->row_pitch_px, 16) };     // ip2.w receives the discard's -1
+        if ((rc = validateQuadPlane(ctx, w, in, quadUV, quad_pitch_px, outs, 5, &qp)) != VQHIP_OK) return rc;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     int slot;
-    rc = acquireSlot(ctx, &slot);
-    if (rc) return rc;
-    const size_t bytes = fillGbufConstants(ctx, slot, materials, numMaterials, fAmbientLightingFactor, ssao);
-    rc = commitSlot(ctx, slot, bytes, st);
-    if (rc) return rc;
-    GbufArgs a;
-    a.ip0 = (const float4*)in->ip0; a.ip1 = (const float4*)in->ip1; a.ip2 = (const float4*)in->ip2;
-    a.gb0 = (float4*)out->gb0; a.gb1 = (float4*)out->gb1; a.gb2 = (float4*)out->gb2; a.gb3 = (float4*)out->gb3;
-    a.gc = (const GbufConstants*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
-    a.width = in->width; a.height = in->height; a.pitch = in->row_pitch_px; a.outPitch = out->row_pitch_px;
+    if ((rc = stageConstants(ctx, st, &slot, &a.gc, fillGbufConstants, materials, numMaterials, fAmbientLightingFactor, ssao)) != VQHIP_OK) return rc;
+    gbufArgs(&a, in, out->row_pitch_px);
     hipError_t e = quad ? launch_gbuffer_from_materials_quad(st, a, qp) : launch_gbuffer_from_materials(st, a);
     if (e != hipSuccess) return failHip(ctx, e, (w + " launch").c_str());
     return releaseSlot(ctx, slot, st);
@@ -1025,23 +1046,15 @@ static int sceneNormalsFromMaterials(vqhip_ctx* ctx, const std::string& w, bool 
     if (pitch < in->width) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": bad output pitch");
     QuadPlane qp = { nullptr, 0 };
     if (quad) {
-        size_t qb;
-        if ((rc = validateQuadPlane(ctx, w, in, quadUV, quad_pitch_px, &qp, &qb)) != VQHIP_OK) return rc;
-        if (rangesOverlap(quadUV, qb, out, planeBytes(in, pitch, outFmt == VQHIP_FMT_RGBA32F ? 16 : 4))) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quadUV overlaps an output");
+        const Span outs[] = { written(in, out, pitch, outFmt == VQHIP_FMT_RGBA32F ? 16 : 4) };
+        if ((rc = validateQuadPlane(ctx, w, in, quadUV, quad_pitch_px, outs, 1, &qp)) != VQHIP_OK) return rc;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     int slot;
-    rc = acquireSlot(ctx, &slot);
-    if (rc) return rc;
-    const size_t bytes = fillGbufConstants(ctx, slot, materials, numMaterials, 0.0f, nullptr);
-    rc = commitSlot(ctx, slot, bytes, st);
-    if (rc) return rc;
-    GbufArgs a;
-    a.ip0 = (const float4*)in->ip0; a.ip1 = (const float4*)in->ip1; a.ip2 = (const float4*)in->ip2;
-    a.gb0 = a.gb1 = a.gb2 = a.gb3 = nullptr;
-    a.gc = (const GbufConstants*)(ctx->devRing + (size_t)slot * kConstSlotBytes);
-    a.width = in->width; a.height = in->height; a.pitch = in->row_pitch_px; a.outPitch = pitch;
+    GbufArgs a = {};
+    if ((rc = stageConstants(ctx, st, &slot, &a.gc, fillGbufConstants, materials, numMaterials, 0.0f, (const vqhip_ssao*)nullptr)) != VQHIP_OK) return rc;
+    gbufArgs(&a, in, pitch);
     hipError_t e = quad ? launch_scene_normals_from_materials_quad(st, a, out, outFmt, qp) : launch_scene_normals_from_materials(st, a, out, outFmt);
     if (e != hipSuccess) return failHip(ctx, e, (w + " launch").c_str());
     return releaseSlot(ctx, slot, st);
@@ -1061,16 +1074,6 @@ int vqhip_scene_normals_from_materials_quad(vqhip_ctx* ctx, void* stream, const 
 
 // PSMain as the engine runs it (ForwardLighting.hlsl:226-380, the lit draws of RenderSceneColor, SceneRendering.cpp:1619-1760): interpolants +
 // materials in, scene colour out, one kernel — the G-buffer record stays in registers. Two ring slots: the producer's constants and the lighting's.
-int vqhip_forward_lighting_from_materials(vqhip_ctx* ctx, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
-        const vqhip_ssao* ssao, const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
-        const VQ_PointLight* extraPoint, int numExtraPoint, const vqhip_envmap* env, const vqhip_shadowmaps* sm,
-        void* out, int out_row_pitch_px, vqhip_format outFmt) {
-    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "forward_lighting_from_materials: ctx is NULL");
-    CTX_GUARD(ctx, "forward_lighting_from_materials");
-    return vqhip_forward_lighting_from_materials_mrt(ctx, stream, in, materials, numMaterials, ssao, perFrame, perView, extraPoint, numExtraPoint, env, sm,
-                                                     out, out_row_pitch_px, outFmt, nullptr);
-}
-
 static int forwardFromMaterials(vqhip_ctx* ctx, const std::string& w, bool quad, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
         const vqhip_ssao* ssao, const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
         const VQ_PointLight* extraPoint, int numExtraPoint, const vqhip_envmap* env, const vqhip_shadowmaps* sm,
@@ -1087,32 +1090,32 @@ static int forwardFromMaterials(vqhip_ctx* ctx, const std::string& w, bool quad,
     if ((rc = fillMrt(ctx, w.c_str(), targets, in->width, &mrt)) != VQHIP_OK) return rc;
     QuadPlane qp = { nullptr, 0 };
     if (quad) {
-        size_t qb;
-        if ((rc = validateQuadPlane(ctx, w, in, quadUV, quad_pitch_px, &qp, &qb)) != VQHIP_OK) return rc;
-        const bool over = rangesOverlap(quadUV, qb, out, planeBytes(in, out_row_pitch_px, outFmt == VQHIP_FMT_RGBA32F ? 16 : 8)) ||
-                          rangesOverlap(quadUV, qb, in->ip2, planeBytes(in, in->row_pitch_px, 16)) ||      // ip2.w receives the discard's -1
-                          rangesOverlap(quadUV, qb, mrt.albedo, planeBytes(in, mrt.albedoPitch, mrt.albedoF32 ? 16 : 8)) ||
-                          rangesOverlap(quadUV, qb, mrt.motion, planeBytes(in, mrt.motionPitch, mrt.motionF32 ? 8 : 4));
-        if (over) return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": quadUV overlaps an output");
+        const Span outs[] = { written(in, out, out_row_pitch_px, outFmt == VQHIP_FMT_RGBA32F ? 16 : 8), written(in, in->ip2, in->row_pitch_px, 16),      // ip2.w receives the discard's -1
+                              written(in, mrt.albedo, mrt.albedoPitch, mrt.albedoF32 ? 16 : 8), written(in, mrt.motion, mrt.motionPitch, mrt.motionF32 ? 8 : 4) };
+        if ((rc = validateQuadPlane(ctx, w, in, quadUV, quad_pitch_px, outs, 4, &qp)) != VQHIP_OK) return rc;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     int slotG, slotF;
-    if ((rc = acquireSlot(ctx, &slotG)) != VQHIP_OK || (rc = acquireSlot(ctx, &slotF)) != VQHIP_OK) return rc;
-    const size_t bytesG = fillGbufConstants(ctx, slotG, materials, numMaterials, perFrame->fAmbientLightingFactor, ssao);     // cbPerFrame.fAmbientLightingFactor, :247
-    const size_t bytesF = fillFrameConstants(ctx, slotF, perFrame, perView, extraPoint, numExtraPoint, env, sm);
-    if ((rc = commitSlot(ctx, slotG, bytesG, st)) != VQHIP_OK || (rc = commitSlot(ctx, slotF, bytesF, st)) != VQHIP_OK) return rc;
-    GbufArgs a;
-    a.ip0 = (const float4*)in->ip0; a.ip1 = (const float4*)in->ip1; a.ip2 = (const float4*)in->ip2;
-    a.gb0 = a.gb1 = a.gb2 = a.gb3 = nullptr;
-    a.gc = (const GbufConstants*)(ctx->devRing + (size_t)slotG * kConstSlotBytes);
-    a.width = in->width; a.height = in->height; a.pitch = in->row_pitch_px; a.outPitch = 0;
-    const FrameConstants* fc = (const FrameConstants*)(ctx->devRing + (size_t)slotF * kConstSlotBytes);
+    GbufArgs a = {};
+    const FrameConstants* fc;
+    if ((rc = stageConstants(ctx, st, &slotG, &a.gc, fillGbufConstants, materials, numMaterials, perFrame->fAmbientLightingFactor, ssao)) != VQHIP_OK ||     // cbPerFrame.fAmbientLightingFactor, :247
+        (rc = stageConstants(ctx, st, &slotF, &fc, fillFrameConstants, perFrame, perView, extraPoint, numExtraPoint, env, sm)) != VQHIP_OK) return rc;
+    gbufArgs(&a, in, 0);
     hipError_t e = quad ? launch_forward_from_materials_quad(st, a, fc, env != nullptr, casters, out, out_row_pitch_px, outFmt, ctx->arithDxc, ctx->opt, mrt, qp)
                         : launch_forward_from_materials(st, a, fc, env != nullptr, casters, out, out_row_pitch_px, outFmt, ctx->arithDxc, ctx->opt, mrt);
     if (e != hipSuccess) return failHip(ctx, e, (w + " launch").c_str());
     if ((rc = releaseSlot(ctx, slotG, st)) != VQHIP_OK) return rc;
     return releaseSlot(ctx, slotF, st);
+}
+int vqhip_forward_lighting_from_materials(vqhip_ctx* ctx, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
+        const vqhip_ssao* ssao, const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
+        const VQ_PointLight* extraPoint, int numExtraPoint, const vqhip_envmap* env, const vqhip_shadowmaps* sm,
+        void* out, int out_row_pitch_px, vqhip_format outFmt) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "forward_lighting_from_materials: ctx is NULL");
+    CTX_GUARD(ctx, "forward_lighting_from_materials");
+    return forwardFromMaterials(ctx, "forward_lighting_from_materials", false, stream, in, materials, numMaterials, ssao, perFrame, perView, extraPoint, numExtraPoint, env, sm,
+                                out, out_row_pitch_px, outFmt, nullptr, nullptr, 0);
 }
 int vqhip_forward_lighting_from_materials_mrt(vqhip_ctx* ctx, void* stream, const vqhip_interpolants* in, const vqhip_material* materials, int numMaterials,
         const vqhip_ssao* ssao, const VQ_PerFrameData* perFrame, const VQ_PerViewLightingData* perView,
@@ -1331,10 +1334,8 @@ int vqhip_composite_reflections(vqhip_ctx* ctx, void* stream, const void* reflec
 // ---- SSR front ends (docs/DESIGN_DETAILS.md §7.11-7.13): what the six entry points below share ----------------------------------------------------------------
 namespace {
 struct Plane { const void* p; int pitchPx; size_t bpp; const char* name; };           // one full-frame plane; pitchPx 0: dense rows
-struct Span { const void* p; size_t n; const char* name; };                           // the bytes that a plane, a per-tile buffer or a list covers
 int pitchOr(int pitchPx, int W) { return pitchPx ? pitchPx : W; }
-size_t planeBytes(int W, int H, const Plane& q) { return ((size_t)(H - 1) * pitchOr(q.pitchPx, W) + W) * q.bpp; }
-Span spanOf(int W, int H, const Plane& q) { return { q.p, planeBytes(W, H, q), q.name }; }
+Span spanOf(int W, int H, const Plane& q) { return { q.p, planeExtent(W, H, pitchOr(q.pitchPx, W), q.bpp), q.name }; }
 bool isNormalFmt(int f) { return f == VQHIP_FMT_R10G10B10A2_UNORM || f == VQHIP_FMT_RGBA32F; }
 bool isAvgFmt(int f) { return f == VQHIP_FMT_R11G11B10_FLOAT || f == VQHIP_FMT_RGBA32F; }
 size_t imgBpp(int f) { return f == VQHIP_FMT_RGBA32F ? 16 : 8; }
@@ -1356,15 +1357,7 @@ const Plane* shortPitch(int W, const Plane* q, int n) {                         
     for (int i = 0; i < n; ++i) if (pitchOr(q[i].pitchPx, W) < W) return &q[i];
     return nullptr;
 }
-// The overlap questions of the denoiser passes: outputs against each other, against the inputs, against the tile list. Each finds the pair; the caller words the refusal
-bool overlapsAny(const Span& s, const Span* outs, int nOut) {
-    for (int i = 0; i < nOut; ++i) if (rangesOverlap(s.p, s.n, outs[i].p, outs[i].n)) return true;
-    return false;
-}
-bool overlapEachOther(const Span* outs, int nOut) {
-    for (int i = 0; i + 1 < nOut; ++i) if (overlapsAny(outs[i], outs + i + 1, nOut - i - 1)) return true;
-    return false;
-}
+// The overlap questions of the denoiser passes beyond overlapsAny and overlapEachOther: outputs against the inputs, against the tile list. Each finds the pair; the caller words the refusal
 const Plane* inputUnder(int W, int H, const Plane* in, int nIn, const Span* outs, int nOut) {     // the first input that one of `outs` lies on
     for (int i = 0; i < nIn; ++i) if (overlapsAny(spanOf(W, H, in[i]), outs, nOut)) return &in[i];
     return nullptr;
@@ -1458,7 +1451,8 @@ int vqhip_ssr_intersect(vqhip_ctx* ctx, void* stream, const uint32_t* rayList, c
     if (badEnv(env)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: env needs the specular cube and the BRDF LUT");
     const Plane planes[] = { { litScene, litPitchPx, imgBpp(litFmt), "" }, { radiance, radiancePitchPx, imgBpp(radianceFmt), "" }, { normals, normalPitchPx, nrmBpp(normalFmt), "" } };
     if (shortPitch(W, planes, 3)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: pitch < width");
-    if (rangesOverlap(litScene, planeBytes(W, H, planes[0]), radiance, planeBytes(W, H, planes[1]))) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: radiance overlaps the lit scene");
+    const Span radianceSpan = spanOf(W, H, planes[1]);
+    if (overlapsAny(spanOf(W, H, planes[0]), &radianceSpan, 1)) return fail(ctx, VQHIP_ERR_INVALID_ARG, "ssr_intersect: radiance overlaps the lit scene");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     SsrTraceArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -2072,8 +2066,7 @@ int shadowDepthCall(vqhip_ctx* ctx, void* stream, const VIEW* views, int numView
     if (anyMasked && numJobs > kRasterMaxMaskedDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": more than 10000 draws in one call that has a masked draw");
     if (maskedTris >= 0xffffffffull) return fail(ctx, VQHIP_ERR_UNSUPPORTED, who + ": 2^32 - 1 or more masked instanced triangles in one call");      // the record's 32-bit stamp
     for (int v = 0; v < numViews; ++v) {
-        const size_t bytes = (size_t)(hv[v].dim - 1) * hv[v].pitch * 4 + (size_t)hv[v].dim * 4;
-        if (rangesOverlap(work, need, hv[v].depth, bytes)) return bad(v, -1, "depth overlaps the work buffer");
+        if (rangesOverlap(work, need, hv[v].depth, planeExtent((int)hv[v].dim, (int)hv[v].dim, hv[v].pitch, 4))) return bad(v, -1, "depth overlaps the work buffer");
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
@@ -2211,12 +2204,11 @@ int sceneDepthCall(vqhip_ctx* ctx, void* stream, const DRAW* draws, int numDraws
         return bad(kMaskedEntry ? "workBytes below vqhip_scene_masked_depth_work_bytes(the call's instanced and masked instanced triangles, numDraws)"
                                 : "workBytes below vqhip_scene_depth_work_bytes(the call's instanced triangles)");
     const bool anyMasked = !table.empty();
-    const size_t rows = (size_t)(height - 1);
-    bool overlap = rangesOverlap(work, need, out->depth, (rows * pitch + width) * px) ||
-                   (out->primitive && rangesOverlap(work, need, out->primitive, (rows * pitch + width) * px));
+    bool overlap = rangesOverlap(work, need, out->depth, planeExtent(width, height, pitch, px)) ||
+                   (out->primitive && rangesOverlap(work, need, out->primitive, planeExtent(width, height, pitch, px)));
     for (int k = 0; k < out->layers; ++k)
-        overlap = overlap || (out->coverage[k] && rangesOverlap(work, need, out->coverage[k], rows * covPitch + width)) ||
-                  (out->layerPrimitive[k] && rangesOverlap(work, need, out->layerPrimitive[k], (rows * pitch + width) * 4));
+        overlap = overlap || (out->coverage[k] && rangesOverlap(work, need, out->coverage[k], planeExtent(width, height, covPitch, 1))) ||
+                  (out->layerPrimitive[k] && rangesOverlap(work, need, out->layerPrimitive[k], planeExtent(width, height, pitch, 4)));
     if (overlap) return bad("an output overlaps the work buffer");
 
     SceneDepthArgs a;
@@ -2327,12 +2319,11 @@ static int sceneInterpolants(vqhip_ctx* ctx, const std::string& w, void* stream,
     if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": more than 20000 draws in one call");
     const size_t need = vqhip_scene_interpolants_work_bytes(numDraws);
     if (workBytes < need) return bad("workBytes below vqhip_scene_interpolants_work_bytes(numDraws)");
-    const size_t rows = (size_t)(height - 1);
-    const size_t ownerBytes = (rows * ownerPitch + width) * 4;
-    const size_t quadBytes = (rows * quadPitch + width) * 16;
+    const size_t ownerBytes = planeExtent(width, height, ownerPitch, 4);
+    const size_t quadBytes = planeExtent(width, height, quadPitch, 16);
     for (int k = 0; k < 6; ++k) {
         if (!planes[k]) continue;
-        const size_t bytes = k == 5 ? quadBytes : (rows * (k < 3 ? pitch : svPitch) + width) * 16;
+        const size_t bytes = k == 5 ? quadBytes : planeExtent(width, height, k < 3 ? pitch : svPitch, 16);
         if (rangesOverlap(work, need, planes[k], bytes)) return bad("an output overlaps the work buffer");
         if (rangesOverlap(owner, ownerBytes, planes[k], bytes)) return bad("an output overlaps the owner plane");
         if (k < 5 && rangesOverlap(planes[5], quadBytes, planes[k], bytes)) return bad("quadUV overlaps another output");
@@ -2416,8 +2407,7 @@ int vqhip_object_ids(vqhip_ctx* ctx, void* stream, const vqhip_object_id_draw* d
     if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": more than 20000 draws in one call");
     const size_t need = vqhip_object_ids_work_bytes(numDraws);
     if (workBytes < need) return bad("workBytes below vqhip_object_ids_work_bytes(numDraws)");
-    const size_t rows = (size_t)(height - 1);
-    const size_t ownerBytes = (rows * ownerPitch + width) * 4, idsBytes = (rows * idsPitch + width) * 16;
+    const size_t ownerBytes = planeExtent(width, height, ownerPitch, 4), idsBytes = planeExtent(width, height, idsPitch, 16);
     if (rangesOverlap(work, need, ids, idsBytes)) return bad("ids overlaps the work buffer");
     if (rangesOverlap(owner, ownerBytes, ids, idsBytes)) return bad("ids overlaps the owner plane");
 
@@ -2498,9 +2488,8 @@ int vqhip_outline(vqhip_ctx* ctx, void* stream, const vqhip_outline_draw* draws,
     size_t offColors, colorCap, offBoxes, offRecords, need;
     if (!outlineLayout(totalTris, &offColors, &colorCap, &offBoxes, &offRecords, &need) || workBytes < need)
         return bad("workBytes below vqhip_outline_work_bytes(the call's triangles)");
-    const size_t rows = (size_t)(height - 1);
     const void* const planes[3] = { out->sceneColor, out->selection, out->writer };
-    const size_t bytes[3] = { (rows * pitch + width) * 8, rows * selPitch + width, (rows * wrPitch + width) * 4 };
+    const size_t bytes[3] = { planeExtent(width, height, pitch, 8), planeExtent(width, height, selPitch, 1), planeExtent(width, height, wrPitch, 4) };
     for (int k = 0; k < 3; ++k) {
         if (!planes[k]) continue;
         if (rangesOverlap(work, need, planes[k], bytes[k])) return bad("an output overlaps the work buffer");
