@@ -357,7 +357,8 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * vqhip_scene_interpolants (+ _work_bytes), vqhip_scene_surface_draw, vqhip_scene_interpolant_targets, option interp_form;
                                * vqhip_scene_masked_depth, vqhip_shadow_masked_depth (+ _work_bytes), vqhip_scene_masked_depth_draw, vqhip_shadow_masked_draw / _view;
                                * vqhip_scene_quad_interpolants and the three _quad producers, vqhip_scene_quad_targets;
-                               * vqhip_object_ids (+ _work_bytes), vqhip_object_id_draw; vqhip_outline (+ _work_bytes), VQ_OutlineData, vqhip_outline_draw / _targets */
+                               * vqhip_object_ids (+ _work_bytes), vqhip_object_id_draw; vqhip_outline (+ _work_bytes), VQ_OutlineData, vqhip_outline_draw / _targets;
+                               * vqhip_displace_meshes, vqhip_displace_job, VQHIP_DISPLACE_MAX_JOBS */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -1096,7 +1097,7 @@ VQHIP_API int vqhip_adaptive_cacao(vqhip_ctx* ctx, void* stream, const float* de
  * (R1 vertex stage, R2 clipping against w >= 2^-24 and the four side planes — no z planes: DepthClipEnable is FALSE —, R3 viewport and 16.8 snap, R4 top-left
  * coverage in int64, R5 z/w and R6 LINEAR_DEPTH interpolation); tests/shadow_raster_ref.py states it in numpy. R2, R5 and R6 are UNPINNED against a D3D12
  * device (docs/WARP_CALIBRATION.md §5).
- * The ENABLE_ALPHA_MASK variant is vqhip_shadow_masked_depth (below). Out of scope: the tessellation and heightmap variants (the null heightmap's + 0.0f is kept), wireframe.
+ * The ENABLE_ALPHA_MASK variant is vqhip_shadow_masked_depth (below). Out of scope: the tessellation variants (the heightmap variant is vqhip_displace_meshes in front of this call; the null heightmap's + 0.0f is kept), wireframe.
  * Three kernels on `stream` (plus one setup launch per further ~700 draws): counters, triangle setup, tile fill. No allocation, no memset node; the call clears
  * each map itself (uncovered texels read 1.0; a view with numDraws == 0 yields all 1.0). View and draw descriptors are host memory, consumed before the call
  * returns; meshes and matrices are device memory, read when the kernels run. The maps of one call must not overlap each other, the work buffer or the inputs. */
@@ -1139,7 +1140,7 @@ VQHIP_API int vqhip_shadow_depth(vqhip_ctx* ctx, void* stream, const vqhip_shado
  * report. docs/DESIGN_DETAILS.md §7.17 is the normative statement (V1 vertex stage = R1, V2 clipping against seven planes, V3 viewport, V4 sample positions, V5
  * per-sample z/w and the depth test as one 64-bit minimum); tests/scene_depth_ref.py states it in numpy. V2's z planes (a guard band is as legal), V4's sample
  * positions and V5's interpolation precision are UNPINNED against a D3D12 device (docs/WARP_CALIBRATION.md §5).
- * The ENABLE_ALPHA_MASK variant is vqhip_scene_masked_depth (below). Out of scope: the tessellation and heightmap variants (the null heightmap's + 0.0f is kept), wireframe, the pass's normals target
+ * The ENABLE_ALPHA_MASK variant is vqhip_scene_masked_depth (below). Out of scope: the tessellation variants (the heightmap variant is vqhip_displace_meshes in front of this call; the null heightmap's + 0.0f is kept), wireframe, the pass's normals target
  * (vqhip_scene_normals_from_materials writes it from interpolants). The interpolant planes are vqhip_scene_interpolants' (below), from this call's owner planes.
  * Outputs (pitches in pixels, coverage_pitch in bytes, 0 = dense = width; every pointer but depth may be NULL):
  *   depth           samples 1: float [height][pitch] — the `depth` of vqhip_depth_hierarchy; samples 4: float [height][pitch][4], 16-byte aligned — the depth_ms of
@@ -1208,7 +1209,7 @@ VQHIP_API int vqhip_scene_depth(vqhip_ctx* ctx, void* stream, const vqhip_scene_
  * The table is staged through the context's constant ring (one table-copy launch per ring slot of 556 draws), then ONE kernel (a wave whose 64 pixels share
  * one owner fetches it once; option interp_form lane switches that path off, same bits). No allocation, no memset node, no
  * readback. Draw descriptors are host memory, consumed before the call returns; meshes and matrices are device memory, read when the kernel runs. Not modelled:
- * the heightmap (the null heightmap's float3 add is kept), tessellation. The alpha mask needs nothing here: vqhip_scene_masked_depth keeps discarded fragments out of
+ * tessellation (the heightmap variant is vqhip_displace_meshes in front of this call; the null heightmap's float3 add is kept). The alpha mask needs nothing here: vqhip_scene_masked_depth keeps discarded fragments out of
  * the owner plane, and the shading entry points repeat the discard. vqhip_gbuffer_from_materials still takes its uv LOD from neighbouring pixels
  * of the planes, so at primitive edges it differs from a helper-lane derivative. vqhip_scene_quad_interpolants and the _quad producers (below, after the
  * masked-depth section) carry the helper lanes' uv from this resolve to the producers and close that gap. */
@@ -1265,7 +1266,7 @@ VQHIP_API int vqhip_scene_interpolants(vqhip_ctx* ctx, void* stream, const vqhip
  * A masked draw's mesh is the engine's vertex: uv at byte 36, strideBytes >= 44. Textures are vqhip_texture2d: RGBA8_UNORM mip chains in device memory; the
  * descriptors (materials, texDiffuseAlpha) are HOST memory, consumed before the call returns.
  * (The names put `masked` before `depth` so that the prefixes vqhip_scene_depth* / vqhip_shadow_depth* keep denoting the opaque pair alone.)
- * Out of scope: the heightmap and tessellation variants, the separate texAlphaMask map (t3: bound, not read by these shaders), the Outline pass's
+ * Out of scope: the tessellation variants (the heightmap variant is vqhip_displace_meshes in front of these calls), the separate texAlphaMask map (t3: bound, not read by these shaders), the Outline pass's
  * masked permutation (the ObjectID pass's rides on this call: vqhip_object_ids, below).
  * Work: the opaque call's layout is the prefix; behind it a device table of the draws' textures (48 bytes per draw, staged through the constant ring like
  * vqhip_scene_interpolants' table: one table-copy launch per ring slot) and one 64-byte side record per masked instanced triangle (the unclipped clip-space
@@ -1369,7 +1370,7 @@ VQHIP_API int vqhip_scene_normals_from_materials_quad(vqhip_ctx* ctx, void* stre
  * rule M3: fragments that rule discards never reach the owner plane, so the ids show what lies behind the holes. One difference from ObjectID.hlsl: M3 discards
  * only when the material's HasDiffuseMap bit is set, ObjectID.hlsl has no such test. It shows only for a material flagged masked WITHOUT a diffuse map, which
  * Material::IsAlphaMasked excludes.
- * Out of scope: the tessellation and heightmap variants of the pass. The Outline pass is vqhip_outline (below); the Magnifier pass runs on the swap-chain image. */
+ * Out of scope: the tessellation variants of the pass (the heightmap variant is vqhip_displace_meshes in front of the depth call). The Outline pass is vqhip_outline (below); the Magnifier pass runs on the swap-chain image. */
 typedef struct vqhip_object_id_draw {   /* one DrawIndexedInstanced of ObjectIDPass::RecordCommands, in the order of the depth call that produced `owner` */
     uint32_t numIndices, numInstances;  /* what that call drew: gives q its meaning (numIndices a multiple of 3, numInstances 1 .. 64) */
     const int32_t* objID;               /* device, int4 [numInstances], 4-byte aligned: PerObjectLightingData.ObjID; .x and .w are read */
@@ -1414,8 +1415,8 @@ VQHIP_API int vqhip_object_ids(vqhip_ctx* ctx, void* stream, const vqhip_object_
  * node, no readback. Draw descriptors are host memory, consumed before the call returns; meshes and constant buffers are device memory, read when the kernels run.
  * numDraws == 0 leaves sceneColor untouched and clears selection / writer. Option raster_tile 64 is honoured.
  * Out of scope: 4x MSAA (the library has no per-sample scene colour: vqhip_forward_lighting_msaa shades and resolves in one kernel; it would take a sample-mask /
- * writer output here and an override input in that resolve), the pass's "_AlphaMasked" permutation, the tessellation and heightmap variants (the null heightmap's
- * + 0.0f is kept), the Magnifier pass. */
+ * writer output here and an override input in that resolve), the pass's "_AlphaMasked" permutation, the tessellation variants (the heightmap variant is
+ * vqhip_displace_meshes in front of this call; the null heightmap's + 0.0f is kept), the Magnifier pass. */
 typedef struct VQ_OutlineData {  /* byte for byte the cbuffer OutlineData of Outline.hlsl / FOutlineRenderData::FConstantBuffer (DrawData.h:69-79) */
     VQ_matrix matWorld, matWorldView, matNormalView, matProj, matViewInverse;
     VQ_float4 Color, uvScaleBias; float Scale, HeightDisplacement;
@@ -1448,6 +1449,50 @@ VQHIP_API size_t vqhip_outline_work_bytes(uint64_t triangles);
  * overlapping another output or the work buffer; VQHIP_ERR_UNSUPPORTED for more than 20 000 draws with indices or 2^28 or more triangles in one call. */
 VQHIP_API int vqhip_outline(vqhip_ctx* ctx, void* stream, const vqhip_outline_draw* draws, int numDraws, int width, int height,
         const vqhip_outline_targets* out, void* work, size_t workBytes);
+
+/* ---- Heightmap displacement for every rasterised pass: CalcHeightOffset of the five vertex stages (ForwardLighting.hlsl:136-154, DepthPrePass.hlsl:96-100,
+ * ShadowDepthPass.hlsl:61-66, ObjectID.hlsl:70-74, Outline.hlsl:78-82), each of which runs
+ *     vPosition.xyz += float3(0, texHeightmap.SampleLevel(LinearSamplerTess, uv * scale + offset, 0).r * displacement, 0)
+ * before any matrix. Batching.cpp:156-157 hands the shadow pass the (tiling, uv_bias) and displacement that Material::GetCBufferData hands the others, and the
+ * Outline pass receives the same number as HeightDisplacement: the offset is a function of (vertex, material) alone. This call therefore writes a displaced COPY of
+ * a mesh's vertex stream, once per (mesh LOD, material), and every rasteriser of this library consumes that copy unchanged: the add happens once, in binary32,
+ * before any matrix, exactly where the reference does it. docs/DESIGN_DETAILS.md §7.22 is the normative statement; tests/displace_ref.py states it in numpy:
+ *   H1  u = uv.x * scale.x + offset.x, v likewise: binary32, product and sum rounded separately, whatever vqhip_set_arithmetic says (§7.18 I1's statement).
+ *   H2  s = the bilinear WRAP fetch of LEVEL 0 of the RGBA8_UNORM chain (LinearSamplerTess is TRILINEAR_WRAP, RootSignatures.cpp:151, :361; SampleLevel 0), red
+ *       channel: 8-bit fixed-point fractions, exact weights, the FMA chain of the sampling contract, then * RN(1 / 255). Only level 0 is read, whatever `mips`
+ *       says. texels == NULL is the null SRV: s = 0.0f. Any uv is safe, NaN and +-inf included: no lane reads outside level 0.
+ *   H3  h = s * displacement (one product); y' = y + h (one sum); x and z are copied bit for bit (the reference's + 0.0f on x and z is the one the rasterisers
+ *       keep downstream).
+ *   H4  the one known deviation, a sign of zero: the consumers' retained y + 0.0f turns a stored y' = -0 into +0, the reference's single y + h keeps -0 (only
+ *       when y and h are both -0). No tested output can tell: §7.22.
+ * outStrideBytes == strideBytes: the whole vertex is copied with y replaced (normal @12, tangent @24, uv @36 and any tail words bit for bit) — the stream of the
+ * lit, Outline and masked draws. outStrideBytes == 12: the displaced position alone — the compact stream of the opaque depth and shadow draws. One call takes many
+ * meshes: the job table is staged through the context's constant ring (a slot holds 556 jobs), ONE kernel launch per ring slot, never one per mesh. No allocation,
+ * no memset node, no readback. Jobs are host memory, consumed before the call returns; vertices, out and the height map are device memory, read and written when
+ * the kernels run. H2 in a vertex stage is UNPINNED against a D3D12 device (docs/WARP_CALIBRATION.md §5), like every other Sample* here.
+ * Out of scope: the tessellated permutations (and their height-derived normals, ForwardLighting.hlsl:255-262), height maps in other formats, displacing in place. */
+typedef struct vqhip_displace_job {
+    const void* vertices;  uint32_t strideBytes;   /* device, 4-byte aligned; the engine's vertex: position @0, uv @36; 44 .. 2048 (D3D12's vertex stride limit), a multiple of 4 */
+    uint32_t    numVertices;                       /* 0 allowed: nothing written */
+    void*       out;       uint32_t outStrideBytes;/* device, 4-byte aligned; == strideBytes (full copy) or 12 (positions only) */
+    uint32_t    reserved;                          /* 0 */
+    vqhip_texture2d heightmap;                     /* RGBA8_UNORM chain, level 0 read; texels NULL = null SRV */
+    VQ_float4   uvScaleOffset;                     /* MaterialData.uvScaleOffset == PerObjectShadowData.texScaleBias */
+    float       displacement;                      /* MaterialData.displacement == Outline's HeightDisplacement */
+} vqhip_displace_job;
+VQHIP_STATIC_ASSERT(sizeof(vqhip_displace_job) == 80 && offsetof(vqhip_displace_job, strideBytes) == 8 && offsetof(vqhip_displace_job, numVertices) == 12 &&
+                    offsetof(vqhip_displace_job, out) == 16 && offsetof(vqhip_displace_job, outStrideBytes) == 24 && offsetof(vqhip_displace_job, reserved) == 28 &&
+                    offsetof(vqhip_displace_job, heightmap) == 32 && offsetof(vqhip_displace_job, uvScaleOffset) == 56 && offsetof(vqhip_displace_job, displacement) == 72,
+                    "vqhip_displace_job layout");
+/* Jobs WITH vertices in one call: what 31 of the constant ring's 32 slots hold, so that one call never laps the ring. */
+#define VQHIP_DISPLACE_MAX_JOBS 17236
+/* Returns VQHIP_ERR_INVALID_ARG — launching nothing, leaving the outputs untouched — for a NULL ctx, NULL jobs with numJobs > 0, numJobs < 0, and for a job with:
+ * NULL vertices or out while numVertices > 0; a stride outside 44 .. 2048 or not a multiple of 4; an outStrideBytes that is neither 12 nor strideBytes;
+ * reserved != 0; vertices or out not 4-byte aligned; a height map with texels whose width or height is outside 1 .. 16384, whose mips is below 1 or above
+ * vqhip_mip_level_count(width, height), or whose texels are not 4-byte aligned; an output that overlaps its own input, any other job's input or output, or a
+ * height map (measured over numVertices * stride bytes and the whole chain). In-place operation is refused: a second call would displace twice.
+ * VQHIP_ERR_UNSUPPORTED for 2^31 or more vertices in one call, or more than VQHIP_DISPLACE_MAX_JOBS jobs with vertices. numJobs == 0 is VQHIP_OK. */
+VQHIP_API int vqhip_displace_meshes(vqhip_ctx* ctx, void* stream, const vqhip_displace_job* jobs, int numJobs);
 
 #ifdef __cplusplus
 }

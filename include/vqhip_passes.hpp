@@ -1171,4 +1171,49 @@ private:
     unsigned mWidth = 0, mHeight = 0;
 };
 
+// ---------------------------------------------------------------------------------------------------------------
+// Heightmap displacement == CalcHeightOffset of the five vertex stages (ForwardLighting.hlsl:136-154, DepthPrePass.hlsl:96-100, ShadowDepthPass.hlsl:61-66,
+// ObjectID.hlsl:70-74, Outline.hlsl:78-82), run ONCE per (mesh LOD, material with a height map and displacement != 0) instead of in every pass, view and frame:
+// vqhip_displace_meshes (docs/DESIGN_DETAILS.md §7.22 H1 .. H4). Not a pass of the reference's frame: a load-time step, called again only when a material's tiling
+// or displacement changes. Each FMesh asks for the full-stride stream (the lit, Outline and masked draws), the 12-byte stream (the opaque depth and shadow draws)
+// or both; the pass owns nothing — the caller brings the vertex buffers, the height map and the output streams, and afterwards points mesh.positions of every
+// draw of that (mesh, material) pair at the stream of its kind. Host-only code: the job table is built here, everything else happens in the library.
+// ---------------------------------------------------------------------------------------------------------------
+class HeightmapDisplacementPass : public OwnsNothingPass {
+public:
+    struct FMesh {
+        const void* Vertices = nullptr; uint32_t StrideBytes = 44; uint32_t NumVertices = 0;   // device: the mesh LOD's vertex buffer (the engine's vertex)
+        vqhip_texture2d Heightmap = {};                                                        // the material's SRVHeightMap; texels NULL: the null SRV
+        VQ_float4 uvScaleOffset = { 1.0f, 1.0f, 0.0f, 0.0f };                                  // MaterialData.uvScaleOffset (tiling, uv_bias)
+        float Displacement = 0.0f;                                                             // MaterialData.displacement
+        void* OutFull = nullptr;                                                               // device, NumVertices * StrideBytes bytes, or nullptr: not wanted
+        void* OutPositions = nullptr;                                                          // device, NumVertices * 12 bytes, or nullptr: not wanted
+    };
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        const std::vector<FMesh>* Meshes = nullptr;                                            // nullptr or empty: nothing to do
+    };
+    explicit HeightmapDisplacementPass(vqhip_ctx* Ctx) : OwnsNothingPass(Ctx) {}
+    // the jobs of a mesh list: one per stream asked for, in the order of the list (full before positions)
+    static void BuildJobs(const std::vector<FMesh>& Meshes, std::vector<vqhip_displace_job>& Jobs) {
+        Jobs.clear();
+        for (const FMesh& m : Meshes) {
+            vqhip_displace_job j = {};
+            j.vertices = m.Vertices; j.strideBytes = m.StrideBytes; j.numVertices = m.NumVertices;
+            j.heightmap = m.Heightmap; j.uvScaleOffset = m.uvScaleOffset; j.displacement = m.Displacement;
+            if (m.OutFull) { j.out = m.OutFull; j.outStrideBytes = m.StrideBytes; Jobs.push_back(j); }
+            if (m.OutPositions) { j.out = m.OutPositions; j.outStrideBytes = 12; Jobs.push_back(j); }
+        }
+    }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        if (p->Meshes) BuildJobs(*p->Meshes, mJobs); else mJobs.clear();
+        mStatus = vqhip_displace_meshes(mCtx, p->Stream, mJobs.empty() ? nullptr : mJobs.data(), (int)mJobs.size());
+    }
+    size_t GetNumJobs() const { return mJobs.size(); }                                         // of the last RecordCommands
+private:
+    std::vector<vqhip_displace_job> mJobs;                                                     // consumed by the call before it returns; kept to spare the allocation
+};
+
 } // namespace vqhip

@@ -319,6 +319,15 @@ OUTLINE_RECORDS_PER_TRIANGLE = 16            # vqhip_outline's work buffer: eigh
 NO_WRITER = 0xFFFFFFFF                       # vqhip_outline's writer value for "not written"
 
 
+class DisplaceJob(C.Structure):  # vqhip_displace_job
+    _fields_ = [("vertices", C.c_void_p), ("strideBytes", C.c_uint32), ("numVertices", C.c_uint32), ("out", C.c_void_p), ("outStrideBytes", C.c_uint32),
+                ("reserved", C.c_uint32), ("heightmap", Texture2D), ("uvScaleOffset", float4), ("displacement", C.c_float)]
+
+
+DISPLACE_MAX_JOBS = 17236                    # VQHIP_DISPLACE_MAX_JOBS: jobs with vertices in one vqhip_displace_meshes call (31 constant-ring slots of 556)
+DISPLACE_POSITION_BYTES = 12                 # outStrideBytes of the compact stream: the displaced position alone
+
+
 def _chk(t, size, **offs):
     assert C.sizeof(t) == size, (t.__name__, C.sizeof(t), size)
     for k, v in offs.items():
@@ -358,6 +367,7 @@ _chk(ObjectIdDraw, 24, numInstances=4, objID=8, meshID=16, materialID=20)
 _chk(OutlineData, 368, matWorldView=64, matNormalView=128, matProj=192, matViewInverse=256, Color=320, uvScaleBias=336, Scale=352, HeightDisplacement=356)
 _chk(OutlineDraw, 40, cb=32)
 _chk(OutlineTargets, 40, selection=8, writer=16, pitch=24, selection_pitch=28, writer_pitch=32, reserved=36)
+_chk(DisplaceJob, 80, strideBytes=8, numVertices=12, out=16, outStrideBytes=24, reserved=28, heightmap=32, uvScaleOffset=56, displacement=72)
 _chk(CacaoConstants, 384, EffectRadius=48, InvSharpness=96, PassIndex=100, PatternRotScaleMatrices=112, NormalsUnpackMul=192, SSAOBufferDimensions=208,
      DepthBufferOffset=240, PerPassFullResUVOffset=248, DeinterleavedDepthBufferNormalisedOffset=312, NormalsWorldToViewspaceMatrix=320)
 

@@ -131,6 +131,7 @@ def load_library():
         "vqhip_object_ids": (i32, [vp, vp, C.POINTER(abi.ObjectIdDraw), i32, i32, i32, vp, i32, vp, i32, vp, sz]),
         "vqhip_outline_work_bytes": (sz, [C.c_uint64]),
         "vqhip_outline": (i32, [vp, vp, C.POINTER(abi.OutlineDraw), i32, i32, i32, C.POINTER(abi.OutlineTargets), vp, sz]),
+        "vqhip_displace_meshes": (i32, [vp, vp, C.POINTER(abi.DisplaceJob), i32]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -171,6 +172,7 @@ EXPORTED_SYMBOLS = [
     "vqhip_scene_masked_depth", "vqhip_scene_masked_depth_work_bytes", "vqhip_shadow_masked_depth", "vqhip_shadow_masked_depth_work_bytes",
     "vqhip_scene_quad_interpolants", "vqhip_gbuffer_from_materials_quad", "vqhip_forward_lighting_from_materials_quad", "vqhip_scene_normals_from_materials_quad",
     "vqhip_object_ids", "vqhip_object_ids_work_bytes", "vqhip_outline", "vqhip_outline_work_bytes",
+    "vqhip_displace_meshes",
 ]
 
 
@@ -258,6 +260,18 @@ class OutlineDraw:
 
     def __init__(self, vertices, indices, cb):
         self.vertices, self.indices, self.cb = vertices, indices, cb
+
+
+class DisplaceJob:
+    """One vqhip_displace_job. vertices: cuda float32 [V, k] with k >= 11 and unit column stride (the engine's vertex: position 3, normal 3, tangent 3, uv 2; the
+    row stride is the vertex stride; V may be 0); heightmap: abi.Texture2D (host descriptor of a cuda RGBA8 mip chain, level 0 is read; texels None = null SRV) or
+    None for the null SRV; uv_scale_offset: MaterialData.uvScaleOffset, 4 floats (scale.xy, offset.xy); displacement: MaterialData.displacement; compact: write
+    the 12-byte positions-only stream instead of the full-stride copy; out: a preallocated cuda float32 [V, 3] contiguous (compact) or [V, k'] with the input's row
+    stride, else allocated."""
+
+    def __init__(self, vertices, heightmap=None, uv_scale_offset=(1.0, 1.0, 0.0, 0.0), displacement=0.0, compact=False, out=None):
+        self.vertices, self.heightmap, self.uv_scale_offset, self.displacement = vertices, heightmap, tuple(float(x) for x in uv_scale_offset), float(displacement)
+        self.compact, self.out = bool(compact), out
 
 
 def scene_depth_work_bytes(instanced_triangles):
@@ -1045,6 +1059,52 @@ class Context:
             self._ck(self.lib.vqhip_object_ids(self._h, self._stream(stream), cdraws, len(draws), w, h, _ptr(owner), owner.stride(0), _ptr(ids), ids.stride(0) // 4,
                                                _ptr(work), work.numel()))
         return call, res
+
+    def displace_meshes(self, jobs, stream=None):
+        """vqhip_displace_meshes: the heightmap-displaced copies of the vertex streams of the DisplaceJob list `jobs`, all in one call. Returns the list of output
+        tensors, one per job: float32 [V, 3] for a compact job, else float32 [V, k] with the input's row stride (every float of the row is copied)."""
+        call, outs = self.displace_meshes_prepared(jobs)
+        call(stream)
+        return outs
+
+    def displace_meshes_prepared(self, jobs):
+        """The descriptors of a displace_meshes call built once: returns (call, outputs) with call(stream=None) issuing vqhip_displace_meshes on the same jobs
+        again. The tensors must stay alive and in place."""
+        who_ = "displace_meshes"
+        jobs = list(jobs)
+        cjobs = (abi.DisplaceJob * max(1, len(jobs)))()
+        outs = []
+        for j, jb in enumerate(jobs):
+            who = f"{who_}: job {j}"
+            p = jb.vertices
+            if p.dim() == 2 and p.shape[0] == 0 and p.is_cuda and p.dtype == torch.float32 and p.shape[1] >= 11:
+                p = p.new_empty((0, p.shape[1]))             # no vertices: whatever strides the empty tensor came with, the job reads nothing
+            _check_vertices(who, "vertices", p, 11)
+            if len(jb.uv_scale_offset) != 4:
+                raise ValueError(f"{who}: uv_scale_offset: expected 4 floats")
+            if jb.heightmap is not None and not isinstance(jb.heightmap, abi.Texture2D):
+                raise ValueError(f"{who}: heightmap: expected abi.Texture2D or None")
+            n, stride = p.shape[0], p.stride(0)
+            o = jb.out
+            if o is None:
+                o = torch.empty((n, 3), dtype=torch.float32, device=self.device) if jb.compact else \
+                    torch.empty((n, stride), dtype=torch.float32, device=self.device)[:, :p.shape[1]]
+            ok = o.is_cuda and o.dtype == torch.float32 and o.dim() == 2 and o.shape[0] == n and o.stride(1) == 1
+            if not (ok and ((o.shape[1] == 3 and o.stride(0) == 3) if jb.compact else o.stride(0) == stride)):
+                raise ValueError(f"{who}: out: expected cuda float32 " + ("[V, 3] contiguous" if jb.compact else "[V, k] with the row stride of vertices"))
+            c = cjobs[j]
+            c.vertices, c.strideBytes, c.numVertices = p.data_ptr() or None, stride * 4, n
+            c.out, c.outStrideBytes, c.reserved = o.data_ptr() or None, abi.DISPLACE_POSITION_BYTES if jb.compact else stride * 4, 0
+            if jb.heightmap is not None:
+                c.heightmap = jb.heightmap
+            c.uvScaleOffset = abi.float4(*jb.uv_scale_offset)
+            c.displacement = jb.displacement
+            outs.append(o)
+        keep = (jobs, outs)
+
+        def call(stream=None, _keep=keep):
+            self._ck(self.lib.vqhip_displace_meshes(self._h, self._stream(stream), cjobs, len(jobs)))
+        return call, outs
 
     def outline(self, draws, width, height, scene_color, selection=True, writer=True, out=None, work=None, stream=None):
         """vqhip_outline: both passes of the Outline pass over the OutlineDraw list `draws`, writing the outline's colour IN PLACE into `scene_color`: cuda

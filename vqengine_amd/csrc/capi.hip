@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
+#include <algorithm>
 #include <atomic>
 #include <string>
 #include <thread>
@@ -2530,6 +2531,92 @@ int vqhip_outline(vqhip_ctx* ctx, void* stream, const vqhip_outline_draw* draws,
     if (int rc = stageJobs<OutlineJob>(ctx, st, numJobs, fill, setup)) return rc;
     e = launch_outline_fill(st, a, ctx->opt.rasterTile == 64 ? 64 : 32, counter, boxes, records);
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (w + " fill launch").c_str());
+}
+
+// ---- Heightmap displacement of vertex streams (displace.hip; docs/DESIGN_DETAILS.md §7.22 H1 .. H4) -------------------------------------------------------------------
+static_assert((vqhip_ctx::kSlots - 1) * (kConstSlotBytes / sizeof(DisplaceJob)) == VQHIP_DISPLACE_MAX_JOBS, "VQHIP_DISPLACE_MAX_JOBS is what 31 ring slots hold");
+static_assert(slotsFor<DisplaceJob>(VQHIP_DISPLACE_MAX_JOBS) < vqhip_ctx::kSlots, "one call never laps the ring");
+
+int vqhip_displace_meshes(vqhip_ctx* ctx, void* stream, const vqhip_displace_job* jobs, int numJobs) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "displace_meshes: ctx is NULL");
+    CTX_GUARD(ctx, "displace_meshes");
+    vqk::Range range_("DisplaceMeshes");
+    const std::string w = "displace_meshes";
+    auto bad = [&](const std::string& m) { return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": " + m); };
+    if (numJobs < 0 || (numJobs > 0 && !jobs)) return bad("numJobs < 0, or jobs is NULL");
+    uint64_t totalVertices = 0;
+    size_t numLive = 0;
+    // what a job reads and writes: [3 j] its input, [3 j + 1] its height map's chain, [3 j + 2] its output; p NULL (a job without vertices, the null SRV): nothing
+    std::vector<Span> spans((size_t)numJobs * 3, Span{ nullptr, 0, "" });
+    for (int j = 0; j < numJobs; ++j) {
+        const vqhip_displace_job& J = jobs[j];
+        auto badJob = [&](const std::string& m) { return bad("job " + std::to_string(j) + ": " + m); };
+        if (J.numVertices && (!J.vertices || !J.out)) return badJob("vertices or out is NULL");
+        if (J.strideBytes < 44 || J.strideBytes > 2048 || J.strideBytes % 4) return badJob("strideBytes must be 44..2048 and a multiple of 4");
+        if (J.outStrideBytes != 12 && J.outStrideBytes != J.strideBytes) return badJob("outStrideBytes must be 12 or strideBytes");
+        if (J.reserved != 0) return badJob("reserved must be 0");
+        if ((uintptr_t)J.vertices % 4 || (uintptr_t)J.out % 4) return badJob("vertices / out must be 4-byte aligned");
+        if (J.heightmap.texels) {                             // a null SRV samples 0: its dimensions are not read
+            const vqhip_texture2d& t = J.heightmap;
+            if (t.width < 1 || t.width > VQHIP_MASK_TEXTURE_MAX_DIM || t.height < 1 || t.height > VQHIP_MASK_TEXTURE_MAX_DIM) return badJob("height map: width and height must be 1..16384");
+            if (t.mips < 1 || t.mips > vqhip_mip_level_count(t.width, t.height)) return badJob("height map: mips must be 1..vqhip_mip_level_count(width, height)");
+            if ((uintptr_t)t.texels % 4) return badJob("height map: texels must be 4-byte aligned");
+        }
+        if (!J.numVertices) continue;
+        totalVertices += J.numVertices; ++numLive;
+        spans[3 * (size_t)j] = { J.vertices, planeExtent((int)J.strideBytes, (int)J.numVertices, J.strideBytes, 1), "input" };
+        if (J.heightmap.texels) spans[3 * (size_t)j + 1] = { J.heightmap.texels, vqhip_mip_chain_bytes_rgba8(J.heightmap.width, J.heightmap.height, J.heightmap.mips), "height map" };
+        spans[3 * (size_t)j + 2] = { J.out, planeExtent((int)J.outStrideBytes, (int)J.numVertices, J.outStrideBytes, 1), "output" };
+    }
+    if (totalVertices >= ((uint64_t)1 << 31)) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": 2^31 or more vertices in one call");
+    if (numLive > VQHIP_DISPLACE_MAX_JOBS) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": more than " + std::to_string(VQHIP_DISPLACE_MAX_JOBS) + " jobs with vertices in one call");
+    // An output must not meet anything else the call touches. In the order of their first bytes, a span overlaps an earlier one iff it starts before the
+    // furthest end seen so far: one sorted sweep keeps the furthest end of the outputs and of everything, instead of comparing every pair of up to 17 236 jobs.
+    {
+        std::vector<uint32_t> order;
+        for (size_t k = 0; k < spans.size(); ++k) if (spans[k].p && spans[k].n) order.push_back((uint32_t)k);
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return (uintptr_t)spans[a].p < (uintptr_t)spans[b].p; });
+        int lastOut = -1, lastAny = -1;                       // the spans whose ends reach furthest so far
+        auto end = [&](int k) { return (uintptr_t)spans[(size_t)k].p + spans[(size_t)k].n; };
+        for (uint32_t k : order) {
+            const Span& s = spans[k];
+            const bool isOut = k % 3 == 2;
+            const int hit = lastOut >= 0 && rangesOverlap(s.p, s.n, spans[(size_t)lastOut].p, spans[(size_t)lastOut].n) ? lastOut
+                          : isOut && lastAny >= 0 && rangesOverlap(s.p, s.n, spans[(size_t)lastAny].p, spans[(size_t)lastAny].n) ? lastAny : -1;
+            if (hit >= 0) {
+                const int o = isOut ? (int)k : hit, other = isOut ? hit : (int)k;
+                return bad("job " + std::to_string(o / 3) + ": the output overlaps the " + spans[(size_t)other].name + " of job " + std::to_string(other / 3) +
+                           (o / 3 == other / 3 && other % 3 == 0 ? " (displacing in place is refused: a second call would displace twice)" : ""));
+            }
+            if (isOut && (lastOut < 0 || end((int)k) > end(lastOut))) lastOut = (int)k;
+            if (lastAny < 0 || end((int)k) > end(lastAny)) lastAny = (int)k;
+        }
+    }
+    if (!numLive) return VQHIP_OK;
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    // the jobs that have vertices, in ring slots of DisplaceJobs: one launch per slot
+    int j = 0;
+    uint64_t blocks = 0;
+    auto fill = [&](DisplaceJob& D, size_t k) {
+        if (!k) blocks = 0;
+        while (!jobs[j].numVertices) ++j;
+        const vqhip_displace_job& J = jobs[j++];
+        std::memset(&D, 0, sizeof(D));
+        D.vertices = J.vertices; D.out = J.out; D.texels = J.heightmap.texels;
+        D.strideBytes = J.strideBytes; D.outStrideBytes = J.outStrideBytes; D.numVertices = J.numVertices;
+        D.width = J.heightmap.width; D.height = J.heightmap.height;
+        D.sx = J.uvScaleOffset.x; D.sy = J.uvScaleOffset.y; D.ox = J.uvScaleOffset.z; D.oy = J.uvScaleOffset.w;
+        D.displacement = J.displacement;
+        D.firstBlock = (uint32_t)blocks;                      // below 2^23 + the slot's jobs: the call has fewer than 2^31 vertices
+        blocks += ((uint64_t)J.numVertices + kDisplaceLanes - 1) / kDisplaceLanes;
+    };
+    auto launch = [&](const DisplaceJob* slotJobs, size_t n, size_t) {
+        hipError_t le = launch_displace(st, slotJobs, (int)n, (uint32_t)blocks);
+        return le == hipSuccess ? VQHIP_OK : failHip(ctx, le, (w + " launch").c_str());
+    };
+    return stageJobs<DisplaceJob>(ctx, st, numLive, fill, launch);
 }
 
 } // extern "C"

@@ -393,6 +393,21 @@ static constexpr size_t kOutlineBoxBytes = 8, kOutlineRecordBytes = 48, kOutline
 hipError_t launch_outline_setup(hipStream_t s, const OutlineJob* jobs, int numJobs, uint32_t firstJob, uint32_t blocks, const OutlineArgs& a, uint32_t* counter, void* boxes, void* records);
 hipError_t launch_outline_fill(hipStream_t s, const OutlineArgs& a, int tile, const uint32_t* counter, const void* boxes, const void* records);
 
+// Heightmap displacement of vertex streams (vqhip_displace_meshes, displace.hip; docs/DESIGN_DETAILS.md §7.22 H1 .. H4). The jobs travel in constant-ring slots,
+// one launch per slot; no work buffer. Jobs without vertices are not in the table.
+struct alignas(16) DisplaceJob {     // one vqhip_displace_job
+    const void* vertices; void* out; const void* texels;    // texels NULL: the null SRV, the sample is 0
+    uint32_t strideBytes, outStrideBytes, numVertices;
+    int32_t width, height;           // level 0 of the height map
+    uint32_t firstBlock;             // of this k_displace_vertices launch: ceil(numVertices / 256) blocks per job
+    float sx, sy, ox, oy;            // uvScaleOffset
+    float displacement;
+    uint32_t pad[3];
+};
+static_assert(sizeof(DisplaceJob) == 80, "DisplaceJob is five uint4");
+static constexpr int kDisplaceLanes = 256;               // vertices per block
+hipError_t launch_displace(hipStream_t s, const DisplaceJob* jobs, int numJobs, uint32_t blocks);
+
 // launchers (each returns the hipError_t of the launch)
 hipError_t launch_forward_lighting(hipStream_t s, const ShadeArgs& a, bool hasEnv, bool hasCasters, int outFmt, const Options& opt);
 hipError_t launch_blur_x(hipStream_t s, const void* in, void* out, int W, int H, int fmt, const Options& opt);

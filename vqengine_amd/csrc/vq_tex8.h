@@ -97,5 +97,12 @@ VQD float fetch_lane_alpha_level0(const void* texels, int w, int h, float u, flo
     const LevelTaps k = pot ? level_taps<true>(w, h, 0, u, v) : level_taps<false>(w, h, 0, u, v);
     return blend_taps(load_taps<false>((const uint32_t*)texels, k), k).w * kRcp255;
 }
+// the same fetch, red channel: texHeightmap.SampleLevel(LinearSamplerTess, uv, 0).r of the five vertex stages' CalcHeightOffset (displace.hip; §7.22 H2).
+// Any u, v is safe: fixed8 turns NaN into 0 and clamps, WRAP brings every tap inside level 0.
+VQD float fetch_lane_red_level0(const void* texels, int w, int h, float u, float v) {
+    const bool pot = ((w & (w - 1)) | (h & (h - 1))) == 0;
+    const LevelTaps k = pot ? level_taps<true>(w, h, 0, u, v) : level_taps<false>(w, h, 0, u, v);
+    return blend_taps(load_taps<false>((const uint32_t*)texels, k), k).x * kRcp255;
+}
 
 } // namespace vqk

@@ -1,4 +1,4 @@
-"""Host-side producers of what vqhip_scene_interpolants consumes beside shadow_scene's: procedural meshes in the engine's full 44-byte vertex (position 3,
+"""Host-side producers of what vqhip_scene_interpolants (and, at the end, vqhip_displace_meshes) consumes beside shadow_scene's: procedural meshes in the engine's full 44-byte vertex (position 3,
 normal 3, tangent 3, uv 2 -> float32 [V, 11]) and the four matrix blocks of PerObjectLightingData per instance. numpy only; shadow_scene is imported unchanged.
 
 Like shadow_scene this is an INPUT producer: the meshes are written for this project, the matrices are formed in binary64 and rounded once. Conventions are the
@@ -132,3 +132,38 @@ def mip_chain_rgba8(level0, mips=None):
         lv = ((s[y0][:, x0] + s[y0][:, x1] + s[y1][:, x0] + s[y1][:, x1]) // 4).astype(np.uint8)
         out.append(lv.reshape(-1, 4))
     return np.ascontiguousarray(np.concatenate(out, axis=0)), n
+
+
+# ---- heightmap displacement: what vqhip_displace_meshes consumes beside the meshes above --------------------------------------------------------------------------
+def heightmap_chain(w, h, kind="hill", seed=0, mips=None):
+    """An RGBA8 height map and its mip chain (mip_chain_rgba8's box filter): (chain uint8 [texels of all levels, 4], number of levels). The height lives in RED;
+    green is its complement, blue and alpha are seeded noise, so that a fetch of the wrong channel shows. kind: "hill" (a smooth bump on a raised base: no texel
+    is 0), "noise" (seeded, every value), "steps" (red = 16 x the texel's number mod 256: bilinear fractions show), "zero" (red 0 everywhere, the rest noise)."""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:h, 0:w]
+    if kind == "hill":
+        cx, cy = 0.5 * (w - 1), 0.5 * (h - 1)
+        r2 = ((x - cx) / max(0.5 * w, 1.0)) ** 2 + ((y - cy) / max(0.5 * h, 1.0)) ** 2
+        red = np.rint(40.0 + 215.0 * np.exp(-3.0 * r2))
+    elif kind == "noise":
+        red = rng.integers(0, 256, size=(h, w))
+    elif kind == "steps":
+        red = (16 * (y * w + x) + 8) % 256
+    elif kind == "zero":
+        red = np.zeros((h, w))
+    else:
+        raise ValueError(f"heightmap_chain: unknown kind {kind!r}")
+    img = np.empty((h, w, 4), dtype=np.uint8)
+    img[..., 0] = red
+    img[..., 1] = 255 - img[..., 0]
+    img[..., 2:] = rng.integers(1, 256, size=(h, w, 2))
+    return mip_chain_rgba8(img, mips)
+
+
+def with_heightmap(mesh, chain, w, h, mips, uv_scale_offset=(1.0, 1.0, 0.0, 0.0), displacement=0.0):
+    """A grid / card / box mesh (vertices float32 [V, >= 11], indices) with the height map of its material attached: the dict tests/displace_ref.py reads and
+    capi.DisplaceJob is filled from — vertices, indices, heightmap = dict(chain | None for the null SRV, w, h, mips), scale_offset, displacement."""
+    v, idx = mesh
+    return {"vertices": np.ascontiguousarray(v, dtype=F), "indices": np.asarray(idx, dtype=np.int64),
+            "heightmap": {"chain": None if chain is None else np.ascontiguousarray(chain, dtype=np.uint8), "w": int(w), "h": int(h), "mips": int(mips)},
+            "scale_offset": tuple(float(x) for x in uv_scale_offset), "displacement": float(displacement)}
