@@ -358,7 +358,8 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * vqhip_scene_masked_depth, vqhip_shadow_masked_depth (+ _work_bytes), vqhip_scene_masked_depth_draw, vqhip_shadow_masked_draw / _view;
                                * vqhip_scene_quad_interpolants and the three _quad producers, vqhip_scene_quad_targets;
                                * vqhip_object_ids (+ _work_bytes), vqhip_object_id_draw; vqhip_outline (+ _work_bytes), VQ_OutlineData, vqhip_outline_draw / _targets;
-                               * vqhip_displace_meshes, vqhip_displace_job, VQHIP_DISPLACE_MAX_JOBS */
+                               * vqhip_displace_meshes, vqhip_displace_job, VQHIP_DISPLACE_MAX_JOBS;
+                               * vqhip_unlit_draws (+ _work_bytes), VQ_UnlitData, vqhip_unlit_draw / _targets, VQHIP_UNLIT_QUEUE_CAPACITY */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -692,8 +693,9 @@ VQHIP_API int vqhip_skydome(vqhip_ctx* ctx, void* stream, const void* equirect_l
         void* color, int width, int height, int row_pitch_px, vqhip_format fmt);
 
 /* Light gizmo meshes — the other half of SURVEY.md §8(f).2 — are drawn by the reference with Unlit.hlsl (SceneRendering.cpp:1787-1819):
- * VSMain transforms the mesh, PSMain (:58-61) returns the light's colour for every covered, depth-tested pixel. Rasterisation stays
- * with the engine; what crosses the boundary is its result, in the same plane the skydome reads: a pixel whose ip2.w index is
+ * VSMain transforms the mesh, PSMain (:58-61) returns the light's colour for every covered, depth-tested pixel. The rasterised route is
+ * vqhip_unlit_draws (below: meshes in, depth-tested colour out, opaque or blended). This call is the route for an engine that rasterises
+ * the gizmos itself; what crosses the boundary is then the result, in the same plane the skydome reads: a pixel whose ip2.w index is
  * -(2+k) is covered by gizmo k (index -1 = sky, >= 0 = material). Those pixels receive colors[k] (all four channels, as PSMain
  * returns float4(color)); every other pixel is left untouched. colors is a HOST array of numColors <= VQHIP_MAX_UNLIT_COLORS entries
  * (FFrameConstantBufferUnlit::color of each FLightRenderData, SceneRendering.cpp:1799). */
@@ -759,7 +761,7 @@ VQHIP_API int vqhip_apply_reflections(vqhip_ctx* ctx, void* stream, const void* 
 /* Replaces VQRenderer::CompositeReflections (SceneRendering.cpp:2362-2403): ApplyReflectionsPass in the permutation its parameters select
  * (ApplyReflections.cpp:62-68). boundingVolumes == NULL: vqhip_apply_reflections. Otherwise "[PSO] ApplyReflectionsAndBoundingVolumes"
  * (COMPOSITE_BOUNDING_VOLUMES, ApplyReflections.hlsl:44-48): Tex_SceneColorBoundingVolumes (the light-bounds target of RenderLightBounds,
- * same format as the scene colour) is blended over the sum,
+ * same format as the scene colour; produced by vqhip_unlit_draws in opaque mode over a zero-cleared plane, vqhip::UnlitDrawsPass::LightBounds) is blended over the sum,
  *     rgb = BV.rgb * BV.a + (scene.rgb + reflection.rgb) * (1 - BV.a),   alpha = BV.a,
  * every product and sum rounded on its own, as written. In place on sceneColor; the inputs must not alias it. fmt: RGBA16F | RGBA32F for all three. */
 VQHIP_API int vqhip_composite_reflections(vqhip_ctx* ctx, void* stream, const void* reflectionRadiance, const void* boundingVolumes, void* sceneColor,
@@ -1493,6 +1495,70 @@ VQHIP_STATIC_ASSERT(sizeof(vqhip_displace_job) == 80 && offsetof(vqhip_displace_
  * height map (measured over numVertices * stride bytes and the whole chain). In-place operation is refused: a second call would displace twice.
  * VQHIP_ERR_UNSUPPORTED for 2^31 or more vertices in one call, or more than VQHIP_DISPLACE_MAX_JOBS jobs with vertices. numJobs == 0 is VQHIP_OK. */
 VQHIP_API int vqhip_displace_meshes(vqhip_ctx* ctx, void* stream, const vqhip_displace_job* jobs, int numJobs);
+
+/* ---- Unlit draws: the light gizmo meshes (SceneRendering.cpp:1787-1819) and the solid half of RenderLightBounds (:1940-1989), both Unlit.hlsl — VSMain: one matrix,
+ * PSMain: one colour per draw — through UNLIT_PSO / UNLIT_BLEND_PSO (PipelineStateObjects.cpp:1174-1232): cull BACK, depth LESS WITHOUT depth writes against the
+ * scene's D32 depth, into the RGBA16F scene colour; UNLIT_BLEND_PSO adds SRC_ALPHA / INV_SRC_ALPHA blending. The light bounds go to scene colour with blending
+ * when reflections are off (:507-510) and to the cleared Tex_SceneColorBoundingVolumes without blending when they are on (:2296-2336: the boundingVolumes plane of
+ * vqhip_composite_reflections). One call, one sample per pixel. docs/DESIGN_DETAILS.md §7.23 is the normative statement (rules U1 .. U7); tests/unlit_ref.py states
+ * it in numpy on top of tests/scene_depth_ref.py:
+ *   U1  vertex: clip[j] = §7.16 R1's mulPoint((x, y + 0.0f, z), matModelViewProj, j). Binary32 whatever vqhip_set_arithmetic says; the host forms
+ *       matWorldTransformation * viewProj, as the reference's CPU code does. A vertex with a non-finite clip component drops its triangle.
+ *   U2  raster: §7.17's V2 (seven planes), V3 (viewport {0, 0, W, H, 0, 1}, 16.8 snap), R4 (int64 edge functions, top-left rule, the sample at the pixel centre)
+ *       and V5 (the fragment's depth), unchanged. One sample per pixel. cullMode per draw (the reference: VQHIP_CULL_BACK).
+ *   U3  depth test: a fragment passes iff its V5 depth is strictly below sceneDepth[pixel] (binary32 compare; a NaN there passes nothing). sceneDepth is never
+ *       written: re-submitting the mesh and matrix that produced sceneDepth writes nothing where that mesh is the visible surface.
+ *   U4  submission order: q = first(draw) + tri, §7.17's sequence number with one instance per draw; the fan pieces of a clipped triangle in fan order.
+ *   U5  blend == 0 (UNLIT_PSO): a pixel with a passing fragment receives the colour of the passing fragment with the largest q, the four channels stored with
+ *       exactly O5's half conversion (round to nearest even; a NaN as 0x7E00 with its sign). Every other pixel keeps its bits.
+ *   U6  blend == 1 (UNLIT_BLEND_PSO): per pixel a fold over the passing fragments in ascending q, starting from the stored halfs decoded exactly:
+ *       ia = 1.0f - a; c' = RN16(RN32(RN32(s.c * a) + RN32(d.c * ia))) for c = r, g, b; a' = RN16(s.a) — rounded to half after EVERY fragment (the render target
+ *       holds halfs between fragments), no FMA contraction. A NaN result stores 0x7E00, sign cleared. Every pixel without a passing fragment keeps its bits.
+ *   U7  writer (optional): the index, into draws, of the last passing fragment's draw; 0xFFFFFFFF where none passed. The call clears it.
+ * U6's blend precision and per-fragment rounding are UNPINNED against a D3D12 device (docs/WARP_CALIBRATION.md §5: D3D bounds them from below only), beside what
+ * §7.17 lists (V2, V5).
+ * Kernels on `stream`: one setup launch per ring slot of draws (fan piece k of triangle q into the FIXED slot 8 q + k, the empty box elsewhere: no counter, memory
+ * order is submission order), one tile fill (every lane owns its pixels in registers; the triangles' boxes, then the slots of those that touch the tile, are scanned
+ * in order and compacted in order into an LDS queue of VQHIP_UNLIT_QUEUE_CAPACITY records, drained front to back whenever it would overflow: the result does not
+ * depend on scheduling), which also clears writer. No
+ * allocation, no memset node, no readback. Draw descriptors are host memory, consumed before the call returns; meshes, constant buffers and planes are device
+ * memory, read when the kernels run. numDraws == 0 leaves sceneColor untouched and clears writer. Option raster_tile 64 is honoured.
+ * Out of scope: the WIREFRAME PSOs (bounding boxes, the second half of RenderLightBounds: D3D's line rasterisation), RenderDebugVertexAxes, 4x MSAA (the library
+ * has no per-sample scene colour, as the Outline pass notes), the instanced cbuffer variant. */
+typedef struct VQ_UnlitData {    /* byte for byte FFrameConstantBufferUnlit, the cbuffer of Unlit.hlsl */
+    VQ_matrix matModelViewProj;
+    VQ_float4 color;
+} VQ_UnlitData;
+typedef struct vqhip_unlit_draw {
+    vqhip_shadow_mesh mesh;      /* position @0; strideBytes >= 12, a multiple of 4 */
+    const VQ_UnlitData* cb;      /* device, 4-byte aligned; read when the kernels run */
+    int32_t cullMode;            /* VQHIP_CULL_* (the reference: VQHIP_CULL_BACK) */
+    int32_t reserved;            /* 0 */
+} vqhip_unlit_draw;
+typedef struct vqhip_unlit_targets {     /* device */
+    void*        sceneColor;     /* RGBA16F [height][pitch], 8-byte aligned: modified IN PLACE, only where a fragment passes */
+    const float* sceneDepth;     /* float [height][depth_pitch], 4-byte aligned: the depth of vqhip_scene_depth at 1 sample; read, never written */
+    uint32_t*    writer;         /* or NULL, 4-byte aligned: U7 */
+    int32_t pitch, depth_pitch, writer_pitch, reserved;   /* pixels per row, 0 = width; reserved 0 */
+} vqhip_unlit_targets;
+VQHIP_STATIC_ASSERT(sizeof(VQ_UnlitData) == 80 && offsetof(VQ_UnlitData, color) == 64, "VQ_UnlitData layout");
+VQHIP_STATIC_ASSERT(sizeof(vqhip_unlit_draw) == 48 && offsetof(vqhip_unlit_draw, cb) == 32 && offsetof(vqhip_unlit_draw, cullMode) == 40, "vqhip_unlit_draw layout");
+VQHIP_STATIC_ASSERT(sizeof(vqhip_unlit_targets) == 40 && offsetof(vqhip_unlit_targets, sceneDepth) == 8 && offsetof(vqhip_unlit_targets, writer) == 16 &&
+                    offsetof(vqhip_unlit_targets, pitch) == 24, "vqhip_unlit_targets layout");
+/* Records the fill's LDS queue holds: a tile touched by more records than this is drained more than once (the result is the same). */
+#define VQHIP_UNLIT_QUEUE_CAPACITY 256
+/* Bytes of work for a call that draws `triangles` triangles (sum over draws of numIndices / 3): 32 bytes per draw of the colour table (sized for
+ * min(triangles, 20 000) draws, at least one), 8 bytes of pixel box and eight slots of 56 bytes per triangle. 0 for 2^28 or more triangles or a size that does
+ * not fit size_t. Host-only. */
+VQHIP_API size_t vqhip_unlit_draws_work_bytes(uint64_t triangles);
+/* Returns VQHIP_ERR_INVALID_ARG — launching nothing, leaving the outputs untouched — for NULL pointers (ctx, out, sceneColor, sceneDepth, work, draws with
+ * numDraws > 0, a mesh's positions or indices, cb), numDraws < 0, width or height outside 1 .. 8192, blend outside 0 / 1, a negative pitch or one below width,
+ * reserved != 0 (targets or a draw), an unknown cullMode, sceneColor not 8-byte aligned, sceneDepth or writer not 4-byte aligned, an indexBits other than 16 / 32,
+ * numIndices % 3 != 0, a stride below 12 or not a multiple of 4, positions or cb not 4-byte aligned, indices not aligned to their size, work not 256-byte
+ * aligned, workBytes below vqhip_unlit_draws_work_bytes of the call's own triangle count, an output overlapping another output or the work buffer, or sceneDepth
+ * overlapping an output or the work buffer; VQHIP_ERR_UNSUPPORTED for more than 20 000 draws with indices or 2^28 or more triangles in one call. */
+VQHIP_API int vqhip_unlit_draws(vqhip_ctx* ctx, void* stream, const vqhip_unlit_draw* draws, int numDraws, int width, int height, int blend,
+        const vqhip_unlit_targets* out, void* work, size_t workBytes);
 
 #ifdef __cplusplus
 }

@@ -1216,4 +1216,70 @@ private:
     std::vector<vqhip_displace_job> mJobs;                                                     // consumed by the call before it returns; kept to spare the allocation
 };
 
+// ---------------------------------------------------------------------------------------------------------------
+// The unlit draws of the lit pass == the "Lights" loop of VQRenderer::RenderSceneColor (SceneRendering.cpp:1787-1819, UNLIT_PSO) and the solid half of
+// VQRenderer::RenderLightBounds (:1940-1989, UNLIT_PSO or UNLIT_BLEND_PSO): vqhip_unlit_draws at one sample per pixel (docs/DESIGN_DETAILS.md §7.23 U1 .. U7).
+// Each FLightRenderData is a vqhip_unlit_draw whose cb is the uploaded FFrameConstantBufferUnlit block (the engine fills it as it does today: color, and
+// matModelViewProj = matWorldTransformation * SceneView.viewProj) and whose cullMode is VQHIP_CULL_BACK. The two fronts fill the parameter block as the two call
+// sites bind their pipeline state:
+//   LightMeshes : opaque, into scene colour.
+//   LightBounds : bReflectionsEnabled — opaque into the cleared Tex_SceneColorBoundingVolumes (the plane vqhip_composite_reflections blends, :2296-2336; the
+//                 caller clears it, as the engine does); otherwise blended straight into scene colour (:507-510).
+// Depth is the scene's (HipDepthPrePass's, one sample), tested LESS and never written. Writer is the library's addition; leave it NULL for the engine's own
+// output. W and H are the window's. The pass owns the work buffer. The wireframe half of RenderLightBounds and the MSAA PSOs are not built (§7.23).
+// ---------------------------------------------------------------------------------------------------------------
+class UnlitDrawsPass : public RenderPassBase {
+public:
+    struct FResourceParameters : public IRenderPassResourceCollection {};
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        const std::vector<vqhip_unlit_draw>* Draws = nullptr;                   // nullptr or empty: nothing to draw — the target stays, Writer is cleared
+        void* Target = nullptr;                                                 // RGBA16F [H][TargetPitch], modified in place: scene colour or the bounding-volumes target
+        int TargetPitch = 0;                                                    // pixels per row, 0 = W
+        const float* SceneDepth = nullptr;                                      // float [H][DepthPitch]
+        int DepthPitch = 0;
+        uint32_t* Writer = nullptr;                                             // optional, [H][W]
+        bool Blend = false;                                                     // UNLIT_BLEND_PSO
+    };
+    struct FTarget { void* Image = nullptr; int Pitch = 0; };                   // an RGBA16F image and its pixels per row (0 = W)
+    // SceneRendering.cpp:1787-1819
+    static FDrawParameters LightMeshes(void* Stream, const std::vector<vqhip_unlit_draw>* Draws, FTarget SceneColor, const float* SceneDepth, int DepthPitch = 0) {
+        FDrawParameters p;
+        p.Stream = Stream; p.Draws = Draws; p.Target = SceneColor.Image; p.TargetPitch = SceneColor.Pitch; p.SceneDepth = SceneDepth; p.DepthPitch = DepthPitch;
+        p.Blend = false;
+        return p;
+    }
+    // SceneRendering.cpp:1940-1989, the solid half
+    static FDrawParameters LightBounds(void* Stream, const std::vector<vqhip_unlit_draw>* Draws, bool bReflectionsEnabled, FTarget SceneColor, FTarget BoundingVolumes,
+                                       const float* SceneDepth, int DepthPitch = 0) {
+        FDrawParameters p;
+        const FTarget& t = bReflectionsEnabled ? BoundingVolumes : SceneColor;
+        p.Stream = Stream; p.Draws = Draws; p.Target = t.Image; p.TargetPitch = t.Pitch; p.SceneDepth = SceneDepth; p.DepthPitch = DepthPitch;
+        p.Blend = !bReflectionsEnabled;
+        return p;
+    }
+    explicit UnlitDrawsPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { mWork.Release(); }
+    void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override { mWidth = Width; mHeight = Height; }
+    void OnDestroyWindowSizeDependentResources() override { mWidth = mHeight = 0; }
+    bool Reserve(uint64_t Triangles) { return mWork.Reserve(vqhip_unlit_draws_work_bytes(Triangles)); }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p || !p->Target || !p->SceneDepth) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        uint64_t triangles = 0;
+        const int numDraws = p->Draws ? (int)p->Draws->size() : 0;
+        for (int d = 0; d < numDraws; ++d) triangles += (*p->Draws)[(size_t)d].mesh.numIndices / 3;
+        if (!Reserve(triangles)) { mStatus = VQHIP_ERR_HIP; return; }
+        vqhip_unlit_targets t = {};
+        t.sceneColor = p->Target; t.pitch = p->TargetPitch; t.sceneDepth = p->SceneDepth; t.depth_pitch = p->DepthPitch; t.writer = p->Writer;
+        mStatus = vqhip_unlit_draws(mCtx, p->Stream, numDraws ? p->Draws->data() : nullptr, numDraws, (int)mWidth, (int)mHeight, p->Blend ? 1 : 0, &t, mWork.ptr, mWork.bytes);
+    }
+    const void* GetWorkBuffer() const { return mWork.ptr; }
+    size_t GetWorkBytes() const { return mWork.bytes; }
+private:
+    WorkBuffer mWork;
+    unsigned mWidth = 0, mHeight = 0;
+};
+
 } // namespace vqhip

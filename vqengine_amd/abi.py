@@ -328,6 +328,24 @@ DISPLACE_MAX_JOBS = 17236                    # VQHIP_DISPLACE_MAX_JOBS: jobs wit
 DISPLACE_POSITION_BYTES = 12                 # outStrideBytes of the compact stream: the displaced position alone
 
 
+class UnlitData(C.Structure):  # VQ_UnlitData == FFrameConstantBufferUnlit, the cbuffer of Unlit.hlsl
+    _fields_ = [("matModelViewProj", matrix), ("color", float4)]
+
+
+class UnlitDraw(C.Structure):  # vqhip_unlit_draw
+    _fields_ = [("mesh", ShadowMesh), ("cb", C.c_void_p), ("cullMode", C.c_int32), ("reserved", C.c_int32)]
+
+
+class UnlitTargets(C.Structure):  # vqhip_unlit_targets
+    _fields_ = [("sceneColor", C.c_void_p), ("sceneDepth", C.c_void_p), ("writer", C.c_void_p), ("pitch", C.c_int32), ("depth_pitch", C.c_int32),
+                ("writer_pitch", C.c_int32), ("reserved", C.c_int32)]
+
+
+UNLIT_DATA_BYTES = 80                        # sizeof(VQ_UnlitData)
+UNLIT_SLOTS_PER_TRIANGLE = 8                 # vqhip_unlit_draws' work buffer: fan piece k of triangle q in the fixed slot 8 q + k, 8 + 48 bytes each
+UNLIT_QUEUE_CAPACITY = 256                   # VQHIP_UNLIT_QUEUE_CAPACITY: records the fill's LDS queue holds between two drains
+
+
 def _chk(t, size, **offs):
     assert C.sizeof(t) == size, (t.__name__, C.sizeof(t), size)
     for k, v in offs.items():
@@ -367,6 +385,9 @@ _chk(ObjectIdDraw, 24, numInstances=4, objID=8, meshID=16, materialID=20)
 _chk(OutlineData, 368, matWorldView=64, matNormalView=128, matProj=192, matViewInverse=256, Color=320, uvScaleBias=336, Scale=352, HeightDisplacement=356)
 _chk(OutlineDraw, 40, cb=32)
 _chk(OutlineTargets, 40, selection=8, writer=16, pitch=24, selection_pitch=28, writer_pitch=32, reserved=36)
+_chk(UnlitData, 80, color=64)
+_chk(UnlitDraw, 48, cb=32, cullMode=40, reserved=44)
+_chk(UnlitTargets, 40, sceneDepth=8, writer=16, pitch=24, depth_pitch=28, writer_pitch=32, reserved=36)
 _chk(DisplaceJob, 80, strideBytes=8, numVertices=12, out=16, outStrideBytes=24, reserved=28, heightmap=32, uvScaleOffset=56, displacement=72)
 _chk(CacaoConstants, 384, EffectRadius=48, InvSharpness=96, PassIndex=100, PatternRotScaleMatrices=112, NormalsUnpackMul=192, SSAOBufferDimensions=208,
      DepthBufferOffset=240, PerPassFullResUVOffset=248, DeinterleavedDepthBufferNormalisedOffset=312, NormalsWorldToViewspaceMatrix=320)

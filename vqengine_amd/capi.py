@@ -132,6 +132,8 @@ def load_library():
         "vqhip_outline_work_bytes": (sz, [C.c_uint64]),
         "vqhip_outline": (i32, [vp, vp, C.POINTER(abi.OutlineDraw), i32, i32, i32, C.POINTER(abi.OutlineTargets), vp, sz]),
         "vqhip_displace_meshes": (i32, [vp, vp, C.POINTER(abi.DisplaceJob), i32]),
+        "vqhip_unlit_draws_work_bytes": (sz, [C.c_uint64]),
+        "vqhip_unlit_draws": (i32, [vp, vp, C.POINTER(abi.UnlitDraw), i32, i32, i32, i32, C.POINTER(abi.UnlitTargets), vp, sz]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -173,6 +175,7 @@ EXPORTED_SYMBOLS = [
     "vqhip_scene_quad_interpolants", "vqhip_gbuffer_from_materials_quad", "vqhip_forward_lighting_from_materials_quad", "vqhip_scene_normals_from_materials_quad",
     "vqhip_object_ids", "vqhip_object_ids_work_bytes", "vqhip_outline", "vqhip_outline_work_bytes",
     "vqhip_displace_meshes",
+    "vqhip_unlit_draws", "vqhip_unlit_draws_work_bytes",
 ]
 
 
@@ -260,6 +263,20 @@ class OutlineDraw:
 
     def __init__(self, vertices, indices, cb):
         self.vertices, self.indices, self.cb = vertices, indices, cb
+
+
+def unlit_draws_work_bytes(triangles):
+    """vqhip_unlit_draws_work_bytes: the work buffer of a vqhip_unlit_draws call that draws `triangles` triangles in all (0: too many). Host-only."""
+    return load_library().vqhip_unlit_draws_work_bytes(int(triangles))
+
+
+class UnlitDraw:
+    """One vqhip_unlit_draw: one mesh with one matrix and one colour. positions: cuda float32 [V, k] with k >= 3 and unit column stride (the row stride is the
+    vertex stride); indices: cuda 1-D int16 / uint16 (read as 16-bit unsigned) or int32, a triangle list; cb: cuda uint8 [80] contiguous or float32 [20], one
+    VQ_UnlitData (unlit_scene.unlit_data builds it); cull: abi.CULL_* (the reference draws with CULL_BACK)."""
+
+    def __init__(self, positions, indices, cb, cull=abi.CULL_BACK):
+        self.positions, self.indices, self.cb, self.cull = positions, indices, cb, int(cull)
 
 
 class DisplaceJob:
@@ -1161,6 +1178,66 @@ class Context:
 
         def call(stream=None, _keep=keep):
             self._ck(self.lib.vqhip_outline(self._h, self._stream(stream), cdraws, len(draws), w, h, C.byref(tg), _ptr(work), work.numel()))
+        return call, res
+
+    def unlit_draws(self, draws, width, height, scene_color, scene_depth, blend=False, writer=True, out=None, work=None, stream=None):
+        """vqhip_unlit_draws: the UnlitDraw list `draws` in submission order, depth-tested (LESS, no writes) against `scene_depth` (cuda float32 [H, W] with unit
+        column stride) and written IN PLACE into `scene_color`: cuda float16 [H, W, 4] with dense pixels (its row stride is the pitch). blend: UNLIT_BLEND_PSO's
+        SRC_ALPHA / INV_SRC_ALPHA fold instead of UNLIT_PSO's overwrite. writer: also return the index of the draw of each pixel's last passing fragment (int32
+        [H, W]; the bits are uint32, -1 = none). out: a dict with a preallocated `writer` tensor (its row stride is the pitch). Returns a dict: scene_color, writer
+        (where asked for), work."""
+        call, res = self.unlit_draws_prepared(draws, width, height, scene_color, scene_depth, blend, writer, out, work)
+        call(stream)
+        return res
+
+    def unlit_draws_prepared(self, draws, width, height, scene_color, scene_depth, blend=False, writer=True, out=None, work=None):
+        """The descriptors of an unlit-draws call built once: returns (call, result) with call(stream=None) issuing vqhip_unlit_draws on the same draws and targets
+        again. The tensors must stay alive and in place."""
+        who_ = "unlit_draws"
+        draws, out = list(draws), dict(out or {})
+        w, h = int(width), int(height)
+        if not (1 <= w <= abi.SCENE_DEPTH_MAX_DIM and 1 <= h <= abi.SCENE_DEPTH_MAX_DIM):
+            raise ValueError(f"{who_}: width and height must be 1..{abi.SCENE_DEPTH_MAX_DIM}")
+        sc, zd = scene_color, scene_depth
+        if not (sc.is_cuda and sc.dtype == torch.float16 and tuple(sc.shape) == (h, w, 4) and sc.stride(2) == 1 and sc.stride(1) == 4 and sc.stride(0) % 4 == 0
+                and sc.stride(0) >= 4 * w):
+            raise ValueError(f"{who_}: scene_color: expected cuda float16 {(h, w, 4)} with dense pixels, got {tuple(sc.shape)} {sc.dtype} strides {sc.stride()}")
+        if not (zd.is_cuda and zd.dtype == torch.float32 and tuple(zd.shape) == (h, w) and zd.stride(1) == 1 and zd.stride(0) >= w):
+            raise ValueError(f"{who_}: scene_depth: expected cuda float32 {(h, w)} with unit column stride, got {tuple(zd.shape)} {zd.dtype} strides {zd.stride()}")
+        res = {"scene_color": sc}
+        if writer:
+            t = out.get("writer")
+            if t is None:
+                t = torch.empty((h, w), dtype=torch.int32, device=self.device)
+            if not (t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (h, w) and t.stride(1) == 1 and t.stride(0) >= w):
+                raise ValueError(f"{who_}: writer: expected cuda int32 {(h, w)} with unit column stride, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+            res["writer"] = t
+        cdraws = (abi.UnlitDraw * max(1, len(draws)))()
+        tris = 0
+        for j, dr in enumerate(draws):
+            who = f"{who_}: draw {j}"
+            p, ix, cb = dr.positions, dr.indices, dr.cb
+            _check_vertices(who, "positions", p, 3)
+            bits = _check_indices(who, ix)
+            if not (cb.is_cuda and cb.is_contiguous() and cb.numel() * cb.element_size() == abi.UNLIT_DATA_BYTES):
+                raise ValueError(f"{who}: cb: expected a contiguous cuda tensor of {abi.UNLIT_DATA_BYTES} bytes (one VQ_UnlitData)")
+            if dr.cull not in (abi.CULL_NONE, abi.CULL_FRONT, abi.CULL_BACK):
+                raise ValueError(f"{who}: cull: expected abi.CULL_NONE, CULL_FRONT or CULL_BACK")
+            c = cdraws[j]
+            _fill_mesh(c, p, ix, bits, empty_indices=p.data_ptr())
+            c.cb, c.cullMode = cb.data_ptr(), dr.cull
+            tris += ix.numel() // 3
+        res["work"] = work = _work_tensor(who_, work, unlit_draws_work_bytes(tris), self.device, " (0: too many triangles)")
+        tg = abi.UnlitTargets()
+        tg.sceneColor, tg.pitch = sc.data_ptr(), sc.stride(0) // 4
+        tg.sceneDepth, tg.depth_pitch = zd.data_ptr(), zd.stride(0)
+        if writer:
+            tg.writer, tg.writer_pitch = res["writer"].data_ptr(), res["writer"].stride(0)
+        keep = (draws, res, zd)
+        mode = 1 if blend else 0
+
+        def call(stream=None, _keep=keep):
+            self._ck(self.lib.vqhip_unlit_draws(self._h, self._stream(stream), cdraws, len(draws), w, h, mode, C.byref(tg), _ptr(work), work.numel()))
         return call, res
 
     def msaa_resolve_surfaces(self, depth_ms, coverage=None, normals=None, normals_fmt=abi.FMT_R10G10B10A2_UNORM, roughness=None, background=None,

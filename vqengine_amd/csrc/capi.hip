@@ -2533,6 +2533,108 @@ int vqhip_outline(vqhip_ctx* ctx, void* stream, const vqhip_outline_draw* draws,
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (w + " fill launch").c_str());
 }
 
+// ---- Unlit draws (raster_unlit.hip; docs/DESIGN_DETAILS.md §7.23 U1 .. U7) -------------------------------------------------------------------------------------------
+static_assert(slotsFor<UnlitJob>(kRasterMaxDraws) < vqhip_ctx::kSlots, "one call never laps the ring");
+static constexpr uint64_t kUnlitMaxTriangles = (uint64_t)1 << 28;     // eight slots each: a slot number is 32 bits wide
+// UnlitColor[min(triangles, max draws), at least 1] | triangle boxes[n] | boxes[8 n] | records[8 n]; false above the limit or when the sizes do not fit
+static bool unlitLayout(uint64_t triangles, size_t* colorCap, size_t* triBoxes, size_t* boxes, size_t* records, size_t* total) {
+    if (triangles >= kUnlitMaxTriangles) return false;
+    const uint64_t cap = triangles * kUnlitFanMax, nc = triangles < kRasterMaxDraws ? (triangles ? triangles : 1) : kRasterMaxDraws;
+    const uint64_t tb = align256(nc * sizeof(UnlitColor)), b = align256(tb + triangles * kUnlitBoxBytes), r = align256(b + cap * kUnlitBoxBytes),
+                   t = align256(r + cap * kUnlitRecordBytes);
+    if (t > (uint64_t)SIZE_MAX) return false;
+    *colorCap = (size_t)nc; *triBoxes = (size_t)tb; *boxes = (size_t)b; *records = (size_t)r; *total = (size_t)t;
+    return true;
+}
+
+size_t vqhip_unlit_draws_work_bytes(uint64_t triangles) {
+    size_t nc, tb, b, r, t;
+    return unlitLayout(triangles, &nc, &tb, &b, &r, &t) ? t : 0;
+}
+
+int vqhip_unlit_draws(vqhip_ctx* ctx, void* stream, const vqhip_unlit_draw* draws, int numDraws, int width, int height, int blend,
+                      const vqhip_unlit_targets* out, void* work, size_t workBytes) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "unlit_draws: ctx is NULL");
+    CTX_GUARD(ctx, "unlit_draws");
+    vqk::Range range_("RenderUnlitDraws");
+    const std::string w = "unlit_draws";
+    auto bad = [&](const std::string& m) { return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": " + m); };
+    if (!out || !out->sceneColor || !out->sceneDepth || !work) return bad("NULL argument (out, out->sceneColor, out->sceneDepth or work)");
+    if (numDraws < 0 || (numDraws > 0 && !draws)) return bad("numDraws < 0, or draws is NULL");
+    if (width < 1 || width > VQHIP_SCENE_DEPTH_MAX_DIM || height < 1 || height > VQHIP_SCENE_DEPTH_MAX_DIM) return bad("width and height must be 1..8192");
+    if (blend != 0 && blend != 1) return bad("blend must be 0 or 1");
+    if (out->reserved != 0) return bad("reserved must be 0");
+    if (out->pitch < 0 || out->depth_pitch < 0 || out->writer_pitch < 0) return bad("negative pitch");
+    const size_t pitch = out->pitch ? (size_t)out->pitch : (size_t)width, zPitch = out->depth_pitch ? (size_t)out->depth_pitch : (size_t)width;
+    const size_t wrPitch = out->writer_pitch ? (size_t)out->writer_pitch : (size_t)width;
+    if (pitch < (size_t)width || zPitch < (size_t)width || wrPitch < (size_t)width) return bad("a pitch below width");
+    if ((uintptr_t)out->sceneColor % 8) return bad("sceneColor is not 8-byte aligned");
+    if ((uintptr_t)out->sceneDepth % 4) return bad("sceneDepth must be 4-byte aligned");
+    if ((uintptr_t)out->writer % 4) return bad("writer must be 4-byte aligned");
+    if ((uintptr_t)work % 256) return bad("work must be 256-byte aligned");
+    uint64_t totalTris = 0;
+    size_t numJobs = 0;
+    for (int d = 0; d < numDraws; ++d) {
+        const vqhip_unlit_draw& D = draws[d];
+        auto badDraw = [&](const std::string& m) { return bad("draw " + std::to_string(d) + ": " + m); };
+        if (!D.mesh.positions || !D.mesh.indices || !D.cb) return badDraw("positions, indices or cb is NULL");
+        if (const std::string m = badMeshDraw(D.mesh, 1, 12, 1); !m.empty()) return badDraw(m);
+        if (D.cullMode != VQHIP_CULL_NONE && D.cullMode != VQHIP_CULL_FRONT && D.cullMode != VQHIP_CULL_BACK) return badDraw("unknown cullMode");
+        if (D.reserved != 0) return badDraw("reserved must be 0");
+        if ((uintptr_t)D.mesh.positions % 4 || (uintptr_t)D.cb % 4 || (uintptr_t)D.mesh.indices % (D.mesh.indexBits / 8))
+            return badDraw("positions / cb must be 4-byte aligned, indices aligned to their size");
+        if (D.mesh.numIndices) { totalTris += D.mesh.numIndices / 3; ++numJobs; }
+    }
+    if (totalTris >= kUnlitMaxTriangles) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": 2^28 or more triangles in one call");
+    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": more than 20000 draws in one call");
+    size_t colorCap, offTriBoxes, offBoxes, offRecords, need;
+    if (!unlitLayout(totalTris, &colorCap, &offTriBoxes, &offBoxes, &offRecords, &need) || workBytes < need)
+        return bad("workBytes below vqhip_unlit_draws_work_bytes(the call's triangles)");
+    const void* const planes[3] = { out->sceneColor, out->writer, out->sceneDepth };        // the input last: it must not overlap an output either
+    const size_t bytes[3] = { planeExtent(width, height, pitch, 8), planeExtent(width, height, wrPitch, 4), planeExtent(width, height, zPitch, 4) };
+    for (int k = 0; k < 3; ++k) {
+        if (!planes[k]) continue;
+        if (rangesOverlap(work, need, planes[k], bytes[k])) return bad(k == 2 ? "sceneDepth overlaps the work buffer" : "an output overlaps the work buffer");
+        for (int m = 0; m < k; ++m)
+            if (planes[m] && rangesOverlap(planes[m], bytes[m], planes[k], bytes[k])) return bad(k == 2 ? "sceneDepth overlaps an output" : "an output overlaps another output");
+    }
+
+    UnlitArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.sceneColor = out->sceneColor; a.sceneDepth = out->sceneDepth; a.writer = out->writer;
+    a.colors = (UnlitColor*)work; a.colorCap = (uint32_t)colorCap;
+    a.slots = (uint32_t)(totalTris * kUnlitFanMax); a.pitch = (uint32_t)pitch; a.depthPitch = (uint32_t)zPitch; a.writerPitch = (uint32_t)wrPitch;
+    a.width = width; a.height = height; a.blend = blend;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    void* triBoxes = (char*)work + offTriBoxes;
+    void* boxes = (char*)work + offBoxes;
+    void* records = (char*)work + offRecords;
+    // the draws that have indices, in ring slots of UnlitJobs: one setup launch per slot
+    int d = 0;
+    uint64_t blocks = 0, firstQ = 0;
+    auto fill = [&](UnlitJob& J, size_t k) {
+        if (!k) blocks = 0;
+        while (!draws[d].mesh.numIndices) ++d;
+        const vqhip_unlit_draw& D = draws[d];
+        std::memset(&J, 0, sizeof(J));
+        J.positions = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices; J.cb = D.cb;
+        J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numTris = D.mesh.numIndices / 3; J.indexBits = D.mesh.indexBits;
+        J.firstBlock = (uint32_t)blocks; J.drawIndex = (uint32_t)d; J.firstQ = (uint32_t)firstQ; J.cullMode = D.cullMode;
+        blocks += ((uint64_t)J.numTris + 255) / 256;
+        firstQ += J.numTris;
+        ++d;
+    };
+    auto setup = [&](const UnlitJob* jobs, size_t n, size_t first) {
+        hipError_t le = launch_unlit_setup(st, jobs, (int)n, (uint32_t)first, (uint32_t)blocks, a, triBoxes, boxes, records);
+        return le == hipSuccess ? VQHIP_OK : failHip(ctx, le, (w + " setup launch").c_str());
+    };
+    if (int rc = stageJobs<UnlitJob>(ctx, st, numJobs, fill, setup)) return rc;
+    if (!a.slots && !a.writer) return VQHIP_OK;                     // no fragment, no plane to clear
+    hipError_t e = launch_unlit_fill(st, a, ctx->opt.rasterTile == 64 ? 64 : 32, triBoxes, boxes, records);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (w + " fill launch").c_str());
+}
+
 // ---- Heightmap displacement of vertex streams (displace.hip; docs/DESIGN_DETAILS.md §7.22 H1 .. H4) -------------------------------------------------------------------
 static_assert((vqhip_ctx::kSlots - 1) * (kConstSlotBytes / sizeof(DisplaceJob)) == VQHIP_DISPLACE_MAX_JOBS, "VQHIP_DISPLACE_MAX_JOBS is what 31 ring slots hold");
 static_assert(slotsFor<DisplaceJob>(VQHIP_DISPLACE_MAX_JOBS) < vqhip_ctx::kSlots, "one call never laps the ring");

@@ -408,6 +408,35 @@ static_assert(sizeof(DisplaceJob) == 80, "DisplaceJob is five uint4");
 static constexpr int kDisplaceLanes = 256;               // vertices per block
 hipError_t launch_displace(hipStream_t s, const DisplaceJob* jobs, int numJobs, uint32_t blocks);
 
+// Unlit draws (vqhip_unlit_draws, raster_unlit.hip; docs/DESIGN_DETAILS.md §7.23 U1 .. U7). The draw jobs travel in constant-ring slots.
+// Work buffer: UnlitColor[min(triangles, 20 000), at least 1] (one per draw with indices: the four colour floats and the draw's index, written by the setup kernel)
+// | the triangles' pixel boxes (8 B each: the union of the triangle's slot boxes, what a tile looks at first) | the slots' pixel boxes (8 B each) | the slots'
+// records (48 B each: three snapped vertices, three z/w, the job's number). Fan piece k of triangle q (§7.17's sequence number) lives in the FIXED slot 8 q + k; an
+// unused slot, and a triangle without slots, holds the empty box: no append counter, and memory order is submission order.
+struct alignas(16) UnlitJob {        // one vqhip_unlit_draw
+    const uint8_t* positions; const void* indices; const VQ_UnlitData* cb;
+    uint32_t strideBytes, numVertices, numTris;
+    int32_t indexBits;
+    uint32_t firstBlock;             // of this k_unlit_setup launch: ceil(numTris / 256) blocks per job
+    uint32_t drawIndex;              // into the caller's draws
+    uint32_t firstQ;                 // U4: the triangles of the jobs before this one, across ring slots
+    int32_t cullMode;
+    uint32_t pad[2];
+};
+static_assert(sizeof(UnlitJob) == 64, "UnlitJob is four uint4");
+struct alignas(16) UnlitColor { float c[4]; uint32_t drawIndex, pad[3]; };
+struct UnlitArgs {
+    void* sceneColor; const float* sceneDepth; uint32_t* writer;
+    UnlitColor* colors;
+    uint32_t slots;                  // 8 x the call's triangles
+    uint32_t pitch, depthPitch, writerPitch, colorCap;
+    int32_t width, height, blend;
+};
+static constexpr size_t kUnlitBoxBytes = 8, kUnlitRecordBytes = 48, kUnlitFanMax = 8;
+static constexpr uint32_t kUnlitEmptyBox = 0x0000ffffu;  // both words: first pixel 65535 > last pixel 0, beyond any target
+hipError_t launch_unlit_setup(hipStream_t s, const UnlitJob* jobs, int numJobs, uint32_t firstJob, uint32_t blocks, const UnlitArgs& a, void* triBoxes, void* boxes, void* records);
+hipError_t launch_unlit_fill(hipStream_t s, const UnlitArgs& a, int tile, const void* triBoxes, const void* boxes, const void* records);
+
 // launchers (each returns the hipError_t of the launch)
 hipError_t launch_forward_lighting(hipStream_t s, const ShadeArgs& a, bool hasEnv, bool hasCasters, int outFmt, const Options& opt);
 hipError_t launch_blur_x(hipStream_t s, const void* in, void* out, int W, int H, int fmt, const Options& opt);
