@@ -359,7 +359,8 @@ VQHIP_API int  vqhip_set_arithmetic(vqhip_ctx* ctx, vqhip_arithmetic mode);
                                * vqhip_scene_quad_interpolants and the three _quad producers, vqhip_scene_quad_targets;
                                * vqhip_object_ids (+ _work_bytes), vqhip_object_id_draw; vqhip_outline (+ _work_bytes), VQ_OutlineData, vqhip_outline_draw / _targets;
                                * vqhip_displace_meshes, vqhip_displace_job, VQHIP_DISPLACE_MAX_JOBS;
-                               * vqhip_unlit_draws (+ _work_bytes), VQ_UnlitData, vqhip_unlit_draw / _targets, VQHIP_UNLIT_QUEUE_CAPACITY */
+                               * vqhip_unlit_draws (+ _work_bytes), VQ_UnlitData, vqhip_unlit_draw / _targets, VQHIP_UNLIT_QUEUE_CAPACITY;
+                               * vqhip_line_draws (+ _work_bytes), vqhip_line_kind, VQ_VertexAxesData, vqhip_line_draw, VQHIP_LINES_MAX_INSTANCES */
 
 /* Replaces VQRenderer::RenderSceneColor's lit draw loop (SceneRendering.cpp:1619-1785, hot part :1730-1784)
  * == ForwardLighting.hlsl:PSMain :289-380 evaluated for every pixel of the G-buffer.
@@ -1524,7 +1525,8 @@ VQHIP_API int vqhip_displace_meshes(vqhip_ctx* ctx, void* stream, const vqhip_di
  * allocation, no memset node, no readback. Draw descriptors are host memory, consumed before the call returns; meshes, constant buffers and planes are device
  * memory, read when the kernels run. numDraws == 0 leaves sceneColor untouched and clears writer. Option raster_tile 64 is honoured.
  * Out of scope: the WIREFRAME PSOs (bounding boxes, the second half of RenderLightBounds: D3D's line rasterisation), RenderDebugVertexAxes, 4x MSAA (the library
- * has no per-sample scene colour, as the Outline pass notes), the instanced cbuffer variant. */
+ * has no per-sample scene colour, as the Outline pass notes), the instanced cbuffer variant. The first two and the instanced cbuffer are vqhip_line_draws' (below);
+ * 4x MSAA stays out of scope there as well. */
 typedef struct VQ_UnlitData {    /* byte for byte FFrameConstantBufferUnlit, the cbuffer of Unlit.hlsl */
     VQ_matrix matModelViewProj;
     VQ_float4 color;
@@ -1558,6 +1560,76 @@ VQHIP_API size_t vqhip_unlit_draws_work_bytes(uint64_t triangles);
  * aligned, workBytes below vqhip_unlit_draws_work_bytes of the call's own triangle count, an output overlapping another output or the work buffer, or sceneDepth
  * overlapping an output or the work buffer; VQHIP_ERR_UNSUPPORTED for more than 20 000 draws with indices or 2^28 or more triangles in one call. */
 VQHIP_API int vqhip_unlit_draws(vqhip_ctx* ctx, void* stream, const vqhip_unlit_draw* draws, int numDraws, int width, int height, int blend,
+        const vqhip_unlit_targets* out, void* work, size_t workBytes);
+
+/* ---- Line draws: what keeps RenderSceneBoundingVolumes (SceneRendering.cpp:2286-2345) from running inside the library after vqhip_unlit_draws and vqhip_outline —
+ * the WIREFRAME PSOs of Unlit.hlsl (RenderBoundingBoxes, :1853-1922, through the instanced cbuffer, up to 512 boxes per draw; the second half of RenderLightBounds,
+ * :1991-2014, the solid bounds' meshes drawn again as wire) and RenderDebugVertexAxes (:2018-2058, VertexDebug.hlsl: an indexed POINT list whose geometry shader
+ * emits three coloured lines per point). Both are D3D's ALIASED line rasterisation (MultisampleEnable and AntialiasedLineEnable at their defaults,
+ * PipelineStateObjects.cpp:1186, 1234-1258, 1391-1422): depth LESS WITHOUT depth writes against the scene's D32 depth, cull NONE, no blending, into the RGBA16F
+ * scene colour, which is modified IN PLACE (vqhip_unlit_targets, unchanged). One call, one sample per pixel, draws of both kinds in submission order. docs/DESIGN_DETAILS.md §7.24 is the normative statement (rules L1 .. L8);
+ * tests/line_ref.py states it in numpy on top of tests/scene_depth_ref.py:
+ *   L1  wireframe vertex: U1 as it stands — clip[j] = mulPoint((x, y + 0.0f, z), matModelViewProj[instance], j), binary32 whatever vqhip_set_arithmetic says. A
+ *       triangle with an index past numVertices is dropped; a line with a non-finite clip component at either end is dropped.
+ *   L2  wireframe lines: triangle (i0, i1, i2) yields the directed lines i0->i1, i1->i2, i2->i0, in that order. Every line is drawn (a shared edge twice); each is
+ *       clipped as a segment of its own: clipping introduces no edge along a clip plane.
+ *   L3  vertex axes: one point per INDEX in index order (an index past numVertices drops its three lines). tbn0 = normalize(T), tbn1 = normalize(cross(N, T)),
+ *       tbn2 = normalize(N); P = mul(matWorld, float4(p, 1)).xyz; O_k = normalize(mul(matNormal, float4(tbn_k, 0)).xyz) * LocalAxisSize; the line k runs from
+ *       mul(matViewProj, float4(P, 1)) to mul(matViewProj, float4(P + O_k, 1)). Binary32, every product and sum rounded in the written order (mulPoint's
+ *       association), the contract's as-written normalize. Colours in emission order: tangent (0.6, 0, 0), cross(N, T) (0, 0, 0.6) — BLUE —, normal (0, 0.6, 0),
+ *       alpha 1. No + 0.0f, no heightmap. A line with a non-finite end is dropped on its own.
+ *   L4  the segment is clipped against V2's seven planes, from the inside end towards the outside end, the direction kept; V3's viewport {0, 0, W, H, 0, 1} and
+ *       16.8 snap; z_i = clip_i.z / clip_i.w of the two post-clip ends.
+ *   L5  coverage, the diamond-exit rule, in integers on the snapped ends: x-major when |dx| >= |dy|, else y-major. Pixel (i, j) has the diamond
+ *       |x - cx| + |y - cy| < 128 around (256 i + 128, 256 j + 128), plus its lower-left edge, lower-right edge and bottom corner (y grows downwards), plus — for
+ *       y-major lines — its right corner. Covered iff the closed segment meets that set and the segment's END point is not in it. Zero length covers nothing.
+ *   L6  depth: with m the major axis and c the pixel centre on it, t = saturate((float)(c - m_0) / (float)(m_1 - m_0)), d = saturate(z_0 + t * (z_1 - z_0));
+ *       the fragment passes iff d is strictly below sceneDepth[pixel] (binary32; a NaN there passes nothing). sceneDepth is never written.
+ *   L7  order and colour: wireframe q = 3 * (first(draw) + instance * numTris + tri) + edge, axes q = first + 3 * point + axis, draws in submission order across
+ *       both kinds. A pixel with a passing fragment receives the colour of the passing fragment with the largest q, stored with O5's half conversion (a NaN as
+ *       0x7E00 with its sign). Every other pixel keeps its bits. No blending.
+ *   L8  writer (optional): as U7 — the index, into draws, of that fragment's draw; 0xFFFFFFFF where none passed. The call clears it.
+ * L5 (the maintainers' reading of the diamond-exit rule), L2's edge order and clipping, and L6's interpolation precision are UNPINNED against a D3D12 device
+ * (docs/WARP_CALIBRATION.md §5), beside what §7.17 lists (V2).
+ * Kernels on `stream`: one setup launch per ring slot of draws (k_lines_setup: line q into the FIXED slot q, the empty box for a dropped line: no counter), one tile
+ * fill (k_lines_fill: one LDS word per pixel, atomicMax of q + 1: the result does not depend on scheduling), which also clears writer. No allocation, no memset
+ * node, no readback. Draw descriptors are host memory, consumed before the call returns; meshes, matrices, colours, constant buffers and planes are device memory,
+ * read when the kernels run. numDraws == 0 leaves sceneColor untouched and clears writer. Option raster_tile 64 is honoured.
+ * Out of scope: 4x MSAA (the library has no per-sample scene colour), the FillMode WIREFRAME permutations of the lit, depth and ObjectID PSOs, antialiased or
+ * quadrilateral lines. */
+typedef enum { VQHIP_LINES_WIREFRAME = 0, VQHIP_LINES_VERTEX_AXES = 1 } vqhip_line_kind;
+typedef struct VQ_VertexAxesData {   /* byte for byte FObjectConstantBufferDebugVertexVectors, the cbuffer of VertexDebug.hlsl */
+    VQ_matrix matWorld, matNormal, matViewProj;
+    float LocalAxisSize;
+    float pad_[3];
+} VQ_VertexAxesData;
+typedef struct vqhip_line_draw {
+    vqhip_shadow_mesh mesh;            /* WIREFRAME: position @0, stride >= 12, numIndices % 3 == 0; VERTEX_AXES: position @0, normal @12, tangent @24, stride >= 36, any numIndices */
+    const VQ_matrix* matModelViewProj; /* WIREFRAME: device, [numInstances] — &VQ_UnlitData.matModelViewProj or the instanced cbuffer's array; else NULL */
+    const VQ_float4* color;            /* WIREFRAME: device — the cbuffer's colour (offset 64, or 512 * 64 in the instanced cbuffer); else NULL */
+    const VQ_VertexAxesData* axes;     /* VERTEX_AXES: device; else NULL */
+    uint32_t numInstances;             /* WIREFRAME: 1 .. 512 (MAX_INSTANCE_COUNT__UNLIT_SHADER); VERTEX_AXES: 1 */
+    int32_t  kind;                     /* vqhip_line_kind */
+} vqhip_line_draw;
+VQHIP_STATIC_ASSERT(sizeof(VQ_VertexAxesData) == 208 && offsetof(VQ_VertexAxesData, matNormal) == 64 && offsetof(VQ_VertexAxesData, matViewProj) == 128 &&
+                    offsetof(VQ_VertexAxesData, LocalAxisSize) == 192, "VQ_VertexAxesData layout");
+VQHIP_STATIC_ASSERT(sizeof(vqhip_line_draw) == 64 && offsetof(vqhip_line_draw, matModelViewProj) == 32 && offsetof(vqhip_line_draw, color) == 40 &&
+                    offsetof(vqhip_line_draw, axes) == 48 && offsetof(vqhip_line_draw, numInstances) == 56 && offsetof(vqhip_line_draw, kind) == 60,
+                    "vqhip_line_draw layout");
+#define VQHIP_LINES_MAX_INSTANCES 512    /* MAX_INSTANCE_COUNT__UNLIT_SHADER */
+/* Bytes of work for a call that draws `lines` lines (sum over draws of numIndices * numInstances for WIREFRAME, 3 * numIndices for VERTEX_AXES): 64 bytes per draw
+ * of the colour table (sized for min(lines, 20 000) draws, at least one), 8 bytes of pixel box and 32 bytes of record per line. 0 for 2^31 or more lines or a size
+ * that does not fit size_t. Host-only. */
+VQHIP_API size_t vqhip_line_draws_work_bytes(uint64_t lines);
+/* Returns VQHIP_ERR_INVALID_ARG — launching nothing, leaving the outputs untouched — for NULL pointers (ctx, out, sceneColor, sceneDepth, work, draws with
+ * numDraws > 0, a mesh's positions or indices), numDraws < 0, width or height outside 1 .. 8192, a negative pitch or one below width, reserved != 0 (targets), an
+ * unknown kind, pointers that do not fit the kind (WIREFRAME: matModelViewProj and color set, axes NULL; VERTEX_AXES: axes set, the other two NULL), numInstances
+ * outside 1 .. 512 (WIREFRAME) or other than 1 (VERTEX_AXES), sceneColor not 8-byte aligned, sceneDepth or writer not 4-byte aligned, an indexBits other than
+ * 16 / 32, numIndices % 3 != 0 (WIREFRAME), a stride below 12 (WIREFRAME) or 36 (VERTEX_AXES) or not a multiple of 4, positions, matrices, colour or axes not
+ * 4-byte aligned, indices not aligned to their size, work not 256-byte aligned, workBytes below vqhip_line_draws_work_bytes of the call's own line count, an output
+ * overlapping another output or the work buffer, or sceneDepth overlapping an output or the work buffer; VQHIP_ERR_UNSUPPORTED for more than 20 000 draws with
+ * indices or 2^31 or more lines in one call. */
+VQHIP_API int vqhip_line_draws(vqhip_ctx* ctx, void* stream, const vqhip_line_draw* draws, int numDraws, int width, int height,
         const vqhip_unlit_targets* out, void* work, size_t workBytes);
 
 #ifdef __cplusplus

@@ -1226,7 +1226,8 @@ private:
 //   LightBounds : bReflectionsEnabled — opaque into the cleared Tex_SceneColorBoundingVolumes (the plane vqhip_composite_reflections blends, :2296-2336; the
 //                 caller clears it, as the engine does); otherwise blended straight into scene colour (:507-510).
 // Depth is the scene's (HipDepthPrePass's, one sample), tested LESS and never written. Writer is the library's addition; leave it NULL for the engine's own
-// output. W and H are the window's. The pass owns the work buffer. The wireframe half of RenderLightBounds and the MSAA PSOs are not built (§7.23).
+// output. W and H are the window's. The pass owns the work buffer. The wireframe half of RenderLightBounds is WireframePass::LightBounds
+// (below); the MSAA PSOs are not built (§7.23).
 // ---------------------------------------------------------------------------------------------------------------
 class UnlitDrawsPass : public RenderPassBase {
 public:
@@ -1280,6 +1281,109 @@ public:
 private:
     WorkBuffer mWork;
     unsigned mWidth = 0, mHeight = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// The line draws of VQRenderer::RenderSceneBoundingVolumes (SceneRendering.cpp:2286-2345): vqhip_line_draws at one sample per pixel (docs/DESIGN_DETAILS.md §7.24
+// L1 .. L8). LineDrawsPass is what the two passes below share: the parameter block, the line count for the work size, the work buffer, the call. The target is
+// the cleared Tex_SceneColorBoundingVolumes when reflections are on (the plane vqhip_composite_reflections blends) and scene colour when they are off (:507-511,
+// :734-735); depth is the scene's (HipDepthPrePass's, one sample), tested LESS and never written; no blending. Writer is the library's addition. W and H are the
+// window's. The MSAA PSOs are not built (§7.24).
+// ---------------------------------------------------------------------------------------------------------------
+class LineDrawsPass : public RenderPassBase {
+public:
+    struct FResourceParameters : public IRenderPassResourceCollection {};
+    struct FDrawParameters : public IRenderPassDrawParameters {
+        void* Stream = nullptr;
+        const std::vector<vqhip_line_draw>* Draws = nullptr;                    // nullptr or empty: nothing to draw — the target stays, Writer is cleared
+        void* Target = nullptr;                                                 // RGBA16F [H][TargetPitch], modified in place: scene colour or the bounding-volumes target
+        int TargetPitch = 0;                                                    // pixels per row, 0 = W
+        const float* SceneDepth = nullptr;                                      // float [H][DepthPitch]
+        int DepthPitch = 0;
+        uint32_t* Writer = nullptr;                                             // optional, [H][W]
+    };
+    struct FTarget { void* Image = nullptr; int Pitch = 0; };                   // an RGBA16F image and its pixels per row (0 = W)
+    static uint64_t Lines(const vqhip_line_draw& d) {
+        return d.kind == VQHIP_LINES_WIREFRAME ? (uint64_t)d.mesh.numIndices * d.numInstances : (uint64_t)d.mesh.numIndices * 3;
+    }
+    explicit LineDrawsPass(vqhip_ctx* Ctx) : RenderPassBase(Ctx) {}
+    bool Initialize() override { return mCtx != nullptr; }
+    void Destroy() override { mWork.Release(); }
+    void OnCreateWindowSizeDependentResources(unsigned Width, unsigned Height, const IRenderPassResourceCollection* = nullptr) override { mWidth = Width; mHeight = Height; }
+    void OnDestroyWindowSizeDependentResources() override { mWidth = mHeight = 0; }
+    bool Reserve(uint64_t NumLines) { return mWork.Reserve(vqhip_line_draws_work_bytes(NumLines)); }
+    void RecordCommands(const IRenderPassDrawParameters* pDrawParameters = nullptr) override {
+        const FDrawParameters* p = static_cast<const FDrawParameters*>(pDrawParameters);
+        if (!p || !p->Target || !p->SceneDepth) { mStatus = VQHIP_ERR_INVALID_ARG; return; }
+        uint64_t lines = 0;
+        const int numDraws = p->Draws ? (int)p->Draws->size() : 0;
+        for (int d = 0; d < numDraws; ++d) lines += Lines((*p->Draws)[(size_t)d]);
+        if (!Reserve(lines)) { mStatus = VQHIP_ERR_HIP; return; }
+        vqhip_unlit_targets t = {};
+        t.sceneColor = p->Target; t.pitch = p->TargetPitch; t.sceneDepth = p->SceneDepth; t.depth_pitch = p->DepthPitch; t.writer = p->Writer;
+        mStatus = vqhip_line_draws(mCtx, p->Stream, numDraws ? p->Draws->data() : nullptr, numDraws, (int)mWidth, (int)mHeight, &t, mWork.ptr, mWork.bytes);
+    }
+    const void* GetWorkBuffer() const { return mWork.ptr; }
+    size_t GetWorkBytes() const { return mWork.bytes; }
+protected:
+    static FDrawParameters Fill(void* Stream, const std::vector<vqhip_line_draw>* Draws, bool bReflectionsEnabled, FTarget SceneColor, FTarget BoundingVolumes,
+                                const float* SceneDepth, int DepthPitch) {
+        FDrawParameters p;
+        const FTarget& t = bReflectionsEnabled ? BoundingVolumes : SceneColor;
+        p.Stream = Stream; p.Draws = Draws; p.Target = t.Image; p.TargetPitch = t.Pitch; p.SceneDepth = SceneDepth; p.DepthPitch = DepthPitch;
+        return p;
+    }
+private:
+    WorkBuffer mWork;
+    unsigned mWidth = 0, mHeight = 0;
+};
+
+// The WIREFRAME PSOs == VQRenderer::RenderBoundingBoxes (SceneRendering.cpp:1853-1922: one FInstancedWireframeRenderData is one draw; its cbuffer is the uploaded
+// FFrameConstantBufferUnlitInstanced block, 512 matrices and then the colour) and the second half of VQRenderer::RenderLightBounds (:1991-2014: one FLightRenderData
+// is one draw; its cbuffer is the uploaded FFrameConstantBufferUnlit block — the colour's alpha is NOT scaled by 0.01 in this loop).
+class WireframePass : public LineDrawsPass {
+public:
+    // one batch of boxes: the cube, the instanced cbuffer on the device, the number of boxes in it (1 .. VQHIP_LINES_MAX_INSTANCES)
+    static vqhip_line_draw Box(const vqhip_shadow_mesh& Cube, const void* InstancedCBuffer, uint32_t NumInstances) {
+        vqhip_line_draw d = {};
+        d.mesh = Cube; d.matModelViewProj = static_cast<const VQ_matrix*>(InstancedCBuffer);
+        d.color = reinterpret_cast<const VQ_float4*>(static_cast<const VQ_matrix*>(InstancedCBuffer) + VQHIP_LINES_MAX_INSTANCES);
+        d.numInstances = NumInstances; d.kind = VQHIP_LINES_WIREFRAME;
+        return d;
+    }
+    // one light volume: the mesh and the cbuffer the solid half drew it with (a copy whose alpha is the render data's own)
+    static vqhip_line_draw Bound(const vqhip_shadow_mesh& Mesh, const VQ_UnlitData* CBuffer) {
+        vqhip_line_draw d = {};
+        d.mesh = Mesh; d.matModelViewProj = &CBuffer->matModelViewProj; d.color = &CBuffer->color; d.numInstances = 1; d.kind = VQHIP_LINES_WIREFRAME;
+        return d;
+    }
+    // SceneRendering.cpp:1853-1922
+    static FDrawParameters BoundingBoxes(void* Stream, const std::vector<vqhip_line_draw>* Draws, bool bReflectionsEnabled, FTarget SceneColor, FTarget BoundingVolumes,
+                                         const float* SceneDepth, int DepthPitch = 0) {
+        return Fill(Stream, Draws, bReflectionsEnabled, SceneColor, BoundingVolumes, SceneDepth, DepthPitch);
+    }
+    // SceneRendering.cpp:1991-2014, the wire half
+    static FDrawParameters LightBounds(void* Stream, const std::vector<vqhip_line_draw>* Draws, bool bReflectionsEnabled, FTarget SceneColor, FTarget BoundingVolumes,
+                                       const float* SceneDepth, int DepthPitch = 0) {
+        return Fill(Stream, Draws, bReflectionsEnabled, SceneColor, BoundingVolumes, SceneDepth, DepthPitch);
+    }
+    explicit WireframePass(vqhip_ctx* Ctx) : LineDrawsPass(Ctx) {}
+};
+
+// VQRenderer::RenderDebugVertexAxes (SceneRendering.cpp:2018-2058, DEBUGVERTEX_LOCALSPACEVECTORS_PSO): one MeshRenderData_t is one draw — the mesh's vertex buffer
+// (position, normal, tangent at bytes 0, 12, 24) and index buffer as a POINT list, and the uploaded FObjectConstantBufferDebugVertexVectors block.
+class VertexAxesPass : public LineDrawsPass {
+public:
+    static vqhip_line_draw Mesh(const vqhip_shadow_mesh& Mesh, const VQ_VertexAxesData* CBuffer) {
+        vqhip_line_draw d = {};
+        d.mesh = Mesh; d.axes = CBuffer; d.numInstances = 1; d.kind = VQHIP_LINES_VERTEX_AXES;
+        return d;
+    }
+    static FDrawParameters VertexAxes(void* Stream, const std::vector<vqhip_line_draw>* Draws, bool bReflectionsEnabled, FTarget SceneColor, FTarget BoundingVolumes,
+                                      const float* SceneDepth, int DepthPitch = 0) {
+        return Fill(Stream, Draws, bReflectionsEnabled, SceneColor, BoundingVolumes, SceneDepth, DepthPitch);
+    }
+    explicit VertexAxesPass(vqhip_ctx* Ctx) : LineDrawsPass(Ctx) {}
 };
 
 } // namespace vqhip

@@ -341,6 +341,18 @@ class UnlitTargets(C.Structure):  # vqhip_unlit_targets
                 ("writer_pitch", C.c_int32), ("reserved", C.c_int32)]
 
 
+class VertexAxesData(C.Structure):  # VQ_VertexAxesData == FObjectConstantBufferDebugVertexVectors, the cbuffer of VertexDebug.hlsl
+    _fields_ = [("matWorld", matrix), ("matNormal", matrix), ("matViewProj", matrix), ("LocalAxisSize", C.c_float), ("pad_", C.c_float * 3)]
+
+
+class LineDraw(C.Structure):  # vqhip_line_draw
+    _fields_ = [("mesh", ShadowMesh), ("matModelViewProj", C.c_void_p), ("color", C.c_void_p), ("axes", C.c_void_p), ("numInstances", C.c_uint32), ("kind", C.c_int32)]
+
+
+LINES_WIREFRAME, LINES_VERTEX_AXES = 0, 1    # vqhip_line_kind
+LINES_MAX_INSTANCES = 512                    # VQHIP_LINES_MAX_INSTANCES == MAX_INSTANCE_COUNT__UNLIT_SHADER
+VERTEX_AXES_DATA_BYTES = 208                 # sizeof(VQ_VertexAxesData)
+LINE_BYTES = 8 + 32                          # vqhip_line_draws' work buffer: line q in the fixed slot q, a pixel box and a record
 UNLIT_DATA_BYTES = 80                        # sizeof(VQ_UnlitData)
 UNLIT_SLOTS_PER_TRIANGLE = 8                 # vqhip_unlit_draws' work buffer: fan piece k of triangle q in the fixed slot 8 q + k, 8 + 48 bytes each
 UNLIT_QUEUE_CAPACITY = 256                   # VQHIP_UNLIT_QUEUE_CAPACITY: records the fill's LDS queue holds between two drains
@@ -388,6 +400,8 @@ _chk(OutlineTargets, 40, selection=8, writer=16, pitch=24, selection_pitch=28, w
 _chk(UnlitData, 80, color=64)
 _chk(UnlitDraw, 48, cb=32, cullMode=40, reserved=44)
 _chk(UnlitTargets, 40, sceneDepth=8, writer=16, pitch=24, depth_pitch=28, writer_pitch=32, reserved=36)
+_chk(VertexAxesData, 208, matNormal=64, matViewProj=128, LocalAxisSize=192)
+_chk(LineDraw, 64, matModelViewProj=32, color=40, axes=48, numInstances=56, kind=60)
 _chk(DisplaceJob, 80, strideBytes=8, numVertices=12, out=16, outStrideBytes=24, reserved=28, heightmap=32, uvScaleOffset=56, displacement=72)
 _chk(CacaoConstants, 384, EffectRadius=48, InvSharpness=96, PassIndex=100, PatternRotScaleMatrices=112, NormalsUnpackMul=192, SSAOBufferDimensions=208,
      DepthBufferOffset=240, PerPassFullResUVOffset=248, DeinterleavedDepthBufferNormalisedOffset=312, NormalsWorldToViewspaceMatrix=320)

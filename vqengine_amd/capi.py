@@ -134,6 +134,8 @@ def load_library():
         "vqhip_displace_meshes": (i32, [vp, vp, C.POINTER(abi.DisplaceJob), i32]),
         "vqhip_unlit_draws_work_bytes": (sz, [C.c_uint64]),
         "vqhip_unlit_draws": (i32, [vp, vp, C.POINTER(abi.UnlitDraw), i32, i32, i32, i32, C.POINTER(abi.UnlitTargets), vp, sz]),
+        "vqhip_line_draws_work_bytes": (sz, [C.c_uint64]),
+        "vqhip_line_draws": (i32, [vp, vp, C.POINTER(abi.LineDraw), i32, i32, i32, C.POINTER(abi.UnlitTargets), vp, sz]),
         "vqhip_rowtile": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "vqhip_comm_unique_id": (i32, [vp]),
         "vqhip_comm_create": (i32, [vp, i32, i32, C.POINTER(vp)]),
@@ -176,6 +178,7 @@ EXPORTED_SYMBOLS = [
     "vqhip_object_ids", "vqhip_object_ids_work_bytes", "vqhip_outline", "vqhip_outline_work_bytes",
     "vqhip_displace_meshes",
     "vqhip_unlit_draws", "vqhip_unlit_draws_work_bytes",
+    "vqhip_line_draws", "vqhip_line_draws_work_bytes",
 ]
 
 
@@ -277,6 +280,31 @@ class UnlitDraw:
 
     def __init__(self, positions, indices, cb, cull=abi.CULL_BACK):
         self.positions, self.indices, self.cb, self.cull = positions, indices, cb, int(cull)
+
+
+def line_draws_work_bytes(lines):
+    """vqhip_line_draws_work_bytes: the work buffer of a vqhip_line_draws call that draws `lines` lines in all (0: too many). Host-only."""
+    return load_library().vqhip_line_draws_work_bytes(int(lines))
+
+
+class WireframeDraw:
+    """One vqhip_line_draw of kind WIREFRAME: every edge of every triangle of one mesh, once per instance, in one colour. positions: cuda float32 [V, k] with
+    k >= 3 and unit column stride; indices: cuda 1-D int16 / uint16 (read as 16-bit unsigned) or int32, a triangle list; matrices: cuda float32 [n, 4, 4]
+    contiguous, n = 1 .. 512 (matModelViewProj per instance); color: cuda float32 [4] contiguous."""
+    kind = abi.LINES_WIREFRAME
+
+    def __init__(self, positions, indices, matrices, color):
+        self.positions, self.indices, self.matrices, self.color = positions, indices, matrices, color
+
+
+class VertexAxesDraw:
+    """One vqhip_line_draw of kind VERTEX_AXES: three coloured lines per INDEX of a point list. vertices: cuda float32 [V, k] with k >= 9 and unit column stride
+    (position 3, normal 3, tangent 3); indices: cuda 1-D 16-bit or 32-bit integers, any length; cb: cuda uint8 [208] contiguous or float32 [52], one
+    VQ_VertexAxesData (line_scene.vertex_axes_data builds it)."""
+    kind = abi.LINES_VERTEX_AXES
+
+    def __init__(self, vertices, indices, cb):
+        self.vertices, self.indices, self.cb = vertices, indices, cb
 
 
 class DisplaceJob:
@@ -1238,6 +1266,79 @@ class Context:
 
         def call(stream=None, _keep=keep):
             self._ck(self.lib.vqhip_unlit_draws(self._h, self._stream(stream), cdraws, len(draws), w, h, mode, C.byref(tg), _ptr(work), work.numel()))
+        return call, res
+
+    def line_draws(self, draws, width, height, scene_color, scene_depth, writer=True, out=None, work=None, stream=None):
+        """vqhip_line_draws: the WireframeDraw / VertexAxesDraw list `draws` in submission order as aliased lines, depth-tested (LESS, no writes) against
+        `scene_depth` (cuda float32 [H, W] with unit column stride) and written IN PLACE, without blending, into `scene_color`: cuda float16 [H, W, 4] with dense
+        pixels (its row stride is the pitch). writer: also return the index of the draw of each pixel's winning fragment (int32 [H, W]; the bits are uint32,
+        -1 = none). out: a dict with a preallocated `writer` tensor. Returns a dict: scene_color, writer (where asked for), work."""
+        call, res = self.line_draws_prepared(draws, width, height, scene_color, scene_depth, writer, out, work)
+        call(stream)
+        return res
+
+    def line_draws_prepared(self, draws, width, height, scene_color, scene_depth, writer=True, out=None, work=None):
+        """The descriptors of a line-draws call built once: returns (call, result) with call(stream=None) issuing vqhip_line_draws on the same draws and targets
+        again. The tensors must stay alive and in place."""
+        who_ = "line_draws"
+        draws, out = list(draws), dict(out or {})
+        w, h = int(width), int(height)
+        if not (1 <= w <= abi.SCENE_DEPTH_MAX_DIM and 1 <= h <= abi.SCENE_DEPTH_MAX_DIM):
+            raise ValueError(f"{who_}: width and height must be 1..{abi.SCENE_DEPTH_MAX_DIM}")
+        sc, zd = scene_color, scene_depth
+        if not (sc.is_cuda and sc.dtype == torch.float16 and tuple(sc.shape) == (h, w, 4) and sc.stride(2) == 1 and sc.stride(1) == 4 and sc.stride(0) % 4 == 0
+                and sc.stride(0) >= 4 * w):
+            raise ValueError(f"{who_}: scene_color: expected cuda float16 {(h, w, 4)} with dense pixels, got {tuple(sc.shape)} {sc.dtype} strides {sc.stride()}")
+        if not (zd.is_cuda and zd.dtype == torch.float32 and tuple(zd.shape) == (h, w) and zd.stride(1) == 1 and zd.stride(0) >= w):
+            raise ValueError(f"{who_}: scene_depth: expected cuda float32 {(h, w)} with unit column stride, got {tuple(zd.shape)} {zd.dtype} strides {zd.stride()}")
+        res = {"scene_color": sc}
+        if writer:
+            t = out.get("writer")
+            if t is None:
+                t = torch.empty((h, w), dtype=torch.int32, device=self.device)
+            if not (t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (h, w) and t.stride(1) == 1 and t.stride(0) >= w):
+                raise ValueError(f"{who_}: writer: expected cuda int32 {(h, w)} with unit column stride, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+            res["writer"] = t
+        cdraws = (abi.LineDraw * max(1, len(draws)))()
+        lines = 0
+        for j, dr in enumerate(draws):
+            who = f"{who_}: draw {j}"
+            c = cdraws[j]
+            if getattr(dr, "kind", None) == abi.LINES_WIREFRAME:
+                p, ix = dr.positions, dr.indices
+                _check_vertices(who, "positions", p, 3)
+                bits = _check_indices(who, ix)
+                n = _check_matrix_blocks(who, (("matrices", dr.matrices, False),))
+                _check_instances_cull(who, n, abi.LINES_MAX_INSTANCES)
+                col = dr.color
+                if not (col.is_cuda and col.dtype == torch.float32 and col.numel() == 4 and col.is_contiguous()):
+                    raise ValueError(f"{who}: color: expected cuda float32 [4] contiguous")
+                c.matModelViewProj, c.color, c.numInstances = dr.matrices.data_ptr(), col.data_ptr(), n
+                lines += ix.numel() * n
+            elif getattr(dr, "kind", None) == abi.LINES_VERTEX_AXES:
+                p, ix, cb = dr.vertices, dr.indices, dr.cb
+                _check_vertices(who, "vertices", p, 9)
+                bits = {2: 16, 4: 32}.get(ix.element_size()) if not ix.dtype.is_floating_point else None
+                if not (ix.is_cuda and ix.dim() == 1 and ix.is_contiguous() and bits):
+                    raise ValueError(f"{who}: indices: expected a contiguous cuda 1-D 16-bit or 32-bit integer tensor")
+                if not (cb.is_cuda and cb.is_contiguous() and cb.numel() * cb.element_size() == abi.VERTEX_AXES_DATA_BYTES):
+                    raise ValueError(f"{who}: cb: expected a contiguous cuda tensor of {abi.VERTEX_AXES_DATA_BYTES} bytes (one VQ_VertexAxesData)")
+                c.axes, c.numInstances = cb.data_ptr(), 1
+                lines += 3 * ix.numel()
+            else:
+                raise ValueError(f"{who}: expected a WireframeDraw or a VertexAxesDraw")
+            _fill_mesh(c, p, ix, bits, empty_indices=p.data_ptr())
+            c.kind = dr.kind
+        res["work"] = work = _work_tensor(who_, work, line_draws_work_bytes(lines), self.device, " (0: too many lines)")
+        tg = abi.UnlitTargets()
+        tg.sceneColor, tg.pitch = sc.data_ptr(), sc.stride(0) // 4
+        tg.sceneDepth, tg.depth_pitch = zd.data_ptr(), zd.stride(0)
+        if writer:
+            tg.writer, tg.writer_pitch = res["writer"].data_ptr(), res["writer"].stride(0)
+        keep = (draws, res, zd)
+
+        def call(stream=None, _keep=keep):
+            self._ck(self.lib.vqhip_line_draws(self._h, self._stream(stream), cdraws, len(draws), w, h, C.byref(tg), _ptr(work), work.numel()))
         return call, res
 
     def msaa_resolve_surfaces(self, depth_ms, coverage=None, normals=None, normals_fmt=abi.FMT_R10G10B10A2_UNORM, roughness=None, background=None,

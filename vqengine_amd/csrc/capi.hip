@@ -2635,6 +2635,120 @@ int vqhip_unlit_draws(vqhip_ctx* ctx, void* stream, const vqhip_unlit_draw* draw
     return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (w + " fill launch").c_str());
 }
 
+// ---- Line draws (raster_lines.hip; docs/DESIGN_DETAILS.md §7.24 L1 .. L8) --------------------------------------------------------------------------------------------
+static_assert(slotsFor<LineJob>(kRasterMaxDraws) < vqhip_ctx::kSlots, "one call never laps the ring");
+static constexpr uint64_t kLinesMax = (uint64_t)1 << 31;             // the fill's LDS word holds q + 1 in 32 bits, and a block number stays far below 2^31
+// LineColor[4 x min(lines, max draws), at least 4] | boxes[n] | records[n]; false above the limit or when the sizes do not fit
+static bool linesLayout(uint64_t lines, size_t* colorCap, size_t* boxes, size_t* records, size_t* total) {
+    if (lines >= kLinesMax) return false;
+    const uint64_t nc = (lines < kRasterMaxDraws ? (lines ? lines : 1) : kRasterMaxDraws) * kLineColorsPerJob;
+    const uint64_t b = align256(nc * sizeof(LineColor)), r = align256(b + lines * kLineBoxBytes), t = align256(r + lines * kLineRecordBytes);
+    if (t > (uint64_t)SIZE_MAX) return false;
+    *colorCap = (size_t)nc; *boxes = (size_t)b; *records = (size_t)r; *total = (size_t)t;
+    return true;
+}
+
+size_t vqhip_line_draws_work_bytes(uint64_t lines) {
+    size_t nc, b, r, t;
+    return linesLayout(lines, &nc, &b, &r, &t) ? t : 0;
+}
+
+int vqhip_line_draws(vqhip_ctx* ctx, void* stream, const vqhip_line_draw* draws, int numDraws, int width, int height, const vqhip_unlit_targets* out, void* work,
+                     size_t workBytes) {
+    if (!ctx) return fail(nullptr, VQHIP_ERR_INVALID_ARG, "line_draws: ctx is NULL");
+    CTX_GUARD(ctx, "line_draws");
+    vqk::Range range_("RenderLineDraws");
+    const std::string w = "line_draws";
+    auto bad = [&](const std::string& m) { return fail(ctx, VQHIP_ERR_INVALID_ARG, w + ": " + m); };
+    if (!out || !out->sceneColor || !out->sceneDepth || !work) return bad("NULL argument (out, out->sceneColor, out->sceneDepth or work)");
+    if (numDraws < 0 || (numDraws > 0 && !draws)) return bad("numDraws < 0, or draws is NULL");
+    if (width < 1 || width > VQHIP_SCENE_DEPTH_MAX_DIM || height < 1 || height > VQHIP_SCENE_DEPTH_MAX_DIM) return bad("width and height must be 1..8192");
+    if (out->reserved != 0) return bad("reserved must be 0");
+    if (out->pitch < 0 || out->depth_pitch < 0 || out->writer_pitch < 0) return bad("negative pitch");
+    const size_t pitch = out->pitch ? (size_t)out->pitch : (size_t)width, zPitch = out->depth_pitch ? (size_t)out->depth_pitch : (size_t)width;
+    const size_t wrPitch = out->writer_pitch ? (size_t)out->writer_pitch : (size_t)width;
+    if (pitch < (size_t)width || zPitch < (size_t)width || wrPitch < (size_t)width) return bad("a pitch below width");
+    if ((uintptr_t)out->sceneColor % 8) return bad("sceneColor is not 8-byte aligned");
+    if ((uintptr_t)out->sceneDepth % 4) return bad("sceneDepth must be 4-byte aligned");
+    if ((uintptr_t)out->writer % 4) return bad("writer must be 4-byte aligned");
+    if ((uintptr_t)work % 256) return bad("work must be 256-byte aligned");
+    auto linesOf = [](const vqhip_line_draw& D) {
+        return D.kind == VQHIP_LINES_WIREFRAME ? (uint64_t)D.mesh.numIndices * D.numInstances : (uint64_t)D.mesh.numIndices * 3;
+    };
+    uint64_t totalLines = 0;
+    size_t numJobs = 0;
+    for (int d = 0; d < numDraws; ++d) {
+        const vqhip_line_draw& D = draws[d];
+        auto badDraw = [&](const std::string& m) { return bad("draw " + std::to_string(d) + ": " + m); };
+        if (D.kind != VQHIP_LINES_WIREFRAME && D.kind != VQHIP_LINES_VERTEX_AXES) return badDraw("unknown kind");
+        const bool wire = D.kind == VQHIP_LINES_WIREFRAME;
+        if (!D.mesh.positions || !D.mesh.indices) return badDraw("positions or indices is NULL");
+        if (wire ? (!D.matModelViewProj || !D.color || D.axes) : (!D.axes || D.matModelViewProj || D.color))
+            return badDraw(wire ? "WIREFRAME takes matModelViewProj and color, and axes NULL" : "VERTEX_AXES takes axes, and matModelViewProj and color NULL");
+        if (D.mesh.indexBits != 16 && D.mesh.indexBits != 32) return badDraw("indexBits must be 16 or 32");
+        if (wire) {
+            if (const std::string m = badMeshDraw(D.mesh, D.numInstances, 12, VQHIP_LINES_MAX_INSTANCES); !m.empty()) return badDraw(m);
+        } else {
+            if (D.mesh.strideBytes < 36 || D.mesh.strideBytes % 4) return badDraw("strideBytes below 36 or not a multiple of 4");
+            if (D.numInstances != 1) return badDraw("numInstances must be 1");
+        }
+        if ((uintptr_t)D.mesh.positions % 4 || (uintptr_t)D.matModelViewProj % 4 || (uintptr_t)D.color % 4 || (uintptr_t)D.axes % 4 ||
+            (uintptr_t)D.mesh.indices % (D.mesh.indexBits / 8))
+            return badDraw("positions / matModelViewProj / color / axes must be 4-byte aligned, indices aligned to their size");
+        if (D.mesh.numIndices) { totalLines += linesOf(D); ++numJobs; }
+    }
+    if (totalLines >= kLinesMax) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": 2^31 or more lines in one call");
+    if (numJobs > kRasterMaxDraws) return fail(ctx, VQHIP_ERR_UNSUPPORTED, w + ": more than 20000 draws in one call");
+    size_t colorCap, offBoxes, offRecords, need;
+    if (!linesLayout(totalLines, &colorCap, &offBoxes, &offRecords, &need) || workBytes < need)
+        return bad("workBytes below vqhip_line_draws_work_bytes(the call's lines)");
+    const void* const planes[3] = { out->sceneColor, out->writer, out->sceneDepth };        // the input last: it must not overlap an output either
+    const size_t bytes[3] = { planeExtent(width, height, pitch, 8), planeExtent(width, height, wrPitch, 4), planeExtent(width, height, zPitch, 4) };
+    for (int k = 0; k < 3; ++k) {
+        if (!planes[k]) continue;
+        if (rangesOverlap(work, need, planes[k], bytes[k])) return bad(k == 2 ? "sceneDepth overlaps the work buffer" : "an output overlaps the work buffer");
+        for (int m = 0; m < k; ++m)
+            if (planes[m] && rangesOverlap(planes[m], bytes[m], planes[k], bytes[k])) return bad(k == 2 ? "sceneDepth overlaps an output" : "an output overlaps another output");
+    }
+
+    LineArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.sceneColor = out->sceneColor; a.sceneDepth = out->sceneDepth; a.writer = out->writer;
+    a.colors = (LineColor*)work; a.colorCap = (uint32_t)colorCap;
+    a.lines = (uint32_t)totalLines; a.pitch = (uint32_t)pitch; a.depthPitch = (uint32_t)zPitch; a.writerPitch = (uint32_t)wrPitch;
+    a.width = width; a.height = height;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    void* boxes = (char*)work + offBoxes;
+    void* records = (char*)work + offRecords;
+    // the draws that have indices, in ring slots of LineJobs: one setup launch per slot
+    int d = 0;
+    uint64_t blocks = 0, firstQ = 0;
+    auto fill = [&](LineJob& J, size_t k) {
+        if (!k) blocks = 0;
+        while (!draws[d].mesh.numIndices) ++d;
+        const vqhip_line_draw& D = draws[d];
+        std::memset(&J, 0, sizeof(J));
+        const bool wire = D.kind == VQHIP_LINES_WIREFRAME;
+        J.vertices = (const uint8_t*)D.mesh.positions; J.indices = D.mesh.indices; J.color = D.color;
+        J.cb = wire ? (const void*)D.matModelViewProj : (const void*)D.axes;
+        J.strideBytes = D.mesh.strideBytes; J.numVertices = D.mesh.numVertices; J.numPrims = wire ? D.mesh.numIndices / 3 : D.mesh.numIndices;
+        J.numLines = (uint32_t)linesOf(D); J.indexBits = (uint16_t)D.mesh.indexBits; J.kind = (uint16_t)D.kind;
+        J.firstBlock = (uint32_t)blocks; J.drawIndex = (uint32_t)d; J.firstQ = (uint32_t)firstQ;
+        blocks += ((uint64_t)J.numLines + 255) / 256;
+        firstQ += J.numLines;
+        ++d;
+    };
+    auto setup = [&](const LineJob* jobs, size_t n, size_t first) {
+        hipError_t le = launch_lines_setup(st, jobs, (int)n, (uint32_t)first, (uint32_t)blocks, a, boxes, records);
+        return le == hipSuccess ? VQHIP_OK : failHip(ctx, le, (w + " setup launch").c_str());
+    };
+    if (int rc = stageJobs<LineJob>(ctx, st, numJobs, fill, setup)) return rc;
+    if (!a.lines && !a.writer) return VQHIP_OK;                     // no fragment, no plane to clear
+    hipError_t e = launch_lines_fill(st, a, ctx->opt.rasterTile == 64 ? 64 : 32, boxes, records);
+    return e == hipSuccess ? VQHIP_OK : failHip(ctx, e, (w + " fill launch").c_str());
+}
+
 // ---- Heightmap displacement of vertex streams (displace.hip; docs/DESIGN_DETAILS.md §7.22 H1 .. H4) -------------------------------------------------------------------
 static_assert((vqhip_ctx::kSlots - 1) * (kConstSlotBytes / sizeof(DisplaceJob)) == VQHIP_DISPLACE_MAX_JOBS, "VQHIP_DISPLACE_MAX_JOBS is what 31 ring slots hold");
 static_assert(slotsFor<DisplaceJob>(VQHIP_DISPLACE_MAX_JOBS) < vqhip_ctx::kSlots, "one call never laps the ring");

@@ -437,6 +437,37 @@ static constexpr uint32_t kUnlitEmptyBox = 0x0000ffffu;  // both words: first pi
 hipError_t launch_unlit_setup(hipStream_t s, const UnlitJob* jobs, int numJobs, uint32_t firstJob, uint32_t blocks, const UnlitArgs& a, void* triBoxes, void* boxes, void* records);
 hipError_t launch_unlit_fill(hipStream_t s, const UnlitArgs& a, int tile, const void* triBoxes, const void* boxes, const void* records);
 
+// Line draws (vqhip_line_draws, raster_lines.hip; docs/DESIGN_DETAILS.md §7.24 L1 .. L8). The draw jobs travel in constant-ring slots.
+// Work buffer: LineColor[4 x min(lines, 20 000), at least 4] (four per draw with lines: the wireframe colour, or the three axis colours, as halfs, and the draw's
+// index, written by the setup kernel) | the lines' pixel boxes (8 B each) | the lines' records (32 B each: the snapped ends, the two z / w, the colour-table entry,
+// the major axis). Line q (L7's sequence number) lives in the FIXED slot q; a dropped line holds the empty box: no append counter.
+struct alignas(16) LineJob {         // one vqhip_line_draw
+    const uint8_t* vertices; const void* indices; const VQ_float4* color;
+    const void* cb;                  // WIREFRAME: VQ_matrix[numInstances]; VERTEX_AXES: one VQ_VertexAxesData
+    uint32_t strideBytes, numVertices;
+    uint32_t numPrims;               // WIREFRAME: triangles of one instance; VERTEX_AXES: indices (points)
+    uint32_t numLines;               // WIREFRAME: 3 x numPrims x numInstances; VERTEX_AXES: 3 x numPrims
+    uint16_t indexBits, kind;
+    uint32_t firstBlock;             // of this k_lines_setup launch: ceil(numLines / 256) blocks per job
+    uint32_t drawIndex;              // into the caller's draws
+    uint32_t firstQ;                 // L7: the lines of the jobs before this one, across ring slots
+};
+static_assert(sizeof(LineJob) == 64, "LineJob is four uint4");
+struct alignas(16) LineColor { uint32_t rg, ba, drawIndex, pad; };
+struct LineArgs {
+    void* sceneColor; const float* sceneDepth; uint32_t* writer;
+    LineColor* colors;
+    uint32_t lines;                  // the call's lines: the slots
+    uint32_t pitch, depthPitch, writerPitch;
+    uint32_t colorCap;               // entries of colors: four per job
+    int32_t width, height;
+};
+static constexpr size_t kLineBoxBytes = 8, kLineRecordBytes = 32;
+static constexpr uint32_t kLineColorsPerJob = 4;
+static constexpr uint32_t kLineEmptyBox = 0x0000ffffu;   // both words: first pixel 65535 > last pixel 0, beyond any target
+hipError_t launch_lines_setup(hipStream_t s, const LineJob* jobs, int numJobs, uint32_t firstJob, uint32_t blocks, const LineArgs& a, void* boxes, void* records);
+hipError_t launch_lines_fill(hipStream_t s, const LineArgs& a, int tile, const void* boxes, const void* records);
+
 // launchers (each returns the hipError_t of the launch)
 hipError_t launch_forward_lighting(hipStream_t s, const ShadeArgs& a, bool hasEnv, bool hasCasters, int outFmt, const Options& opt);
 hipError_t launch_blur_x(hipStream_t s, const void* in, void* out, int W, int H, int fmt, const Options& opt);
